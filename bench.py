@@ -7,8 +7,11 @@ the three Missions — round 6; `--per-mission-launches`: one kernel per Mission
 records packed and joined on the device, exact replay of the regions around long runs on the device ->
 findings in reference order in pinned host memory) over the rank's HBM-resident shard.
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`
-(HIP-event kernel time vs the 8 TB/s HBM peak) and `cpu_baseline` (the oracle, the only
-runnable restatement of the reference, on a bounded sample).
+(HIP-event kernel time of the timed steps vs the 8 TB/s HBM peak).  A plain run sets up, warms up, times `--steps` steps and
+prints that line; `--full` adds what takes runs of its own: every scan kernel launched alone after the timed region
+(`roofline.per_kernel_ms_alone`, `fused.ms_alone`, `frac_alone`), `cpu_baseline` (the oracle, the only runnable restatement of
+the reference, on a bounded sample) and the check of the front end's Missions against tests/refconfig.py.
+`--dump-outputs DIR` writes the last timed step's findings (a seeded sample, and CRCs of them all) as .npy files.
 """
 import argparse
 import json
@@ -60,6 +63,61 @@ def scan_kernel_source_hash():
     return h.hexdigest()[:16]
 
 
+DUMP_SAMPLE = 1 << 19   # findings in the --dump-outputs sample: 8 float64 arrays of this length = 32 MiB
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: what the caller of the timed path receives, one step's findings in reference order, as float64 .npy files
+    that two builds can be compared by.  position, mission_id, precision, completes_previous, input_file_id, str_len and
+    string_crc32 (CRC-32 of the finding's UTF-8 string) hold the findings at sample_index: every finding if there are at most
+    DUMP_SAMPLE, else that many indices drawn with a fixed seed, in order.  digest = [findings, bytes of strings, CRC-32 of
+    every finding's fields above (but the string's), CRC-32 of every string in order].  Frees `res`."""
+    import ctypes
+    import zlib
+    import numpy as np
+    from stringsext_amd import Finding
+    fields = [("position", "<u8"), ("mission_id", "u1"), ("precision", "u1"), ("completes_previous", "u1"),
+              ("input_file_id", "<i2"), ("str_len", "<u4")]
+    names = [f for f, _ in fields]
+    view = np.dtype({"names": names + ["str_off"], "formats": [t for _, t in fields] + ["<u4"],
+                     "offsets": [getattr(Finding, f).offset for f in names + ["str_off"]], "itemsize": ctypes.sizeof(Finding)})
+    total = len(res)
+    idx = np.arange(total) if total <= DUMP_SAMPLE else np.sort(np.random.default_rng(SEED).choice(total, DUMP_SAMPLE, replace=False))
+    cols = {f: [] for f in names + ["string_crc32"]}
+    crc_rec = crc_str = n_str = 0
+    base = 0
+    for fp, n, ap, alen in res.segment_pointers():
+        if not n:
+            continue
+        f = np.ctypeslib.as_array(ctypes.cast(fp, ctypes.POINTER(ctypes.c_uint8)), (n * view.itemsize,)).view(view)
+        arena = ctypes.string_at(ap, alen) if alen else b""
+        packed = np.empty(n, dtype=np.dtype(fields))
+        for name in names:
+            packed[name] = f[name]
+        crc_rec = zlib.crc32(packed.tobytes(), crc_rec)
+        off, ln = f["str_off"].astype(np.int64), f["str_len"].astype(np.int64)
+        n_str += int(ln.sum())
+        if np.array_equal(off[1:], off[:-1] + ln[:-1]):   # the strings lie in finding order, back to back
+            crc_str = zlib.crc32(arena[off[0]:off[-1] + ln[-1]], crc_str)
+        else:
+            for o, l in zip(off.tolist(), ln.tolist()):
+                crc_str = zlib.crc32(arena[o:o + l], crc_str)
+        mine = idx[(idx >= base) & (idx < base + n)] - base
+        for name in names:
+            cols[name].append(packed[name][mine])
+        cols["string_crc32"].append(np.array([zlib.crc32(arena[o:o + l]) for o, l in zip(off[mine].tolist(), ln[mine].tolist())],
+                                             dtype=np.uint32))
+        base += n
+    assert base == total, (base, total)
+    res.free()
+    os.makedirs(out_dir, exist_ok=True)
+    out = {name: np.concatenate(c) if c else np.zeros(0) for name, c in cols.items()}
+    out["sample_index"] = idx
+    out["digest"] = np.array([total, n_str, crc_rec, crc_str])
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -95,7 +153,17 @@ def main():
                     help="strong: the workload's ONE image is split over the ranks — the default for `--gpus N` with N > 1 (BASELINE.json's "
                          "metric: 64 GiB at 1/2/4/8 GPUs); weak: every rank scans the workload's size — the default of `--workload c4` "
                          "(BASELINE config 4: 32 GiB per rank, 256 GiB over eight) and of N = 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: the scan kernels alone, the CPU baseline (unless --no-cpu-baseline), "
+                         "the front end checked against tests/refconfig.py")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the findings of the last timed step to DIR/*.npy (float64; a seeded sample of at most %d findings, "
+                         "CRCs over all of them)" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs writes the result of --gpus 1")
     if args.scaling is None:   # (round 5: the driver's `--gpus N` line is on the metric's configuration; round 4 defaulted to N x 64 GiB)
         args.scaling = "strong" if args.gpus > 1 and args.workload != "c4" else "weak"
 
@@ -112,7 +180,6 @@ def main():
     import torch
     import torch.distributed as dist
 
-    import refconfig as rc
     import stringsext_amd as sx
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -141,7 +208,9 @@ def main():
     if args.chars_min:
         wl = dict(wl, flags=dict(wl["flags"], chars_min=args.chars_min), name=wl["name"].replace("-n %s" % wl["flags"]["chars_min"], "-n " + args.chars_min) + f" [--chars-min {args.chars_min}]")
     missions = sx.missions_from_flags(**wl["flags"])   # the product's front end, from the literal flag strings
-    assert missions == rc.missions(**wl["flags"])      # (the reference's rules restated in tests/refconfig.py: the checker)
+    if args.full:
+        import refconfig as rc
+        assert missions == rc.missions(**wl["flags"])  # (the reference's rules restated in tests/refconfig.py: the checker)
     nbytes = int((args.gib if args.gib is not None else wl["gib"]) * (1 << 30)) // 4096 * 4096
     if args.scaling == "strong":   # ONE image of the workload's size, a byte range of it per rank
         nbytes = nbytes // world // 4096 * 4096
@@ -179,11 +248,14 @@ def main():
 
     timings = {}
 
-    def step():
+    def step(keep=False):
         sc.reset()
         if world == 1:
             res = sc.scan_device(dptr, nbytes, file_id=1)
             n = len(res)
+            if keep:   # --dump-outputs: the last timed step's Result is read after the timed region and freed then
+                state["last"] = res
+                return n, sc.stats()
         else:
             # shard scan + one all_gather over RCCL ("where did everybody start and stop", finding counts), then the
             # gather of the Finding buffers to rank 0 (BASELINE config 4) — all inside the timed region
@@ -220,8 +292,8 @@ def main():
     wave_windows = rescans = seq_pieces = fast_regions = general_regions = 0
     rescan_ms = 0.0
     findings = records = replay_bytes = 0
-    for _ in range(args.steps):
-        n, st = step()
+    for i in range(args.steps):
+        n, st = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
         findings = n
         records = st.run_records
         replay_bytes = st.replay_bytes
@@ -247,13 +319,15 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=xdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, state.pop("last"))
 
-    # outside the timed region: every mission's scan kernel launched alone (nothing else on the
+    # outside the timed region (--full): every mission's scan kernel launched alone (nothing else on the
     # device), for the roofline's "what the kernel can do" next to "what it did in the job"
     alone_ms = []
     alone_warm_ms = []
     fused_alone_ms = None
-    if rank == 0 and not args.no_alone:
+    if rank == 0 and args.full and not args.no_alone:
         for k, m in enumerate(missions):
             mc = max(1, min(m["chars_min_nb"], m["output_line_char_nb_max"]))
             best = None
@@ -383,7 +457,7 @@ def main():
             "sequential_pieces": int(seq_pieces),
             "kernels_only_gib_s": round(world * nbytes / (span_all * 1e-3) / (1 << 30), 1) if span_all > 0 else None,
         }
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             import threading
             import sxo_binding as sxo
 

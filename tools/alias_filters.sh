@@ -3,6 +3,8 @@
 # -> gpurun_out/TAG_bench_c3_ubf_<filter>{,_generic}.json, TAG_ubf_cjk_kernel_stats.csv, pmc_TAG_ubf_cjk_sq.csv
 # (not Asian: two thirds of all UTF-16 units pass it, random bytes are then one string from end to end)
 tag=$1; shift
+# the bench lines below print the scan kernels alone (roofline.per_kernel_ms_alone): a --full figure
+python() { if [ "$1" = bench.py ]; then shift; command python bench.py --full "$@"; else command python "$@"; fi; }
 filters=${@:-Cjk Hangul Kana All}
 for f in $filters; do
   python bench.py --ubf $f --no-cpu-baseline 2>/dev/null < /dev/null | tail -1 > gpurun_out/${tag}_bench_c3_ubf_${f}.json

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Everything profiles/ holds for one commit, in one go on the GPU box: tools/final_profiles.sh TAG  -> gpurun_out/TAG_*
 tag=$1
+# every bench line below records the --full figures (CPU baseline, the scan kernels alone), as before bench.py had the option
+python() { if [ "$1" = bench.py ]; then shift; command python bench.py --full "$@"; else command python "$@"; fi; }
 python bench.py > gpurun_out/${tag}_bench_c3_64gib.json 2> gpurun_out/${tag}_bench_c3.err < /dev/null
 tail -c 600 gpurun_out/${tag}_bench_c3_64gib.json; echo
 # the same Missions with one launch each (rounds 1-5), and the fused launch over the buffer in one piece

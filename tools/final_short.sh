@@ -2,6 +2,8 @@
 # The short form of final_profiles.sh (when the round's GPU minutes are nearly spent): tools/final_short.sh TAG -> gpurun_out/TAG_*
 # the GPU suite, the headline line, its kernel statistics and launch rows, the two traffic passes, one line each of C1 / C2 / C5
 tag=$1
+# every bench line below records the --full figures (CPU baseline, the scan kernels alone), as before bench.py had the option
+python() { if [ "$1" = bench.py ]; then shift; command python bench.py --full "$@"; else command python "$@"; fi; }
 timeout 900 python -m pytest tests -q -m gpu -x 2>&1 | tail -5 > gpurun_out/${tag}_gputests.log; cat gpurun_out/${tag}_gputests.log
 python bench.py > gpurun_out/${tag}_bench_c3_64gib.json 2> gpurun_out/${tag}_bench_c3.err < /dev/null
 tail -c 400 gpurun_out/${tag}_bench_c3_64gib.json; echo

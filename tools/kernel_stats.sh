@@ -6,7 +6,7 @@ name=$1; shift
 repo=$(pwd)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/ks_$name
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$name -o $name -- python $repo/bench.py --no-cpu-baseline "$@" > /tmp/ks_$name.log 2>/tmp/ks_$name.err < /dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$name -o $name -- python $repo/bench.py --full --no-cpu-baseline "$@" > /tmp/ks_$name.log 2>/tmp/ks_$name.err < /dev/null
 cd $repo
 f=$(find /tmp/ks_$name -name '*kernel_stats.csv' | head -1)
 if [ -z "$f" ]; then echo "no kernel_stats.csv under /tmp/ks_$name"; tail -5 /tmp/ks_$name.err; exit 1; fi

@@ -5,7 +5,7 @@ name=$1; shift
 repo=$(pwd)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kt_$name
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_$name -o $name -- python $repo/bench.py --no-cpu-baseline "$@" > /tmp/kt_$name.log 2>/tmp/kt_$name.err < /dev/null
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_$name -o $name -- python $repo/bench.py --full --no-cpu-baseline "$@" > /tmp/kt_$name.log 2>/tmp/kt_$name.err < /dev/null
 cd $repo
 f=$(find /tmp/kt_$name -name '*kernel_trace.csv' | head -1)
 if [ -z "$f" ]; then echo "no kernel_trace.csv"; tail -5 /tmp/kt_$name.err; exit 1; fi

@@ -5,7 +5,7 @@ name=$1; shift; ctrs=$1; shift
 repo=$(pwd)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc_$name
-rocprofv3 --pmc $ctrs --output-format csv -d /tmp/pmc_$name -o $name -- python $repo/bench.py --steps 1 --warmup 0 --no-cpu-baseline "$@" > /tmp/pmc_$name.log 2>&1
+rocprofv3 --pmc $ctrs --output-format csv -d /tmp/pmc_$name -o $name -- python $repo/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "$@" > /tmp/pmc_$name.log 2>&1
 cd $repo
 python - "$name" <<'PY'
 import csv, glob, sys, collections

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {   # NAME bench-args...
   name=$1; shift
   rm -rf /tmp/sr_$name
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/sr_$name -o $name -- python $repo/bench.py --no-cpu-baseline --steps 2 --warmup 1 "$@" > /tmp/sr_$name.log 2>/dev/null < /dev/null
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/sr_$name -o $name -- python $repo/bench.py --full --no-cpu-baseline --steps 2 --warmup 1 "$@" > /tmp/sr_$name.log 2>/dev/null < /dev/null
   f=$(find /tmp/sr_$name -name '*kernel_stats.csv' | head -1)
   if [ -z "$f" ]; then echo "$name: no kernel stats" >> $out; return; fi
   python3 - "$f" "$name" "$*" /tmp/sr_$name.log >> $out <<'PY'

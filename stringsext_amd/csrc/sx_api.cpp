@@ -19,8 +19,7 @@ PinnedPool::Block PinnedPool::take(size_t bytes) {
     }
     Block b;
     const size_t cap = bytes + bytes / 8 + (1u << 20);
-    static const unsigned flags = [] { const char* e = getenv("SX_POOL_PIN_FLAGS"); return e ? (unsigned)strtoul(e, nullptr, 0) : (unsigned)hipHostMallocNonCoherent; }();
-    if (hipHostMalloc(&b.p, cap, flags) != hipSuccess) { b.p = nullptr; return b; }
+    if (hipHostMalloc(&b.p, cap, hipHostMallocNonCoherent) != hipSuccess) { b.p = nullptr; return b; }
     b.cap = cap;
     return b;
 }
@@ -59,20 +58,19 @@ int ensure_pinned(sx_ctx* ctx, uint64_t bytes) {
     ctx->h_pin = nullptr; ctx->h_pin_cap = 0;
     bytes += bytes / 4 + (1u << 20);
     unsigned flags = hipHostMallocNonCoherent;  // CPU-cached: it is only read by the host after a stream sync
-    if (const char* e = getenv("SX_PIN_FLAGS")) flags = (unsigned)strtoul(e, nullptr, 0);
+    if (ctx->sw.pin_flags >= 0) flags = (unsigned)ctx->sw.pin_flags;
     HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_pin, bytes, flags));
     ctx->h_pin_cap = bytes;
     return SX_OK;
 }
-static bool small_copy_on() { const char* e = getenv("SX_SMALL_COPY"); return !(e && !atoi(e)); }
 int read_back_async(sx_ctx* ctx, hipStream_t s, void* pinned_dst, const void* dev_src, size_t bytes) {
-    if (small_copy_on() && bytes <= (1u << 20) && ((((uintptr_t)pinned_dst | (uintptr_t)dev_src | bytes) & 3) == 0))
+    if (ctx->sw.small_copy && bytes <= (1u << 20) && ((((uintptr_t)pinned_dst | (uintptr_t)dev_src | bytes) & 3) == 0))
         HIP_TRY(ctx, launch_small_copy(pinned_dst, dev_src, bytes, s));
     else HIP_TRY(ctx, hipMemcpyAsync(pinned_dst, dev_src, bytes, hipMemcpyDeviceToHost, s));
     return SX_OK;
 }
 int read_back_sync(sx_ctx* ctx, MissionDev& d, hipStream_t s, void* host_dst, const void* dev_src, size_t bytes) {
-    if (!small_copy_on() || bytes > kSmallReadBytes || ((((uintptr_t)dev_src | bytes) & 3) != 0)) {
+    if (!ctx->sw.small_copy || bytes > kSmallReadBytes || ((((uintptr_t)dev_src | bytes) & 3) != 0)) {
         HIP_TRY(ctx, hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
         return SX_OK;
@@ -158,7 +156,7 @@ unsigned replay_threads(const sx_ctx* ctx) {
     // a few threads per usable CPU smooth out the quota's time slicing (measured: 4x is best)
     unsigned n = ctx->opt.replay_threads ? ctx->opt.replay_threads
                                          : std::min(std::thread::hardware_concurrency(), 4 * usable_cpus());
-    if (const char* e = getenv("SX_REPLAY_THREADS")) n = (unsigned)atoi(e);
+    if (ctx->sw.replay_threads) n = (unsigned)ctx->sw.replay_threads;
     if (n < 1) n = 1;
     return n > 256 ? 256 : n;
 }
@@ -206,7 +204,7 @@ const uint32_t* sx_wave_pair_codes(const sx_mission* mission, uint32_t* out8192)
     if (!mission || !out8192) return nullptr;
     Mission m;
     std::string err;
-    if (Mission::from_c(*mission, false, &m, &err) != SX_OK || m.wave_pairs.size() != 8192) return nullptr;
+    if (Mission::from_c(*mission, false, Switches{}.wave_same, &m, &err) != SX_OK || m.wave_pairs.size() != 8192) return nullptr;
     memcpy(out8192, m.wave_pairs.data(), 8192 * 4);
     return out8192;
 }
@@ -215,7 +213,7 @@ const uint32_t* sx_wave_pair_codes2(const sx_mission* mission, uint32_t* out4096
     if (!mission || !out4096) return nullptr;
     Mission m;
     std::string err;
-    if (Mission::from_c(*mission, false, &m, &err) != SX_OK || m.wave_pairs2.size() != 4096) return nullptr;
+    if (Mission::from_c(*mission, false, Switches{}.wave_same, &m, &err) != SX_OK || m.wave_pairs2.size() != 4096) return nullptr;
     memcpy(out4096, m.wave_pairs2.data(), 4096 * 4);
     return out4096;
 }
@@ -224,7 +222,7 @@ int sx_wave_swar(const sx_mission* mission, uint32_t* out26) {
     if (!mission || !out26) return SX_E_INVALID;
     Mission m;
     std::string err;
-    const int rc = Mission::from_c(*mission, false, &m, &err);
+    const int rc = Mission::from_c(*mission, false, Switches{}.wave_same, &m, &err);
     if (rc != SX_OK) return rc;
     static_assert(sizeof(WvSwar) == 26 * 4, "sx_wave_swar hands the struct out as 26 words");
     memcpy(out26, &m.wave_swar, sizeof(WvSwar));
@@ -235,7 +233,7 @@ int sx_scan_classifier(const sx_mission* mission, int generic, uint32_t* out20) 
     if (!mission || !out20) return SX_E_INVALID;
     Mission m;
     std::string err;
-    const int rc = Mission::from_c(*mission, generic != 0, &m, &err);
+    const int rc = Mission::from_c(*mission, generic != 0, Switches{}.wave_same, &m, &err);
     if (rc != SX_OK) return rc;
     const ScanParams& p = m.proto;
     const uint32_t head[7] = { p.a_lo, p.a_hi, p.u_lo, p.u_hi, p.l3_lo, p.l3_hi, p.n_ranges };
@@ -250,7 +248,7 @@ int sx_wave_classes(const sx_mission* mission, uint8_t* classes) {
     if (!mission || !classes) return SX_E_INVALID;
     Mission m;
     std::string err;
-    const int rc = Mission::from_c(*mission, false, &m, &err);
+    const int rc = Mission::from_c(*mission, false, Switches{}.wave_same, &m, &err);
     if (rc != SX_OK) return rc;
     if (!m.wave_ok || m.wave_lead_check || (m.wave_lut.size() != 256 && !(m.wave_family == 2 && m.wave_lut.size() == 512))) return 0;   // (wave_lead_check: -r, covered per buffer only)
     memcpy(classes, m.wave_lut.data(), m.wave_lut.size());   // (UTF-16: 512 bytes)
@@ -260,13 +258,14 @@ int sx_wave_classes(const sx_mission* mission, uint8_t* classes) {
 int sx_create(sx_ctx** out, const sx_mission* missions, int n_missions, int hip_device, const sx_options* opt) {
     if (!out || !missions || n_missions <= 0 || n_missions > 26) { g_create_error = "bad arguments"; return SX_E_INVALID; }
     sx_ctx* ctx = new sx_ctx();
+    ctx->sw = Switches::from_env();   // the one reading of the environment: everything below the C-ABI asks ctx->sw
     if (opt) ctx->opt = *opt;
-    if (const char* e = getenv("SX_RESULT_ON_DEVICE")) if (atoi(e)) ctx->opt.flags |= SX_OPT_RESULT_ON_DEVICE;   // (tests / fuzz: the flag through the environment)
+    if (ctx->sw.result_on_device) ctx->opt.flags |= SX_OPT_RESULT_ON_DEVICE;   // (tests / fuzz: the flag through the environment)
     ctx->missions.resize((size_t)n_missions);
     ctx->states.resize((size_t)n_missions);
     for (int k = 0; k < n_missions; k++) {
         std::string err;
-        int rc = Mission::from_c(missions[k], (ctx->opt.flags & SX_OPT_GENERIC_KERNELS) != 0, &ctx->missions[(size_t)k], &err);
+        int rc = Mission::from_c(missions[k], (ctx->opt.flags & SX_OPT_GENERIC_KERNELS) != 0, ctx->sw.wave_same, &ctx->missions[(size_t)k], &err);
         if (rc != SX_OK) { g_create_error = "mission " + std::to_string(k) + ": " + err; delete ctx; return rc; }
         ctx->states[(size_t)k].reset(ctx->missions[(size_t)k]);
     }
@@ -293,18 +292,22 @@ int sx_create(sx_ctx** out, const sx_mission* missions, int n_missions, int hip_
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, hip_device) == hipSuccess && cus > 0) ctx->n_cus = (unsigned)cus;
-        if (const char* e2 = getenv("SX_SCAN_BLOCKS_PER_CU")) ctx->scan_blocks_per_cu = (unsigned)atoi(e2);
-        if (const char* e2 = getenv("SX_REGION_CAP")) ctx->region_cap = (uint32_t)atoi(e2);
-        if (const char* e2 = getenv("SX_SCAN_CUS")) ctx->n_cus = (unsigned)std::max(1, atoi(e2));  // tests: persistent grid on small inputs
+        if (ctx->sw.scan_blocks_per_cu >= 0) ctx->scan_blocks_per_cu = (unsigned)ctx->sw.scan_blocks_per_cu;
+        if (ctx->sw.region_cap >= 0) ctx->region_cap = (uint32_t)ctx->sw.region_cap;
+        if (ctx->sw.scan_cus) ctx->n_cus = (unsigned)ctx->sw.scan_cus;  // tests: persistent grid on small inputs
     }
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);  // numerically lower = higher priority
-    if (const char* e = getenv("SX_PRIO")) { (void)sscanf(e, "%d,%d", &prio_lo, &prio_hi); fprintf(stderr, "[sx] stream priorities: scan %d, post %d\n", prio_lo, prio_hi); }
+    if (ctx->sw.prio_n >= 0) {
+        if (ctx->sw.prio_n >= 1) prio_lo = ctx->sw.prio_scan;
+        if (ctx->sw.prio_n >= 2) prio_hi = ctx->sw.prio_post;
+        fprintf(stderr, "[sx] stream priorities: scan %d, post %d\n", prio_lo, prio_hi);
+    }
     // Two streams for the whole context: the scan kernels of all missions queue up in one (a
     // kernel alone already fills the device, and HIP multiplexes streams onto few hardware
     // queues: more streams only alias), everything else runs in a second, higher-priority one
     // so that it overlaps the scans of the next piece.  SX_OPT_MISSION_STREAMS: a scan stream per mission.
-    const bool per_mission = (ctx->opt.flags & SX_OPT_MISSION_STREAMS) || getenv("SX_MISSION_STREAMS");
+    const bool per_mission = (ctx->opt.flags & SX_OPT_MISSION_STREAMS) || ctx->sw.mission_streams;
     if ((e = hipStreamCreateWithPriority(&ctx->post_stream, hipStreamNonBlocking, prio_hi)) != hipSuccess) return fail("hipStreamCreate", e);
     if (!per_mission && (e = hipStreamCreateWithPriority(&ctx->scan_stream, hipStreamNonBlocking, prio_lo)) != hipSuccess)
         return fail("hipStreamCreate", e);
@@ -408,6 +411,7 @@ int sx_device_runs(sx_ctx* ctx, int mission_index, const void* device_bytes, uin
                    uint64_t min_chars, sx_run** runs, uint64_t* n_runs) {
     if (!ctx || !runs || !n_runs || mission_index < 0 || (size_t)mission_index >= ctx->missions.size()) return SX_E_INVALID;
     begin_call(ctx);
+    ctx->sw.scan_warm = Switches::from_env().scan_warm;   // (the one switch read after sx_create, sx_switches.hpp: measurements set it around this call on a live context)
     if (ctx->host_only) { ctx->err = "host-only context: no device scan"; return SX_E_STATE; }
     if ((uintptr_t)device_bytes & 15) { ctx->err = "device_bytes must be 16-byte aligned"; return SX_E_INVALID; }
     if (ctx->missions[(size_t)mission_index].host_sequential()) { ctx->err = "an ISO-2022-JP mission has no stage A (one sequential pass on the host)"; return SX_E_INVALID; }
@@ -650,11 +654,11 @@ int sx_device_read_bandwidth(sx_ctx* ctx, const void* device_bytes, uint64_t len
     // repeats < 0: probe with the scan kernels' traversal (private sub-chunk per wavefront) instead of grid-stride
     const uint32_t sub = repeats < 0 ? (ctx->opt.subchunk_bytes ? ctx->opt.subchunk_bytes : 256u * 1024u) : 0u;
     if (repeats < 0) repeats = -repeats;
-    HIP_TRY(ctx, launch_read_sum((const uint8_t*)device_bytes, len, d_out, d.stream, sub));  // warm-up
+    HIP_TRY(ctx, launch_read_sum((const uint8_t*)device_bytes, len, d_out, d.stream, sub, ctx->sw.probe_rot));  // warm-up
     float best = 1e30f;
     for (int i = 0; i < repeats; i++) {
         HIP_TRY(ctx, hipEventRecord(d.slot[0].ev0, d.stream));
-        HIP_TRY(ctx, launch_read_sum((const uint8_t*)device_bytes, len, d_out, d.stream, sub));
+        HIP_TRY(ctx, launch_read_sum((const uint8_t*)device_bytes, len, d_out, d.stream, sub, ctx->sw.probe_rot));
         HIP_TRY(ctx, hipEventRecord(d.slot[0].ev1, d.stream));
         HIP_TRY(ctx, hipStreamSynchronize(d.stream));
         float ms = 0;

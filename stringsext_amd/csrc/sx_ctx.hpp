@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "sx_host.hpp"
+#include "sx_switches.hpp"
 
 namespace sx {
 
@@ -149,6 +150,7 @@ struct sx_ctx {
     bool sharded_call = false, single_piece = true;   // (SX_OPT_RESULT_ON_DEVICE applies to plain scans of one piece only)
     int device = -1;
     sx_options opt{};
+    sx::Switches sw;   // the SX_* switches as sx_create found them (sx_switches.hpp)
     std::string err;
     sx_stats stats{};
     hipStream_t scan_stream = nullptr, post_stream = nullptr;

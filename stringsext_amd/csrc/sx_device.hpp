@@ -142,7 +142,8 @@ size_t replay_heads_scratch_bytes(uint64_t n_runs);
 hipError_t launch_replay_heads(const ReplayParams& P, uint32_t* slot_of, uint32_t* n_heads, uint32_t* head_list, ReplayRegionOut* ro,
                                void* scratch, size_t scratch_bytes,
                                hipStream_t stream);
-hipError_t launch_replay_count(const ReplayParams& P, ReplayRegionOut* out, hipStream_t stream);
+// (count_waves: Switches::count_waves, wavefronts per SIMD the cached kernel is built for: 4 / 6 / 8)
+hipError_t launch_replay_count(const ReplayParams& P, ReplayRegionOut* out, hipStream_t stream, int count_waves);
 // Does the fast pre-pass cover this Mission?  (UTF-8, no -g / -r, 1 <= n <= q: a run is one stretch of accepted characters and
 // SplitStr never abandons a call's text.)
 bool replay_fast_covers(const ReplayParams& P);
@@ -159,18 +160,19 @@ hipError_t launch_split_write(const ReplayParams& P, const void* scratch, uint64
 // "which regions stand" + output offsets on the device (sx_replay_dev.hip)
 // runs resolved per lane in the first stage of the stitch: the second stage is one wavefront walking the block
 // summaries, so with many runs (string-dense input) larger blocks keep that walk short
-inline uint32_t stitch_block_runs(uint64_t n_runs) {
-    if (const char* e = getenv("SX_STITCH_BLOCK")) { const int v = atoi(e); if (v > 0) return (uint32_t)v; }  // tests
+// (block_override: Switches::stitch_block, 0 = none)
+inline uint32_t stitch_block_runs(uint64_t n_runs, int block_override) {
+    if (block_override > 0) return (uint32_t)block_override;
     return n_runs > (1ull << 20) ? 512u : 128u;
 }
 enum : uint32_t { kTotEnd = 0, kTotLast, kTotFindings, kTotBytes, kTotStanding, kTotReplayBytes, kTotTooLong, kTotLastStart, kTotCount };
 size_t stitch_scratch_bytes(uint64_t n_runs);
-size_t stitch_blocks_bytes(uint64_t n_runs);
+size_t stitch_blocks_bytes(uint64_t n_runs, int block_override);
 hipError_t launch_stitch_blocks(const ReplayParams& P, const ReplayRegionOut* ro, uint8_t* stands, void* blocks,
-                                uint64_t* totals, hipStream_t stream);
+                                uint64_t* totals, hipStream_t stream, int block_override);
 hipError_t launch_stitch_finish(const ReplayParams& P, const ReplayRegionOut* ro, uint8_t* stands, const void* blocks,
                                 uint64_t E0, uint64_t* fpos, uint64_t* apos, uint64_t* totals, void* scratch,
-                                size_t scratch_bytes, hipStream_t stream);
+                                size_t scratch_bytes, hipStream_t stream, int block_override);
 hipError_t launch_replay_write_flagged(const ReplayParams& P, const ReplayRegionOut* ro, const uint8_t* stands,
                                        const uint64_t* fpos, const uint64_t* apos, sx_finding* findings,
                                        uint8_t* arena, uint64_t avg_out_bytes, hipStream_t stream);
@@ -255,13 +257,15 @@ hipError_t launch_slab_cuts(const ReplayParams& P, uint32_t n_slabs, uint64_t* i
 hipError_t launch_merge_cuts(const sx_finding* f, uint64_t n, uint64_t nb, const uint64_t* cuts, uint32_t n_cuts, uint64_t* idx,
                              uint64_t* off, hipStream_t stream);
 size_t merge_findings_scratch_bytes(uint64_t n_findings, int n_missions);
-hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream);
+// (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
+hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit
 hipError_t launch_small_copy(void* pinned_dst, const void* dev_src, size_t bytes, hipStream_t stream);
 
 // order run records by start on the device (sx_sort.hip); unused slots end up last with start = ~0
 size_t sort_scratch_bytes(uint32_t n);
-hipError_t sort_records(DevRun* recs, uint32_t n, uint64_t max_key, void* scratch, size_t scratch_bytes, hipStream_t stream);
+// (timing: Switches::timing2, a time stamp on stderr after every step, each behind a stream sync)
+hipError_t sort_records(DevRun* recs, uint32_t n, uint64_t max_key, void* scratch, size_t scratch_bytes, hipStream_t stream, bool timing);
 
 // region mode: records of all sub-chunks, in order, packed into `out`; *total = their number
 size_t compact_scratch_bytes(uint64_t n_regions);
@@ -288,10 +292,12 @@ struct FusedParams {
     uint32_t pf_zero[kFusedMax];      // prefilter slots: the bits that are clear in the high byte of every accepted unit
 };
 int fused_slot_of(ClassifierKind kind, const ScanParams& p);
-hipError_t launch_scan_fused(const FusedParams& fp, uint32_t used, hipStream_t stream);
+// (prefilter_override: Switches::fused_prefilter, 0: no prefilter, 2: pairs only, anything else: the kernel's own choice)
+hipError_t launch_scan_fused(const FusedParams& fp, uint32_t used, hipStream_t stream, int prefilter_override);
 hipError_t launch_fill_background(uint8_t* dst, uint64_t first_index, uint64_t len, uint64_t seed,
                                   hipStream_t stream);
-hipError_t launch_read_sum(const uint8_t* src, uint64_t len, uint64_t* out, hipStream_t stream, uint32_t subchunk = 0);
+// (subchunk != 0: the scan kernels' traversal, wavefront w beginning at tile w * rot of its sub-chunk — Switches::probe_rot)
+hipError_t launch_read_sum(const uint8_t* src, uint64_t len, uint64_t* out, hipStream_t stream, uint32_t subchunk = 0, uint32_t rot = 0);
 // dst[seg_dst[i] .. ] = src[seg_src[i] .. seg_src[i]+seg_len[i]) for i < n
 hipError_t launch_gather(const uint8_t* src, uint8_t* dst, const uint64_t* seg_src, const uint64_t* seg_dst,
                          const uint32_t* seg_len, uint32_t n, hipStream_t stream);

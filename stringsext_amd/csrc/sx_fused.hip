@@ -444,7 +444,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PFM ? 6 : 5
 }
 
 template <class C0, class C1, class C2>
-static hipError_t launch_f(const FusedParams& fp, uint32_t used, hipStream_t stream) {
+static hipError_t launch_f(const FusedParams& fp, uint32_t used, hipStream_t stream, int prefilter_override) {
     const u64 waves = (fp.len + fp.subchunk - 1) / fp.subchunk;
     const u64 blocks = (waves + 3) / 4;
     if (blocks == 0) return hipSuccess;
@@ -454,7 +454,7 @@ static hipError_t launch_f(const FusedParams& fp, uint32_t used, hipStream_t str
     if ((used & 2u) && Prefilter<C1>::mode_for(fp.m[1]) != 1) mode = Prefilter<C1>::mode_for(fp.m[1]);
     if ((used & 4u) && mode && Prefilter<C2>::mode_for(fp.m[2]) != 1) mode = Prefilter<C2>::mode_for(fp.m[2]) == 0 ? 0 : 2;
     if (!(used & 6u)) mode = 0;
-    if (const char* e = getenv("SX_FUSED_PREFILTER")) { const int v = atoi(e); if (v == 0) mode = 0; else if (v == 2 && mode == 1) mode = 2; }
+    if (prefilter_override == 0) mode = 0; else if (prefilter_override == 2 && mode == 1) mode = 2;
     q.pf_zero[0] = 0; q.pf_zero[1] = Prefilter<C1>::zero_bits(fp.m[1]); q.pf_zero[2] = Prefilter<C2>::zero_bits(fp.m[2]);
     if (mode == 1) hipLaunchKernelGGL((scan_kernel_fused<C0, C1, C2, 1>), dim3((unsigned)blocks), dim3(256), 0, stream, q);
     else if (mode == 2) hipLaunchKernelGGL((scan_kernel_fused<C0, C1, C2, 2>), dim3((unsigned)blocks), dim3(256), 0, stream, q);
@@ -472,7 +472,7 @@ int fused_slot_of(ClassifierKind kind, const ScanParams& p) {
 }
 
 // used: bit s set = slot s holds a Mission (fp.m[s]); the others are ignored.  All used slots share data, len and subchunk.
-hipError_t launch_scan_fused(const FusedParams& fp, uint32_t used, hipStream_t stream) {
+hipError_t launch_scan_fused(const FusedParams& fp, uint32_t used, hipStream_t stream, int prefilter_override) {
     u32 parity = 0;
     if (used & 2u) parity = fp.m[1].parity & 1u; else if (used & 4u) parity = fp.m[2].parity & 1u;
     FusedParams q = fp;
@@ -490,7 +490,7 @@ hipError_t launch_scan_fused(const FusedParams& fp, uint32_t used, hipStream_t s
         q.fsh[s][0] = sh0; q.fsh[s][1] = sh1; q.fsh[s][2] = sh2; q.fsh[s][3] = sh3;
     }
 #define SX_ARG(...) __VA_ARGS__
-#define SX_F(U, P, A, B, C) if (used == U && parity == P) return launch_f<A, B, C>(q, used, stream);
+#define SX_F(U, P, A, B, C) if (used == U && parity == P) return launch_f<A, B, C>(q, used, stream, prefilter_override);
     SX_F(1u, 0u, Utf8Range2, NoCls, NoCls)   // (one Mission: the fast loop alone is worth it — 82 instead of 91 vector instructions per tile)
     SX_F(7u, 0u, Utf8Range2, SX_ARG(Utf16RangeT<0, 0>), SX_ARG(Utf16RangeT<1, 0>))
     SX_F(7u, 1u, Utf8Range2, SX_ARG(Utf16RangeT<0, 1>), SX_ARG(Utf16RangeT<1, 1>))

@@ -76,7 +76,8 @@ struct Mission {
     // Big5 / EUC-JP, per buffer (set by the schedule before stage A/B of a buffer; the replay only reads it):
     // how many bytes at the buffer start finish the token that was pending on entry — where its token grid begins
     mutable uint32_t buf_entry_skip = 0;
-    static int from_c(const sx_mission& in, bool force_generic, Mission* out, std::string* err);
+    // (wave_same_on: Switches::wave_same — -r inside the wave kernels; off: Missions with -r as before round 5)
+    static int from_c(const sx_mission& in, bool force_generic, bool wave_same_on, Mission* out, std::string* err);
 };
 
 // ---------------------------------------------------------------------------------------
@@ -304,7 +305,8 @@ struct Result {
     // one contiguous findings array + arena (copies if there are several segments)
     bool flatten(std::string* err);
 };
-void merge_findings(std::vector<MissionFindings>& per_mission, const std::shared_ptr<PinnedPool>& pool, Result* out);
+// (seg_bytes: Switches::host_merge_seg_bytes, string bytes per output segment; 0: as many as str_off can address)
+void merge_findings(std::vector<MissionFindings>& per_mission, const std::shared_ptr<PinnedPool>& pool, Result* out, uint64_t seg_bytes);
 
 // Finding::print — src/finding.rs:112-155
 void print_findings(const std::vector<Mission>& missions, const Result& r, int n_inputs, int radix, bool no_metadata,

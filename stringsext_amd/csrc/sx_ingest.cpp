@@ -217,7 +217,7 @@ int sx_scan(sx_ctx* ctx, const uint8_t* bytes, uint64_t len, int input_file_id, 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // Measured (4 GiB, MI355X box): one hipMemcpy from pageable memory + one scan moves 50 GiB/s, the
     // chunked pipeline below 34 GiB/s (its staging memcpy is the bottleneck) — so it is opt-in.
-    const uint64_t stream_from = getenv("SX_SCAN_STREAM_MIB") ? (uint64_t)atoll(getenv("SX_SCAN_STREAM_MIB")) << 20 : 0;
+    const uint64_t stream_from = ctx->sw.scan_stream_mib << 20;
     if (stream_from >= kInputBufLen && len >= 2 * stream_from) {
         // the ingest pipeline: pinned staging, the copy of one chunk overlapped with the scan of
         // the chunk before; one result with a segment per chunk
@@ -269,7 +269,7 @@ int sx_scan_file(sx_ctx* ctx, const char* path, uint64_t chunk_bytes, int input_
     if (fr.fd < 0) { ctx->err = std::string("cannot open `") + path + "`: " + strerror(errno); return SX_E_INVALID; }
     struct stat st;
     if (fr.fd > 0 && fstat(fr.fd, &st) == 0 && S_ISREG(st.st_mode)) { fr.seekable = true; fr.size = (uint64_t)st.st_size; }
-    if (fr.seekable && fr.size > 0 && getenv("SX_INGEST_MMAP")) {
+    if (fr.seekable && fr.size > 0 && ctx->sw.ingest_mmap) {
         // opt-in: map the file and copy to HBM straight from the page cache.  Measured slower than the
         // pread threads + pinned staging (19 vs 27 GiB/s on 16 GiB): the page faults of the mapping cost more
         // than the staging copy.

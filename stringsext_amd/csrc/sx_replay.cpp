@@ -626,7 +626,7 @@ void merge_sorted_device_runs(const DevRun* v, size_t n, uint64_t min_chars, std
 
 // Interleave the missions' findings of one buffer (src/main.rs k-merge order: slice by slice,
 // position, then mission) and append them to `out` as one more segment.
-void merge_findings(std::vector<MissionFindings>& per, const std::shared_ptr<PinnedPool>& pool, Result* out) {
+void merge_findings(std::vector<MissionFindings>& per, const std::shared_ptr<PinnedPool>& pool, Result* out, uint64_t seg_bytes) {
     out->pool = pool;
     size_t nonempty = 0, which = 0;
     for (size_t k = 0; k < per.size(); k++) if (per[k].count()) { nonempty++; which = k; }
@@ -647,8 +647,7 @@ void merge_findings(std::vector<MissionFindings>& per, const std::shared_ptr<Pin
     size_t total = 0, bytes = 0;
     for (auto& mf : per) { total += mf.count(); bytes += mf.strings_len(); }
     std::vector<size_t> idx(per.size(), 0);
-    uint64_t seg_cap = 0xFFFFFFF0ull;
-    if (const char* e = getenv("SX_HOST_MERGE_SEG_BYTES")) seg_cap = std::max<uint64_t>(1, (uint64_t)atoll(e));   // (tests: results of several segments without gigabytes of strings)
+    const uint64_t seg_cap = seg_bytes ? seg_bytes : 0xFFFFFFF0ull;   // (tests: results of several segments without gigabytes of strings)
     if (bytes <= seg_cap) {   // the usual case: the arenas are copied whole, the offsets rebased
         out->segs.emplace_back();
         MissionFindings& m = out->segs.back();

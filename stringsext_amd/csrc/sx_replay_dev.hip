@@ -575,25 +575,25 @@ size_t stitch_scratch_bytes(uint64_t n_runs) {
     (void)rocprim::exclusive_scan(nullptr, a, it, (u64*)nullptr, (u64)0, (size_t)n_runs, rocprim::plus<u64>(), (hipStream_t)0);
     return a + 512;
 }
-uint64_t stitch_block_count(uint64_t n_runs) { const uint64_t k = stitch_block_runs(n_runs); return (n_runs + k - 1) / k; }
-size_t stitch_blocks_bytes(uint64_t n_runs) { return stitch_block_count(n_runs) * sizeof(StitchBlock) + 64; }
+uint64_t stitch_block_count(uint64_t n_runs, int block_override) { const uint64_t k = stitch_block_runs(n_runs, block_override); return (n_runs + k - 1) / k; }
+size_t stitch_blocks_bytes(uint64_t n_runs, int block_override) { return stitch_block_count(n_runs, block_override) * sizeof(StitchBlock) + 64; }
 
 // stage 1 (no dependency on the entry region): the blocks' own chains.  totals must be zeroed.
 hipError_t launch_stitch_blocks(const ReplayParams& P, const ReplayRegionOut* ro, uint8_t* stands, void* blocks,
-                                uint64_t* totals, hipStream_t stream) {
+                                uint64_t* totals, hipStream_t stream, int block_override) {
     if (P.n_runs == 0) return hipSuccess;
-    const u64 nb = stitch_block_count(P.n_runs);
+    const u64 nb = stitch_block_count(P.n_runs, block_override);
     hipLaunchKernelGGL(stitch_blocks_kernel, dim3((unsigned)nb), dim3(64), 0, stream, P, ro, stands,
-                       (StitchBlock*)blocks, nb, stitch_block_runs(P.n_runs), totals);
+                       (StitchBlock*)blocks, nb, stitch_block_runs(P.n_runs, block_override), totals);
     return hipGetLastError();
 }
 // stage 2: chain the blocks from E0 (end of the host's entry region), assign output offsets, totals
 hipError_t launch_stitch_finish(const ReplayParams& P, const ReplayRegionOut* ro, uint8_t* stands, const void* blocks,
                                 uint64_t E0, uint64_t* fpos, uint64_t* apos, uint64_t* totals, void* scratch,
-                                size_t scratch_bytes, hipStream_t stream) {
+                                size_t scratch_bytes, hipStream_t stream, int block_override) {
     if (P.n_runs == 0) return hipSuccess;
-    const u64 nb = stitch_block_count(P.n_runs);
-    hipLaunchKernelGGL(stitch_chain_kernel, dim3(1), dim3(64), 0, stream, P, ro, stands, (const StitchBlock*)blocks, nb, stitch_block_runs(P.n_runs), E0, totals);
+    const u64 nb = stitch_block_count(P.n_runs, block_override);
+    hipLaunchKernelGGL(stitch_chain_kernel, dim3(1), dim3(64), 0, stream, P, ro, stands, (const StitchBlock*)blocks, nb, stitch_block_runs(P.n_runs, block_override), E0, totals);
     void* tmp = (void*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
     size_t tmp_bytes = scratch_bytes - (size_t)((uint8_t*)tmp - (uint8_t*)scratch);
     auto itf = rocprim::make_transform_iterator(rocprim::counting_iterator<u64>(0), StandingFindings{ stands, ro });
@@ -653,13 +653,12 @@ hipError_t launch_replay_heads(const ReplayParams& P, uint32_t* slot_of, uint32_
     hipLaunchKernelGGL(replay_heads_total_kernel, dim3(1), dim3(1), 0, stream, head + (P.n_runs - 1), slot_of + (P.n_runs - 1), n_heads);
     return hipGetLastError();
 }
-hipError_t launch_replay_count(const ReplayParams& P, ReplayRegionOut* out, hipStream_t stream) {
+hipError_t launch_replay_count(const ReplayParams& P, ReplayRegionOut* out, hipStream_t stream, int waves) {
     if (P.n_runs == 0) return hipSuccess;
     dim3 grid((unsigned)((P.n_runs + 63) / 64));
     const bool cache = P.cache_arena != nullptr;
     if (cache && P.hard_list && grid.x > 4096u) grid.x = 4096u;   // (behind the fast pre-pass: a short list, walked by a bounded grid)
     const unsigned lds = 64u * win_row_bytes(P.W);
-    static const int waves = [] { const char* e = getenv("SX_COUNT_WAVES"); return e ? atoi(e) : 4; }();
 #define SX_LAUNCH_COUNT(E)                                                                                              \
     do {                                                                                                                \
         if (!cache) hipLaunchKernelGGL((replay_count_kernel<E>), grid, dim3(64), 0, stream, P, out);                     \

@@ -18,13 +18,11 @@ namespace sx {
 uint64_t piece_bytes(const sx_ctx* ctx, uint64_t len) {
     uint64_t piece = 0;
     bool halves = false;
-    if (const char* e = getenv("SX_PIECE_MIB")) piece = (uint64_t)atoll(e) << 20;
+    if (ctx->sw.piece_mib >= 0) piece = (uint64_t)ctx->sw.piece_mib << 20;
     else if (len >= (16ull << 30) && ctx->missions.size() >= 2 && !(ctx->opt.flags & (SX_OPT_NO_FUSED_SCAN | SX_OPT_MISSION_STREAMS | SX_OPT_RESULT_ON_DEVICE))) {
         // (the first piece the larger one: its stage B must fit under the second piece's scan, and what follows the second piece's
-        // scan — its own stage B and copy — is the step's tail; SX_PIECE_FRAC: percent of the buffer in the first piece)
-        uint64_t pct = 50;
-        if (const char* e = getenv("SX_PIECE_FRAC")) pct = (uint64_t)std::min(95, std::max(5, atoi(e)));
-        piece = ((len / 100) * pct + kInputBufLen - 1) / kInputBufLen * kInputBufLen;
+        // scan — its own stage B and copy — is the step's tail: half the buffer each)
+        piece = ((len / 100) * 50 + kInputBufLen - 1) / kInputBufLen * kInputBufLen;
         halves = true;
     }
     if (piece == 0 || (!halves && len < 2 * piece)) return len;
@@ -43,11 +41,11 @@ uint64_t piece_bytes(const sx_ctx* ctx, uint64_t len) {
 // the merger (2.25 GB); the first buffer of a stream is scanned in one go.  SX_SEQ_PIECE_MIB / SX_SEQ_PIECE_KIB set the size (0: never).
 static uint64_t seq_piece_bytes(const sx_ctx* ctx, uint64_t len) {
     uint64_t piece = 0;
-    if (const char* e = getenv("SX_SEQ_PIECE_KIB")) {   // (tests: small buffers)
-        piece = (uint64_t)atoll(e) << 10;
+    if (ctx->sw.seq_piece_kib >= 0) {   // (tests: small buffers)
+        piece = (uint64_t)ctx->sw.seq_piece_kib << 10;
         if (piece == 0) return len;
-    } else if (const char* e = getenv("SX_SEQ_PIECE_MIB")) {
-        piece = (uint64_t)atoll(e) << 20;
+    } else if (ctx->sw.seq_piece_mib >= 0) {
+        piece = (uint64_t)ctx->sw.seq_piece_mib << 20;
         if (piece == 0) return len;
     } else {
         if (ctx->missions.size() < 2 || ctx->out_density <= 0) return len;
@@ -76,7 +74,7 @@ static int entry_param(sx_ctx* ctx, size_t k, const Decoder* carried, const uint
     else HIP_TRY(ctx, hipMemcpy(first, d_bytes, n, hipMemcpyDeviceToHost));
     *out = carried->entry_skip_scan(first, n);                     // for the scan kernel (its own grammar for gb18030)
     if (out_replay) *out_replay = carried->entry_skip(first, n);   // for the replay: the true token grid
-    if (getenv("SX_DEBUG_ENTRY")) { const DDecoder& dd = const_cast<Decoder*>(carried)->raw(); fprintf(stderr, "[sx] entry mission %zu: dlead %02x gb2 %02x gb3 %02x rq_n %u first %02x %02x -> scan %u replay %u\n", k, dd.dlead, dd.gb2, dd.gb3, dd.rq_n, first[0], first[1], *out, out_replay ? *out_replay : 0u); }
+    if (ctx->sw.debug_entry) { const DDecoder& dd = const_cast<Decoder*>(carried)->raw(); fprintf(stderr, "[sx] entry mission %zu: dlead %02x gb2 %02x gb3 %02x rq_n %u first %02x %02x -> scan %u replay %u\n", k, dd.dlead, dd.gb2, dd.gb3, dd.rq_n, first[0], first[1], *out, out_replay ? *out_replay : 0u); }
     return SX_OK;
 }
 int set_entry_params(sx_ctx* ctx, bool carried_state_is_entry, const uint8_t* host_bytes, const uint8_t* d_bytes, uint64_t len,
@@ -108,8 +106,7 @@ void mission_order(sx_ctx* ctx, std::vector<int>* out) {
     // (= the scans alone, 34.5 ms, plus the 6.0 ms stage B takes on an idle chip).  With round 4's scan kernels second to last was
     // the best (38.1): they were bound by VALU issue and lost to stage B what it won; the round-5 kernels issue a tenth fewer
     // instructions per tile and keep two tiles in flight.
-    int mode = 0;
-    if (const char* e = getenv("SX_BUSIEST_LAST")) mode = atoi(e);
+    const int mode = ctx->sw.busiest_last;
     if (mode) std::reverse(order.begin(), order.end());
     if (mode == 2 && nm >= 3) std::swap(order[nm - 1], order[nm - 2]);
 }
@@ -134,8 +131,8 @@ struct BufferScan {
     // A Mission whose last whole buffer was string-dense and went through the wave kernels (sx_wave.cpp) does without stage A
     // for the next one: its stage B replays every window anyway, and says afterwards whether the buffer was dense again.
     bool skip_scan(const sx_ctx* ctx, size_t k) const {
-        return whole && len >= 2 * kInputBufLen && k < ctx->wave_pred.size() && ctx->wave_pred[k] && ctx->missions[k].wave_ok && !getenv("SX_WAVE_KEEP_SCAN")
-               && !(getenv("SX_WAVE_REPLAY") && !atoi(getenv("SX_WAVE_REPLAY")));
+        return whole && len >= 2 * kInputBufLen && k < ctx->wave_pred.size() && ctx->wave_pred[k] && ctx->missions[k].wave_ok && !ctx->sw.wave_keep_scan
+               && ctx->sw.wave_replay != 0;
     }
     bool none_scanned(const sx_ctx* ctx) const {
         if (not_scanned.size() != ctx->missions.size()) return false;
@@ -190,8 +187,8 @@ struct BufferScan {
             std::vector<std::thread>& t;
             ~Joiner() { for (auto& x : t) if (x.joinable()) x.join(); }
         } joiner{ wave_threads };
-        const uint64_t defer_all = nm >= 2 ? [] { const char* e = getenv("SX_DEFER_MIN_BYTES"); return e ? (uint64_t)atoll(e) : (256ull << 20); }() : 0;
-        if (nm >= 2 && !(getenv("SX_WAVE_THREADS") && !atoi(getenv("SX_WAVE_THREADS")))) {
+        const uint64_t defer_all = nm >= 2 ? ctx->sw.defer_min_bytes : 0;
+        if (nm >= 2 && ctx->sw.wave_threads) {
             if (ctx->wave_density.size() != nm) ctx->wave_density.assign(nm, 0.0);
             for (size_t k = 0; k < nm; k++) {
                 const bool unscanned = k < not_scanned.size() && not_scanned[k];
@@ -260,10 +257,8 @@ struct BufferScan {
             if (replayed) { pre.done[k] = 1; if ((rc = queue_next()) != SX_OK) return rc; continue; }
             if (device_replay_wanted(ctx, job, k, (*runs)[k].size())) {
                 // (with several missions a large output stays on the device: replay_all interleaves them there, one copy instead of two)
-                uint64_t defer = nm >= 2 ? (256ull << 20) : 0;
-                if (const char* e = getenv("SX_DEFER_MIN_BYTES")) defer = nm >= 2 ? (uint64_t)atoll(e) : 0;
                 SX_TL("mission %zu: device replay begins (%zu runs)", k, (*runs)[k].size());
-                rc = device_replay_mission(ctx, k, early_view, job, (*runs)[k], &pre.per[k], &pre.ends[k], defer);
+                rc = device_replay_mission(ctx, k, early_view, job, (*runs)[k], &pre.per[k], &pre.ends[k], defer_all);
                 SX_TL("mission %zu: device replay done", k);
                 if (rc == SX_NEED_RUNS) {   // the wave kernels gave up on a buffer whose runs were only counted: stage A in full, then the other stage B
                     ctx->wave_off[k] = 1;
@@ -275,7 +270,7 @@ struct BufferScan {
                     ctx->last_runs[k] = (*runs)[k].size();
                     if ((rc = queue_next()) != SX_OK) return rc;   // (the slot's records are out: now the next piece may have it)
                     if (!device_replay_wanted(ctx, job, k, (*runs)[k].size())) continue;   // few runs after all: the host's share of stage B
-                    rc = device_replay_mission(ctx, k, early_view, job, (*runs)[k], &pre.per[k], &pre.ends[k], defer);
+                    rc = device_replay_mission(ctx, k, early_view, job, (*runs)[k], &pre.per[k], &pre.ends[k], defer_all);
                 }
                 if (rc != SX_OK) return rc;
                 pre.done[k] = 1;
@@ -303,7 +298,7 @@ struct BufferScan {
 int scan_common(sx_ctx* ctx, const uint8_t* host_bytes, const uint8_t* d_bytes, uint64_t len, int file_id,
                        int is_last, sx_result** out, uint32_t slice_base0, sx_result* append_to) {
     const double t_begin = now_ms();
-    g_tl_on = getenv("SX_TIMELINE") ? atoi(getenv("SX_TIMELINE")) : 0; g_tl_t0 = t_begin;
+    g_tl_on = ctx->sw.timeline; g_tl_t0 = t_begin;
     SX_TL("scan_common: %llu bytes", (unsigned long long)len);
     const size_t nm = ctx->missions.size();
     // SX_OPT_RESULT_ON_DEVICE: a result left in HBM is the context's memory, and every BUFFER reuses it — the chunks of one sx_scan_stream /

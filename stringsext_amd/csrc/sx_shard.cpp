@@ -260,8 +260,8 @@ static int splice_segs(const sx_finding* const* findings, const uint64_t* n_find
 // (an output segment ends where its arena would pass 2 GiB; SX_SPLICE_SEG_BYTES: tests)
 int sx_shard_splice_segs(const sx_finding* const* findings, const uint64_t* n_findings, const uint8_t* const* arenas,
                          const uint64_t* arena_lens, const uint32_t* n_segs_of_rank, int world, uint64_t file_len, sx_result** out) {
-    uint64_t seg_cap = 2048ull << 20;
-    if (const char* e = getenv("SX_SPLICE_SEG_BYTES")) seg_cap = std::max<uint64_t>(1, (uint64_t)atoll(e));
+    const Switches sw = Switches::from_env();   // (no context here: read per call)
+    const uint64_t seg_cap = sw.splice_seg_bytes ? sw.splice_seg_bytes : 2048ull << 20;
     return splice_segs(findings, n_findings, arenas, arena_lens, n_segs_of_rank, world, file_len, seg_cap, out);
 }
 

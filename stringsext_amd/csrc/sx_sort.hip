@@ -39,7 +39,7 @@ size_t sort_scratch_bytes(uint32_t n) {
     return (size_t)n * 8 * 4 + tmp + 1024;
 }
 
-hipError_t sort_records(DevRun* recs, uint32_t n, uint64_t max_key, void* scratch, size_t scratch_bytes, hipStream_t stream) {
+hipError_t sort_records(DevRun* recs, uint32_t n, uint64_t max_key, void* scratch, size_t scratch_bytes, hipStream_t stream, bool dbg) {
     if (n == 0) return hipSuccess;
     uint64_t* k0 = (uint64_t*)scratch;
     uint64_t* v0 = k0 + n;
@@ -48,7 +48,6 @@ hipError_t sort_records(DevRun* recs, uint32_t n, uint64_t max_key, void* scratc
     uint8_t* tmp = (uint8_t*)(((uintptr_t)(v1 + n) + 255) & ~(uintptr_t)255);  // rocPRIM wants its storage aligned
     size_t tmp_bytes = scratch_bytes - (size_t)(tmp - (uint8_t*)scratch);
     const unsigned blocks = (n + 255) / 256;
-    static const bool dbg = getenv("SX_TIMING2") != nullptr;
     auto stamp = [&](const char* what) {
         if (!dbg) return;
         (void)hipStreamSynchronize(stream);
@@ -475,11 +474,10 @@ hipError_t launch_small_copy(void* pinned_dst, const void* dev_src, size_t bytes
     hipLaunchKernelGGL(small_copy_kernel, dim3(blocks), dim3(64), 0, stream, (uint32_t*)pinned_dst, (const uint32_t*)dev_src, (uint32_t)(bytes / 4));
     return hipGetLastError();
 }
-hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream) {
+hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nt) {
     if (!bytes) return hipSuccess;
     if ((((uintptr_t)dst | (uintptr_t)src) & 15) != 0) return hipErrorInvalidValue;
-    static const int nt = [] { const char* e = getenv("SX_MERGE_COPY_NT"); return e ? atoi(e) : 1; }();
-    static const int threads = [] { const char* e = getenv("SX_MERGE_COPY_THREADS"); return e ? std::max(64, std::min(1024, atoi(e))) : 512; }();   // (round 4, C5 with 16-byte records: 256 -> 474 ms per step, 512 -> 444, 1024 -> 454)
+    // (threads: round 4, C5 with 16-byte records: 256 -> 474 ms per step, 512 -> 444, 1024 -> 454)
     const uint64_t n16 = bytes / 16;
     if (nt)
         hipLaunchKernelGGL(copy_bytes_kernel<true>, dim3(workgroups ? workgroups : 2), dim3((unsigned)threads), 0, stream, (copy_v4u*)dst, (const copy_v4u*)src, n16,

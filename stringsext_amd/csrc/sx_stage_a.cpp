@@ -12,20 +12,30 @@ static bool large_regions_fit(uint64_t len, uint64_t n_regions, uint32_t cap) {
     return slots < (1ull << 31) && slots * sizeof(DevRun) <= std::max<uint64_t>(256ull << 20, len / 2);
 }
 
+// Bytes per wavefront of the scan kernels (sx_options::subchunk_bytes, 256 KiB by default): whole tiles, one at least.
+static uint32_t subchunk_bytes(const sx_ctx* ctx) {
+    const uint32_t sub = ctx->opt.subchunk_bytes ? ctx->opt.subchunk_bytes : 256u * 1024u;
+    return std::max<uint32_t>(kTileBytes, sub / kTileBytes * kTileBytes);
+}
+
+// May Missions share the fused launch (sx_fused.hip) in this context?  Not with a scan stream per Mission, nor with SX_FUSED=0, nor while
+// SX_SCAN_WARM precedes every launch by identical ones.
+static bool fusion_allowed(const sx_ctx* ctx) {
+    return !(ctx->opt.flags & (SX_OPT_NO_FUSED_SCAN | SX_OPT_MISSION_STREAMS)) && !ctx->sw.mission_streams && ctx->sw.fused && ctx->sw.scan_warm < 0;
+}
+
 ScanParams scan_params(const sx_ctx* ctx, int mission, const ScanSlot& s, const uint8_t* d_bytes, uint64_t len,
                        uint32_t parity, uint64_t min_chars) {
     const Mission& m = ctx->missions[(size_t)mission];
-    uint32_t sub = ctx->opt.subchunk_bytes ? ctx->opt.subchunk_bytes : 256u * 1024u;
-    sub = std::max<uint32_t>(kTileBytes, sub / kTileBytes * kTileBytes);
     ScanParams p = m.proto;
-    p.data = d_bytes; p.len = len; p.subchunk = sub; p.parity = parity;
+    p.data = d_bytes; p.len = len; p.subchunk = subchunk_bytes(ctx); p.parity = parity;
     p.pair_lut = ctx->dev[(size_t)mission].d_pair_lut;
     if (p.gb4) {   // (sx_codec_core.hpp: the decoder's blob is [kGbN two-byte cells][breakpoints][code points])
         p.gb_ranges = ctx->dev[(size_t)mission].d_table ? ctx->dev[(size_t)mission].d_table + kGbN : nullptr;
         p.ubf = m.c.ubf;
         if (!p.gb_ranges) p.gb4 = 0;
     }
-    p.wave_prio = getenv("SX_SCAN_PRIO") ? (uint32_t)atoi(getenv("SX_SCAN_PRIO")) : 0u;
+    p.wave_prio = ctx->sw.scan_prio;
     p.min_chars = (uint32_t)std::min<uint64_t>(min_chars, kRecCharsMask);
     if (p.min_chars == 0) p.min_chars = 1;
     // (<= 14: the scan kernel's candidate test takes the previous lane's mask without what ITS predecessor spilled into it — at most
@@ -59,8 +69,7 @@ int stage_a_launch(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
         ScanSlot& s = d.slot[si];
         if (s.free_pending) { HIP_TRY(ctx, hipStreamWaitEvent(d.stream, s.ev_free, 0)); s.free_pending = false; }
         {   // region mode unless the mission's last buffer was too dense for it (or the options rule it out)
-            uint32_t sub = ctx->opt.subchunk_bytes ? ctx->opt.subchunk_bytes : 256u * 1024u;
-            sub = std::max<uint32_t>(kTileBytes, sub / kTileBytes * kTileBytes);
+            const uint32_t sub = subchunk_bytes(ctx);
             const uint64_t n_regions = (len + sub - 1) / sub;
             if (ctx->dense.size() != ctx->missions.size()) ctx->dense.assign(ctx->missions.size(), 0);
             s.region_cap = 0; s.n_regions = n_regions;
@@ -89,8 +98,7 @@ int stage_a_launch(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
     launch:
         const bool dbcs = ctx->missions[(size_t)which[k]].is_dbcs();
         if (dbcs) {   // a flag word per sub-chunk: where its token grid stands, for the sub-chunks behind it (sx_kernels.hip scan_kernel_dbcs)
-            uint32_t sub = ctx->opt.subchunk_bytes ? ctx->opt.subchunk_bytes : 256u * 1024u;
-            sub = std::max<uint32_t>(kTileBytes, sub / kTileBytes * kTileBytes);
+            const uint32_t sub = subchunk_bytes(ctx);
             const uint64_t n_sub = (len + sub - 1) / sub;
             if (s.grid_cap < n_sub) {
                 if (s.d_grid) HIP_TRY(ctx, hipFree(s.d_grid));
@@ -107,9 +115,7 @@ int stage_a_launch(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
     std::vector<ScanParams> params(which.size());
     for (size_t k = 0; k < which.size(); k++)
         params[k] = scan_params(ctx, which[k], ctx->dev[(size_t)which[k]].slot[si], d_bytes, len, parity[k], min_chars[k]);
-    const bool may_fuse = !(ctx->opt.flags & (SX_OPT_NO_FUSED_SCAN | SX_OPT_MISSION_STREAMS)) && !getenv("SX_MISSION_STREAMS") &&
-                          !(getenv("SX_FUSED") && !atoi(getenv("SX_FUSED"))) && !getenv("SX_SCAN_WARM");
-    if (may_fuse) {
+    if (fusion_allowed(ctx)) {
         FusedParams fp{};
         uint32_t used = 0;
         size_t member[kFusedMax] = { 0, 0, 0 };
@@ -131,7 +137,7 @@ int stage_a_launch(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
                 HIP_TRY(ctx, hipMemsetAsync(d.slot[si].d_counters, 0, kCounterWords * sizeof(uint32_t), st));
             }
             for (int sl = 0; sl < kFusedMax; sl++) if ((used >> sl) & 1u) HIP_TRY(ctx, hipEventRecord(ctx->dev[(size_t)which[member[sl]]].slot[si].ev0, st));
-            HIP_TRY(ctx, launch_scan_fused(fp, used, st));
+            HIP_TRY(ctx, launch_scan_fused(fp, used, st, ctx->sw.fused_prefilter));
             bool first = true;
             for (int sl = 0; sl < kFusedMax; sl++) if ((used >> sl) & 1u) {
                 ScanSlot& s = ctx->dev[(size_t)which[member[sl]]].slot[si];
@@ -152,12 +158,11 @@ int stage_a_launch(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
         const uint64_t n_sub = (len + p.subchunk - 1) / p.subchunk;
         // SX_SCAN_WARM=n (measurements): the launch is preceded by n identical ones, so that the timed one starts on a busy chip
         // (bench.py's "alone" launches start from an idle one and take ~1 ms longer: DESIGN §6)
-        if (const char* e = getenv("SX_SCAN_WARM"))
-            for (int w = atoi(e); w > 0; w--) {
-                if (dbcs) HIP_TRY(ctx, hipMemsetAsync(s.d_grid, 0, n_sub * 4, d.stream));
-                HIP_TRY(ctx, hipMemsetAsync(s.d_counters, 0, kCounterWords * sizeof(uint32_t), d.stream));
-                HIP_TRY(ctx, launch_scan(ctx->missions[(size_t)which[k]].kind, p, d.stream));
-            }
+        for (int w = ctx->sw.scan_warm; w > 0; w--) {
+            if (dbcs) HIP_TRY(ctx, hipMemsetAsync(s.d_grid, 0, n_sub * 4, d.stream));
+            HIP_TRY(ctx, hipMemsetAsync(s.d_counters, 0, kCounterWords * sizeof(uint32_t), d.stream));
+            HIP_TRY(ctx, launch_scan(ctx->missions[(size_t)which[k]].kind, p, d.stream));
+        }
         if (dbcs) HIP_TRY(ctx, hipMemsetAsync(s.d_grid, 0, n_sub * 4, d.stream));
         HIP_TRY(ctx, hipMemsetAsync(s.d_counters, 0, kCounterWords * sizeof(uint32_t), d.stream));
         HIP_TRY(ctx, hipEventRecord(s.ev0, d.stream));
@@ -219,7 +224,7 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
                 // the memory allows, scan again with those — the kernel then appends without atomics, which
                 // on string-dense input is 20x faster than the shared pool — else use the pool from now on.
                 const uint32_t big = (counters[3] + counters[3] / 4 + 127) / 64 * 64;
-                if (s.region_cap == ctx->region_cap && counters[3] && large_regions_fit(len, s.n_regions, big) && !getenv("SX_NO_LARGE_REGIONS")) {
+                if (s.region_cap == ctx->region_cap && counters[3] && large_regions_fit(len, s.n_regions, big) && !ctx->sw.no_large_regions) {
                     ctx->dense[(size_t)which[k]] = big;
                     s.region_cap = big;
                     if (ensure_capacity(ctx, s, (uint32_t)(s.n_regions * big)) != SX_OK) {  // no room after all: the pool
@@ -250,11 +255,11 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
         }
         const double tc0 = now_ms();
         SX_TL("mission %d: counters read (%u records)", which[k], s.region_cap ? counters[2] : counters[0]);
-        if (getenv("SX_TIMING2")) fprintf(stderr, "[sx]   mission %d: kernel done at +%.2f ms, counters at +%.2f ms\n", which[k], t_ev - t0, tc0 - t0);
+        if (ctx->sw.timing2) fprintf(stderr, "[sx]   mission %d: kernel done at +%.2f ms, counters at +%.2f ms\n", which[k], t_ev - t0, tc0 - t0);
         if (skip_runs) {
             HIP_TRY(ctx, hipEventRecord(s.ev_free, d.stream_b));
             s.free_pending = true;
-            if (getenv("SX_TIMING")) fprintf(stderr, "[sx] mission %d: kernel %.2f ms, %llu records counted: string-dense, every window is replayed\n", which[k], ms, (unsigned long long)(*out)[k].n);
+            if (ctx->sw.timing) fprintf(stderr, "[sx] mission %d: kernel %.2f ms, %llu records counted: string-dense, every window is replayed\n", which[k], ms, (unsigned long long)(*out)[k].n);
             ctx->stats.run_records += (*out)[k].n;
             ctx->stats.bytes_scanned += len;
             ctx->stats.heavy_tiles += counters[1];
@@ -286,7 +291,7 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
             SX_TL("mission %d: regions packed (%u)", which[k], nrec);
         } else if (ctx->region_cap && !large_regions && nrec < s.n_regions * ctx->region_cap / 4)
             ctx->dense[(size_t)which[k]] = 0;  // sparse again: regions next time
-        const uint32_t join_min = getenv("SX_DEVICE_JOIN_MIN") ? (uint32_t)atoi(getenv("SX_DEVICE_JOIN_MIN")) : 65536u;
+        const uint32_t join_min = ctx->sw.device_join_min;
         const bool dev_sorted = nrec >= join_min && nrec > 0;  // worth a handful of small kernels
         double tc1 = tc0;
         RunList& rl = (*out)[k];
@@ -296,13 +301,13 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
             int rc = ensure_scratch(ctx, sb); if (rc != SX_OK) return rc;
             if (d.ev_runs) HIP_TRY(ctx, hipEventSynchronize(d.ev_runs));  // the previous list's copy (normally long done)
             rc = ensure_rp(ctx, d, 0, (uint64_t)nrec * sizeof(sx_run)); if (rc != SX_OK) return rc;
-            if (!regions) HIP_TRY(ctx, sort_records(s.d_recs, nrec, len, ctx->d_scratch, ctx->d_scratch_cap, d.stream_b));
-            if (getenv("SX_TIMING2")) { HIP_TRY(ctx, hipStreamSynchronize(d.stream_b)); fprintf(stderr, "[sx]   sort done +%.2f ms\n", now_ms() - tc0); }
+            if (!regions) HIP_TRY(ctx, sort_records(s.d_recs, nrec, len, ctx->d_scratch, ctx->d_scratch_cap, d.stream_b, ctx->sw.timing2));
+            if (ctx->sw.timing2) { HIP_TRY(ctx, hipStreamSynchronize(d.stream_b)); fprintf(stderr, "[sx]   sort done +%.2f ms\n", now_ms() - tc0); }
             HIP_TRY(ctx, merge_sorted_records(d_records, nrec, min_chars[k], ctx->d_scratch, ctx->d_scratch_cap,
                                               (sx_run*)d.d_rp[0], s.d_counters + 2, d.stream_b));
             HIP_TRY(ctx, hipEventRecord(s.ev_free, d.stream_b));
             s.free_pending = true;
-            if (getenv("SX_TIMING2")) { HIP_TRY(ctx, hipStreamSynchronize(d.stream_b)); fprintf(stderr, "[sx]   join done +%.2f ms\n", now_ms() - tc0); }
+            if (ctx->sw.timing2) { HIP_TRY(ctx, hipStreamSynchronize(d.stream_b)); fprintf(stderr, "[sx]   join done +%.2f ms\n", now_ms() - tc0); }
             uint32_t nruns32 = 0;
             { const int rb = read_back_sync(ctx, d, d.stream_b, &nruns32, s.d_counters + 2, 4); if (rb != SX_OK) return rb; }
             uint64_t nruns = nruns32;
@@ -312,7 +317,7 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
             // starts follows from the run alone (sx_replay_core.hpp kPieceCont): stage B then gets a region per
             // window instead of one serial replay per run (text: a run per line, most of them cross a window start).
             const Mission& mm = ctx->missions[(size_t)which[k]];
-            if (cut_into_pieces && nruns && !getenv("SX_NO_PIECES") && mm.c.grep_char < 0 && !mm.c.require_same_unicode_block
+            if (cut_into_pieces && nruns && !ctx->sw.no_pieces && mm.c.grep_char < 0 && !mm.c.require_same_unicode_block
                 && mm.c.chars_min_nb >= 1 && mm.c.chars_min_nb <= mm.q && mm.q <= 255) {   // (q: what the replay kernels' buffers hold, sx_replay_core.hpp kObCapBig)
                 ReplayParams SP{};
                 SP.data = d_bytes; SP.len = len; SP.runs = d_list; SP.n_runs = nruns; SP.encoding = mm.c.encoding; SP.table = d.d_table;
@@ -358,20 +363,11 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
                 HIP_TRY(ctx, hipStreamSynchronize(d.stream_b));
             }
             tc1 = now_ms();
-            if (getenv("SX_DEBUG_RECS")) {
-                std::vector<DevRun> srt(recs_p, recs_p + nrec);
-                std::sort(srt.begin(), srt.end(), [](const DevRun& a, const DevRun& b) { return a.start < b.start; });
-                for (const DevRun& r : srt)
-                    fprintf(stderr, "[sx] rec start=%llu len=%u chars=%u flags=%s%s\n", (unsigned long long)r.start, r.len,
-                            r.chars_flags & kRecCharsMask, (r.chars_flags & kRecStartOpen) ? "S" : "-",
-                            (r.chars_flags & kRecEndOpen) ? "E" : "-");
-                fprintf(stderr, "[sx] slow tiles %u\n", counters[1]);
-            }
             if (regions) merge_sorted_device_runs(recs_p, nrec, min_chars[k], &rl.own);
             else merge_device_runs(recs_p, nrec, min_chars[k], 64 * 1024, &rl.own);
             rl.use_own();
         }
-        if (getenv("SX_TIMING"))
+        if (ctx->sw.timing)
             fprintf(stderr, "[sx] mission %d: kernel %.2f ms, %u %s, %s %.2f ms, %s %.2f ms -> %zu runs\n", which[k], ms, nrec,
                     regions ? "records (regions)" : (large_regions ? "record slots (large regions)" : "record slots (pool)"), dev_sorted ? (regions ? "device pack+join" : "device sort+join") : "d2h",
                     tc1 - tc0, dev_sorted ? "d2h runs" : "host join", now_ms() - tc1, rl.size());

@@ -21,9 +21,9 @@ bool device_replay_wanted(const sx_ctx* ctx, const ReplayJob& job, size_t k, siz
     // rule "the last accepted char in front of a window start is the leftover" (derive_at) does not hold.  Such a
     // mission is replayed by ONE exact sequential pass on the host: no derived states, no speculation.
     if (ctx->missions[k].c.chars_min_nb == 0) return false;
-    if (getenv("SX_HOST_REPLAY")) return false;
+    if (ctx->sw.host_replay) return false;
     if (wave_replay_wanted(ctx, job, k, n_runs)) return true;
-    return (ctx->opt.flags & SX_OPT_DEVICE_REPLAY) || getenv("SX_DEVICE_REPLAY") || n_runs >= 4096;
+    return (ctx->opt.flags & SX_OPT_DEVICE_REPLAY) || ctx->sw.device_replay || n_runs >= 4096;
 }
 
 // Stage B of one mission on the device (sx_replay_dev.hip) + the little the host keeps:
@@ -63,7 +63,7 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
     // that step for buffers with regions the device gave back (kRegionTooLong).
     ReplayParams P{};
     bool fast_pass = false;
-    bool dev_stitch = n > 0 && !getenv("SX_HOST_STITCH");
+    bool dev_stitch = n > 0 && !ctx->sw.host_stitch;
     uint64_t* h_tot = nullptr;
     ReplayRegionOut* ro = nullptr;
     {
@@ -79,7 +79,7 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
         rc = ensure_rp(ctx, d, 2, n * 8); if (rc) return rc;
         rc = ensure_rp(ctx, d, 3, (n + 1) * 8); if (rc) return rc;
         rc = ensure_rp(ctx, d, 4, (n + 1) * 8); if (rc) return rc;
-        rc = ensure_rp(ctx, d, 6, stitch_blocks_bytes(n)); if (rc) return rc;
+        rc = ensure_rp(ctx, d, 6, stitch_blocks_bytes(n, ctx->sw.stitch_block)); if (rc) return rc;
         rc = ensure_rp(ctx, d, 7, kTotCount * 8); if (rc) return rc;
         rc = ensure_scratch(ctx, stitch_scratch_bytes(n)); if (rc) return rc;
         if (!runs.on_device)   // (never slabbed)
@@ -89,17 +89,17 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
         P.lo = job.lo[k]; P.hi = job.hi; P.consumed0 = job.consumed0[k]; P.stream0 = job.stream0[k];
         P.slice_base = job.slice_base; P.encoding = m.c.encoding; P.table = d.d_table;
         P.chars_min_nb = m.c.chars_min_nb; P.same_block = m.c.require_same_unicode_block; P.q = (uint32_t)m.q;
-        P.W = (uint32_t)W; P.long_run = m.long_run; P.skip = getenv("SX_NO_REPLAY_SKIP") ? 0u : 1u; P.grep_char = m.c.grep_char; P.mission_id = m.c.mission_id;
+        P.W = (uint32_t)W; P.long_run = m.long_run; P.skip = ctx->sw.no_replay_skip ? 0u : 1u; P.grep_char = m.c.grep_char; P.mission_id = m.c.mission_id;
         P.file_id = job.file_id; P.af_lo = m.c.af_lo; P.af_hi = m.c.af_hi; P.ubf = m.c.ubf;
         P.max_windows = kMaxRegionWindowsDefault;
         P.entry_skip = m.buf_entry_skip;
         P.grid_flags = nullptr; P.grid_sub = 0;
         // (not for gb18030 / GBK — ADVICE round 5: the scan kernel publishes the hang-over of the TWO-byte grammar; a four-byte token that
         //  straddles a sub-chunk start followed by lead / digit bytes only would start the walk two bytes off and never resynchronise)
-        if (d.grid_of_scan && d.grid_data == job.d_bytes && d.grid_len == job.len && !getenv("SX_NO_GRID_BOUND") && !enc_is_gb(m.c.encoding)) { P.grid_flags = d.grid_of_scan; P.grid_sub = d.grid_sub; }
-        if (const char* e = getenv("SX_MAX_REGION_WINDOWS")) P.max_windows = (uint32_t)std::max(1, atoi(e));
+        if (d.grid_of_scan && d.grid_data == job.d_bytes && d.grid_len == job.len && !ctx->sw.no_grid_bound && !enc_is_gb(m.c.encoding)) { P.grid_flags = d.grid_of_scan; P.grid_sub = d.grid_sub; }
+        if (ctx->sw.max_region_windows) P.max_windows = ctx->sw.max_region_windows;
         // pass-1 output cache: one arena for all replaying regions (slot = arena / their number, on the device)
-        if (dev_stitch && !getenv("SX_NO_REPLAY_CACHE")) {
+        if (dev_stitch && !ctx->sw.no_replay_cache) {
             // the arena is at most 1 KiB per run; 8 GiB of the 288 GB, and for a flood of runs (a Mission with hundreds of
             // millions of them: slots of the minimum size, 160 bytes, for as many regions as possible — a region without slot
             // is replayed twice) up to a third of what is free, at most 40 GiB
@@ -109,7 +109,7 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
                 if (hipMemGetInfo(&fr, &tot) == hipSuccess)
                     budget = std::max(budget, std::min<uint64_t>(40960ull << 20, ((uint64_t)fr + ctx->d_cache_cap) / 3));
             }
-            if (const char* e = getenv("SX_REPLAY_CACHE_MIB")) budget = (uint64_t)atoll(e) << 20;
+            if (ctx->sw.replay_cache_mib >= 0) budget = (uint64_t)ctx->sw.replay_cache_mib << 20;
             uint64_t arena = std::max<uint64_t>(4096, std::min<uint64_t>(budget, (uint64_t)n * 1024));
             const uint64_t lists = (uint64_t)(3 * n + 8) * 4 + 512;   // slot_of, n_heads, head_list; (round 5) n_hard, hard_list
             rc = ensure_cache(ctx, arena + lists);
@@ -128,13 +128,13 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
                                              ctx->d_scratch_cap, d.stream_b));
             // (round 5) the fast pre-pass settles the regions that are one run inside one window; the general kernel gets the rest
             P.n_hard = slot_of + 2 * n + 4; P.hard_list = slot_of + 2 * n + 5;
-            if (replay_fast_covers(P) && !(getenv("SX_FAST_REPLAY") && !atoi(getenv("SX_FAST_REPLAY")))) {
+            if (replay_fast_covers(P) && ctx->sw.fast_replay) {
                 HIP_TRY(ctx, hipMemsetAsync(P.n_hard, 0, 4, d.stream_b));
                 HIP_TRY(ctx, launch_replay_fast(P, (ReplayRegionOut*)d.d_rp[1], d.stream_b));
                 fast_pass = true;
             } else { P.n_hard = nullptr; P.hard_list = nullptr; }
         }
-        HIP_TRY(ctx, launch_replay_count(P, (ReplayRegionOut*)d.d_rp[1], d.stream_b));
+        HIP_TRY(ctx, launch_replay_count(P, (ReplayRegionOut*)d.d_rp[1], d.stream_b, ctx->sw.count_waves));
         if (fast_pass) {   // (statistics: how many regions each pass took; read with the totals below)
             h_tot[32] = 0; h_tot[33] = 0;
             { int rb = read_back_async(ctx, d.stream_b, h_tot + 32, P.n_hard, 4); if (rb == SX_OK) rb = read_back_async(ctx, d.stream_b, h_tot + 33, P.n_heads, 4); if (rb != SX_OK) return rb; }
@@ -146,7 +146,7 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
         if (dev_stitch) {
             HIP_TRY(ctx, hipMemsetAsync(d.d_rp[7], 0, kTotCount * 8, d.stream_b));
             HIP_TRY(ctx, launch_stitch_blocks(P, (const ReplayRegionOut*)d.d_rp[1], (uint8_t*)d.d_rp[2], d.d_rp[6],
-                                              (uint64_t*)d.d_rp[7], d.stream_b));
+                                              (uint64_t*)d.d_rp[7], d.stream_b, ctx->sw.stitch_block));
         } else
             HIP_TRY(ctx, hipMemcpyAsync(ro, d.d_rp[1], n * sizeof(ReplayRegionOut), hipMemcpyDeviceToHost, d.stream_b));
     }
@@ -182,7 +182,7 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
     if (dev_stitch) {
         HIP_TRY(ctx, launch_stitch_finish(P, (const ReplayRegionOut*)d.d_rp[1], (uint8_t*)d.d_rp[2], d.d_rp[6], E,
                                           (uint64_t*)d.d_rp[3], (uint64_t*)d.d_rp[4], (uint64_t*)d.d_rp[7], ctx->d_scratch,
-                                          ctx->d_scratch_cap, d.stream_b));
+                                          ctx->d_scratch_cap, d.stream_b, ctx->sw.stitch_block));
         { const int rb = read_back_async(ctx, d.stream_b, h_tot, d.d_rp[7], kTotCount * 8); if (rb != SX_OK) return rb; }
     }
     SX_TL("  replay: pass 1 + stitch queued, host entry part done");
@@ -308,8 +308,8 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
             } else {
                 // (experiments, SX_REPLAY_COPY_WGS=n: the copy as a kernel of n workgroups instead of the runtime's blit, which slows every
                 // kernel next to it — here: the last Mission's scan launch, DESIGN.md section 2 "Schedule")
-                static const int wgs = [] { const char* e = getenv("SX_REPLAY_COPY_WGS"); return e ? atoi(e) : 0; }();
-                if (wgs > 0 && out_bytes >= (1u << 20)) HIP_TRY(ctx, launch_copy_bytes(blk.p, d_all, out_bytes, (uint32_t)wgs, d.stream_b));
+                const int wgs = ctx->sw.replay_copy_wgs;
+                if (wgs > 0 && out_bytes >= (1u << 20)) HIP_TRY(ctx, launch_copy_bytes(blk.p, d_all, out_bytes, (uint32_t)wgs, d.stream_b, ctx->sw.merge_copy_threads, ctx->sw.merge_copy_nt != 0));
                 else HIP_TRY(ctx, hipMemcpyAsync(blk.p, d_all, out_bytes, hipMemcpyDeviceToHost, d.stream_b));
             }
         }
@@ -377,19 +377,17 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
     }
     if (end_pos) *end_pos = std::max(E, std::min(job.hi, job.len));
     carry.last_start = last_start; carry.last_is_entry = last_is_entry; carry.any = true;
-    if (getenv("SX_TIMING"))
+    if (ctx->sw.timing)
         fprintf(stderr, "[sx] device replay mission %zu: %zu runs, pass1+entry %.2f ms, validity %.2f ms (%zu standing, %zu host parts), "
                         "pass2+d2h %.2f ms (%llu findings), splice+state %.2f ms\n", k, n, t1 - t0, t2 - t1, (size_t)n_standing,
                 host_parts.size(), t3 - t2, (unsigned long long)nf, now_ms() - t3);
     return SX_OK;
 }
 
-// The stream of the result copies (slabs, merge parts).  SX_COPY_PRIO=-1/0/1: its priority (experiments).
+// The stream of the result copies (slabs, merge parts).
 int ensure_copy_stream(sx_ctx* ctx) {
     if (ctx->merge_copy_stream) return SX_OK;
-    int prio = 0;
-    if (const char* e = getenv("SX_COPY_PRIO")) prio = atoi(e);
-    HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->merge_copy_stream, hipStreamNonBlocking, prio));
+    HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->merge_copy_stream, hipStreamNonBlocking, 0));
     for (hipEvent_t& e : ctx->merge_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return SX_OK;
 }
@@ -410,10 +408,10 @@ int device_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob
     }
     if (runs.skipped) return SX_NEED_RUNS;
     size_t K = 1;
-    const bool can = ctx->missions.size() == 1 && runs.on_device && !getenv("SX_HOST_STITCH") && defer_min_bytes == 0;
+    const bool can = ctx->missions.size() == 1 && runs.on_device && !ctx->sw.host_stitch && defer_min_bytes == 0;
     const bool keep_dev_wanted = (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) && ctx->missions.size() == 1 && defer_min_bytes == 0 && job.commit_state && !ctx->sharded_call && ctx->single_piece;   // (one slab then: one block of the context's)
     if (can && n >= (1u << 20) && !keep_dev_wanted) K = 3;   // (measured on string-dense and text-like input: 3 beats 2, 4 and 6)
-    if (const char* e = getenv("SX_SLABS")) { K = (size_t)std::max(1, std::min(64, atoi(e))); if (!can || n < 8 * K) K = 1; }
+    if (ctx->sw.slabs) { K = (size_t)ctx->sw.slabs; if (!can || n < 8 * K) K = 1; }
     std::vector<uint64_t> idx{ 0 }, his{ 0 };
     if (K > 1) {   // where to cut
         int rc = ensure_copy_stream(ctx); if (rc != SX_OK) return rc;
@@ -522,11 +520,11 @@ static int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFi
         for (auto& mf : per) { if (mf.keep_on_device) continue; int rc = fetch_deferred(ctx, mf); if (rc != SX_OK) return rc; }   // (SX_OPT_RESULT_ON_DEVICE: it stays)
         return SX_OK;
     };
-    if (!(with >= 2 && on_dev == with && same_origin && total >= 4096 && !getenv("SX_HOST_MERGE"))) return give_up();
+    if (!(with >= 2 && on_dev == with && same_origin && total >= 4096 && !ctx->sw.host_merge)) return give_up();
     const double tm0 = now_ms();
     // The records cross PCIe as sx_finding16 (include/stringsext_amd.h): half the bytes of what bounds this path.  Not with lines of
     // more than 16 000 chars (str_len has 16 bits there), nor where the one-pass merger does not apply (SX_PACKED=0: tests).
-    bool pack = !(getenv("SX_PACKED") && !atoi(getenv("SX_PACKED")));
+    bool pack = ctx->sw.packed;
     for (size_t k = 0; k < nm; k++) pack = pack && ctx->missions[k].q <= 16000;
     std::shared_ptr<SegInfo> seg_info;
     if (pack) {
@@ -536,8 +534,8 @@ static int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFi
         for (size_t k = 0; k < nm; k++) seg_info->pos0[ctx->missions[k].c.mission_id] = job.consumed0[k];
     }
     uint64_t part_bytes = 2048ull << 20, part_findings = 96ull << 20;
-    if (const char* e = getenv("SX_MERGE_PART_MIB")) part_bytes = std::max<uint64_t>(1, (uint64_t)atoll(e)) << 20;
-    if (const char* e = getenv("SX_MERGE_PART_FINDINGS")) part_findings = std::max<uint64_t>(1024, (uint64_t)atoll(e));
+    if (ctx->sw.merge_part_mib) part_bytes = ctx->sw.merge_part_mib << 20;
+    if (ctx->sw.merge_part_findings) part_findings = ctx->sw.merge_part_findings;
     if (part_bytes > (3584ull << 20)) part_bytes = 3584ull << 20;
     uint64_t K = std::max<uint64_t>(1, std::max((bytes + part_bytes - 1) / part_bytes, (total + part_findings - 1) / part_findings));
     hipStream_t s = ctx->post_stream;
@@ -650,9 +648,8 @@ static int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFi
             // — a blit kernel that fills the chip with wavefronts waiting on PCIe — delays every kernel next to it until it is done
             // (a 6 ms scan takes 45), eight workgroups slow the count passes by half, one does not fill the link; two copy at
             // ~45 GB/s and cost the count passes 8 %.  With nothing next to it the runtime's copy is the faster one (53 GB/s).
-            static const int copy_wgs_env = [] { const char* e = getenv("SX_MERGE_COPY_WGS"); return e ? atoi(e) : -1; }();
-            const int copy_wgs = copy_wgs_env >= 0 ? copy_wgs_env : (ctx->merge_async ? 2 : 0);
-            if (copy_wgs > 0) HIP_TRY(ctx, launch_copy_bytes(blk.p, d_out, out_bytes, (uint32_t)copy_wgs, cs));
+            const int copy_wgs = ctx->sw.merge_copy_wgs >= 0 ? ctx->sw.merge_copy_wgs : (ctx->merge_async ? 2 : 0);
+            if (copy_wgs > 0) HIP_TRY(ctx, launch_copy_bytes(blk.p, d_out, out_bytes, (uint32_t)copy_wgs, cs, ctx->sw.merge_copy_threads, ctx->sw.merge_copy_nt != 0));
             else HIP_TRY(ctx, hipMemcpyAsync(blk.p, d_out, out_bytes, hipMemcpyDeviceToHost, cs));
         }
         HIP_TRY(ctx, hipEventRecord(ev_copied[ob], cs));
@@ -678,7 +675,7 @@ static int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFi
     if (!outs.empty()) outs[0].replay_bytes = rb; else per[0].replay_bytes = rb;
     into->pool = ctx->pool;
     for (auto& o : outs) { ctx->stats.replay_bytes += o.replay_bytes; into->segs.push_back(std::move(o)); o.ext = {}; }
-    if (getenv("SX_TIMING"))
+    if (ctx->sw.timing)
         fprintf(stderr, "[sx] device merge of %zu missions (%zu held back on the device): %llu findings, %llu parts, %.2f ms\n", with, deferred,
                 (unsigned long long)total, (unsigned long long)K, now_ms() - tm0);
     return SX_OK;
@@ -799,9 +796,9 @@ int replay_all(sx_ctx* ctx, ByteView& bytes, const ReplayJob& job, const std::ve
         if (rc != SX_OK) return rc;
     }
     SX_TL("replay_all: device_merge done");
-    merge_findings(per, ctx->pool, into);
+    merge_findings(per, ctx->pool, into, ctx->sw.host_merge_seg_bytes);
     SX_TL("replay_all: merge_findings done");
-    if (getenv("SX_TIMING")) {
+    if (ctx->sw.timing) {
         double mx = 0, sum = 0;
         for (double v : task_ms) { sum += v; mx = std::max(mx, v); }
         fprintf(stderr, "[sx] replay: parts %.2f ms (%zu tasks, %zu workers; task sum %.1f max %.1f ms), stitch %.2f ms, merge %.2f ms, "
@@ -903,7 +900,7 @@ int download_for_replay(sx_ctx* ctx, const uint8_t* d_bytes, uint64_t len,
             }
         }
         ctx->stats.d2h_ms += now_ms() - t0;
-        if (getenv("SX_TIMING"))
+        if (ctx->sw.timing)
             fprintf(stderr, "[sx] sparse download: ranges %.2f ms, sort+merge+segments %.2f ms (%zu ranges, %zu segs), gather+d2h %.2f ms (%.1f MB)\n",
                     t_rg - t0, t_seg - t_rg, mg.size(), seg_src.size(), now_ms() - t_seg, total / 1e6);
     return SX_OK;

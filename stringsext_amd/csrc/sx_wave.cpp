@@ -22,8 +22,8 @@ namespace sx {
 // works a lane per finding, 2.0 ps per input byte (single byte: 5.5 + 2.9 ms per 4 GiB with 15 M findings) / 6.3 ps (two-byte
 // family: 24.7 + 2.2 ms, Big5 on random bytes with a run per 490 bytes) / 5.5 ps (UTF-8 on random bytes, where a decoder call starts
 // every other byte; on text it is the single-byte figure).
-static uint64_t wave_min_density_bytes(uint32_t family = 0) {
-    static const uint64_t v = [] { const char* e = getenv("SX_WAVE_BYTES_PER_RUN"); return e ? (uint64_t)atoll(e) : 0ull; }();
+static uint64_t wave_min_density_bytes(const sx_ctx* ctx, uint32_t family) {
+    const uint64_t v = ctx->sw.wave_bytes_per_run;
     // (round 4: the count passes are 2.5 to 4 times faster — single byte 0.7 ps per byte, two-byte family 1.4, EUC-JP 2.3 — and a Mission on
     // the wave path leaves the shared stage-B stream alone: EUC-JP + Asian on random bytes, a run per 3.4 KB, C5: 444 -> 415 ms per step)
     return v ? v : (family == 5 ? 4000ull : family == 4 ? 1600ull : family == 1 ? 480ull : family == 2 ? 960ull : 1000ull);
@@ -38,9 +38,9 @@ bool wave_replay_wanted(const sx_ctx* ctx, const ReplayJob& job, size_t k, size_
     if (k < ctx->wave_off.size() && ctx->wave_off[k]) return false;
     if (job.lo[k] != 0 || job.hi != job.len || !job.entry_exact[k] || job.len < 2 * kInputBufLen) return false;   // whole buffers only
     if (ctx->opt.flags & SX_OPT_HOST_REPLAY) return false;
-    if (const char* e = getenv("SX_WAVE_REPLAY")) return atoi(e) != 0;
-    if (getenv("SX_HOST_REPLAY") || getenv("SX_HOST_STITCH") || getenv("SX_NO_REPLAY_CACHE")) return false;   // tests of the other path
-    if ((uint64_t)n_runs * wave_min_density_bytes(m.wave_family) > job.len) return true;
+    if (ctx->sw.wave_replay >= 0) return ctx->sw.wave_replay != 0;
+    if (ctx->sw.host_replay || ctx->sw.host_stitch || ctx->sw.no_replay_cache) return false;   // tests of the other path
+    if ((uint64_t)n_runs * wave_min_density_bytes(ctx, m.wave_family) > job.len) return true;
     // (round 4: the two-byte family too — inside a fill of lead-range bytes its wave kernels take the token grid from the wavefront in
     // front by parity; EUC-JP, whose tokens have two or three bytes, still gives up after 64 KiB of look-back)
     return m.wave_family <= 4 && heavy_tiles * 2048 > job.len && (uint64_t)n_runs * 4096 < job.len;
@@ -63,7 +63,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         int lo = 0, hi = 0;   // (lo: the numerically greatest = lowest priority, hi: the highest)
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         int prio = hi;
-        if (const char* e = getenv("SX_WAVE_STREAM_PRIO")) prio = atoi(e) == 0 ? lo : atoi(e) == 1 ? (lo + hi) / 2 : hi;
+        if (ctx->sw.wave_stream_prio == 0) prio = lo; else if (ctx->sw.wave_stream_prio == 1) prio = (lo + hi) / 2;
         HIP_TRY(ctx, hipStreamCreateWithPriority(&d.stream_w, hipStreamNonBlocking, prio));
     }
     const hipStream_t sb = own_stream ? d.stream_w : d.stream_b;
@@ -144,14 +144,14 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         uint64_t batches = (n_windows + (8192ull * 64) - 1) / (8192ull * 64);
         batches = std::max<uint64_t>(1, std::min<uint64_t>(8, batches));
         if (m.wave_same) batches = 1;   // (-r in the kernels: a window costs 5 to 20 times the usual, one wavefront per SIMD does not hide it — Russian text 51 -> 26 ms per 256 MiB)
-        if (const char* e = getenv("SX_WAVE_BATCHES")) batches = (uint64_t)std::max(1, std::min(64, atoi(e)));
+        if (ctx->sw.wave_batches) batches = (uint64_t)ctx->sw.wave_batches;
         const uint32_t nwin = (uint32_t)(batches * kWvBatch - kWvWarm);
         n_waves = (n_windows + nwin - 1) / nwin;
         // Slabs of wavefronts: count -> write -> copy to the host, the copy of a slab next to the kernels of the following one.
         // (Several Missions: one slab; their outputs stay in HBM and are interleaved there, sx_stage_b.cpp device_merge.)
         uint64_t K = 1;
         if (ctx->missions.size() == 1 && defer_min_bytes == 0) K = std::min<uint64_t>(8, std::max<uint64_t>(1, len >> 25));   // >= 32 MiB of input each, eight at most (measured: 256 MiB of text in 4 / 8 / 16 slabs 7.9 / 7.2 / 8.0 ms; `-e ascii -n 4` on 1 GiB in 8 / 16 / 32: 5.15 / 5.27 / 7.0 ms)
-        if (const char* e = getenv("SX_WAVE_SLABS")) K = (uint64_t)std::max(1, std::min(64, atoi(e)));
+        if (ctx->sw.wave_slabs) K = (uint64_t)ctx->sw.wave_slabs;
         if (ctx->missions.size() != 1 || defer_min_bytes != 0) K = 1;
         // SX_OPT_RESULT_ON_DEVICE (round 5): one Mission, no pieces — the result stays where the writer put it (one slab: one block of the context's)
         const bool keep_dev = (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) && ctx->missions.size() == 1 && defer_min_bytes == 0 && job.commit_state && !ctx->sharded_call && ctx->single_piece;
@@ -197,7 +197,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         P.swar = m.wave_swar; P.pairs2 = d.d_wave_pairs2;
         if (m.wave_family == 4 && !d.d_wave_pairs2) P.swar.cls = 0;
         if (m.wave_family == 5 && !d.d_wave_pairs2) return SX_WAVE_FALLBACK;
-        if (const char* e = getenv("SX_WAVE_LUT")) if (atoi(e) && m.wave_family != 5) P.swar.cls = 0;   // tests: the class table also where ranges would do
+        if (ctx->sw.wave_lut && m.wave_family != 5) P.swar.cls = 0;   // tests: the class table also where ranges would do
         P.wave_nf = d_u; P.wave_nb = d_u + n_waves; P.wave_in = d_u + 2 * n_waves; P.wave_out = d_u + 3 * n_waves;
         P.wave_grid = m.wave_family == 4 || m.wave_family == 5 ? d_u + 4 * n_waves : nullptr;   // (EUC-JP since round 5: fills without 8E / 8F)
         // -r on a UTF-8 Mission: the kernels collect the lead bytes that pass ubf; two kinds (the leftover's included) and the buffer goes back
@@ -217,7 +217,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         // density; stage A's record count; else one per window), at most two per window and a third of the input's size in all.  A
         // wavefront that finds more is only counted, and the launch takes the window-parallel writer.
         P.desc = nullptr; P.desc_cap = 0;
-        if (nwin <= kWvDescMaxWin && !(getenv("SX_WAVE_DESC") && !atoi(getenv("SX_WAVE_DESC")))) {
+        if (nwin <= kWvDescMaxWin && ctx->sw.wave_desc) {
             if (ctx->wave_density.size() != ctx->missions.size()) ctx->wave_density.assign(ctx->missions.size(), 0.0);
             double per_byte = ctx->wave_density[k];
             if (per_byte <= 0 && k < ctx->last_runs.size() && ctx->last_runs[k] && ctx->last_runs[k] < len / 16) per_byte = (double)ctx->last_runs[k] / (double)len;
@@ -232,8 +232,8 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
             // (more findings expected than descriptors may be kept: the count pass would leave them for nothing — the window-parallel writer at once)
             // (clearly more: `-e ascii -n 4` on random bytes expects 1.0 to 1.15 times the room and its wavefronts mostly fit — with the lane-per-finding
             // writer 12.4 -> 6 ms per GiB; Russian text with -r: 1.65 times)
-            const bool too_dense = per_byte > 0 && per_byte * bytes_per_wave > 1.4 * (double)(per_win * nwin + 64) && !getenv("SX_WAVE_DESC_CAP");
-            if (const char* e = getenv("SX_WAVE_DESC_CAP")) cap = (uint64_t)std::max(1, atoi(e));
+            const bool too_dense = per_byte > 0 && per_byte * bytes_per_wave > 1.4 * (double)(per_win * nwin + 64) && !ctx->sw.wave_desc_cap;
+            if (ctx->sw.wave_desc_cap) cap = (uint64_t)ctx->sw.wave_desc_cap;
             if (too_dense) cap = 0;
             if (cap == 0) { }
             else if (ensure_rp(ctx, d, 2, n_waves * cap * 12 + 64) == SX_OK) { P.desc = (uint32_t*)d.d_rp[2]; P.desc_cap = (uint32_t)cap; }
@@ -249,7 +249,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         }
         // A single Mission's slabs go to the host as they are written: as sx_finding16 (include/stringsext_amd.h), half the bytes of what
         // bounds this path.  (Several Missions: the outputs are interleaved first, 32-byte records; device_merge packs then.)
-        const bool pack = ctx->missions.size() == 1 && defer_min_bytes == 0 && !(getenv("SX_PACKED") && !atoi(getenv("SX_PACKED")));
+        const bool pack = ctx->missions.size() == 1 && defer_min_bytes == 0 && ctx->sw.packed;
         const size_t rec = pack ? sizeof(sx_finding16) : sizeof(sx_finding);
         std::shared_ptr<SegInfo> seg_info;
         std::vector<sx_finding16> hf16;
@@ -268,7 +268,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         bool pending[2] = { false, false };
         for (uint64_t j = 0; j < K; j++) {
             const uint64_t v0 = n_waves * j / K, v1 = n_waves * (j + 1) / K;
-            if (getenv("SX_TIMING2")) fprintf(stderr, "[sx]   wave mission %zu slab %llu: waves [%llu, %llu) of %llu, E %llu, count...\n", k, (unsigned long long)j, (unsigned long long)v0, (unsigned long long)v1, (unsigned long long)n_waves, (unsigned long long)E);
+            if (ctx->sw.timing2) fprintf(stderr, "[sx]   wave mission %zu slab %llu: waves [%llu, %llu) of %llu, E %llu, count...\n", k, (unsigned long long)j, (unsigned long long)v0, (unsigned long long)v1, (unsigned long long)n_waves, (unsigned long long)E);
             HIP_TRY(ctx, hipEventRecord(d.wave_ev[4 * j], sb));
             HIP_TRY(ctx, launch_wave_count(P, v0, v1, d_fb, d_ab, d_tot + 4 * j, w_scratch, w_scratch_cap, sb));
             HIP_TRY(ctx, hipEventRecord(d.wave_ev[4 * j + 1], sb));
@@ -276,7 +276,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
             if (d_leads) HIP_TRY(ctx, hipMemcpyAsync(h_tot + 4 * K, d_leads, 8, hipMemcpyDeviceToHost, sb));   // (pinned: 4096 bytes, K <= 64 slabs use 2048)
             HIP_TRY(ctx, hipStreamSynchronize(sb));
             if (d_leads && __builtin_popcountll(h_tot[4 * K] | left_leads) > 1) {
-                if (getenv("SX_TIMING")) fprintf(stderr, "[sx] wave replay mission %zu: -r and two kinds of lead bytes in this buffer: lane-per-region path\n", k);
+                if (ctx->sw.timing) fprintf(stderr, "[sx] wave replay mission %zu: -r and two kinds of lead bytes in this buffer: lane-per-region path\n", k);
                 return abandon(SX_WAVE_FALLBACK);
             }
             // Round 5: wavefronts whose warm-up windows led them to a wrong entry state run again from what their predecessor really left
@@ -284,8 +284,8 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
             // it began — until the verification passes; a chain of wrong wavefronts takes a launch per link.  (Before: any wrong
             // assumption sent the whole buffer to the lane-per-region path.)
             bool repaired = false;
-            if ((h_tot[4 * j + 2] & 0xFFFFFFFFull) != 0 && (h_tot[4 * j + 3] >> 32) == 0 && !getenv("SX_WAVE_FAIL") && !(getenv("SX_WAVE_REPAIR") && !atoi(getenv("SX_WAVE_REPAIR")))) {
-                const int max_rounds = getenv("SX_WAVE_REPAIR") ? std::max(1, atoi(getenv("SX_WAVE_REPAIR"))) : 48;
+            if ((h_tot[4 * j + 2] & 0xFFFFFFFFull) != 0 && (h_tot[4 * j + 3] >> 32) == 0 && !ctx->sw.wave_fail && ctx->sw.wave_repair != 0) {
+                const int max_rounds = ctx->sw.wave_repair > 0 ? ctx->sw.wave_repair : 48;
                 P.redo = 1;
                 for (int round = 0; round < max_rounds && (h_tot[4 * j + 2] & 0xFFFFFFFFull) != 0; round++) {
                     HIP_TRY(ctx, launch_wave_count(P, v0, v1, d_fb, d_ab, d_tot + 4 * j, w_scratch, w_scratch_cap, sb));
@@ -298,8 +298,8 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
                 repaired = true;
                 HIP_TRY(ctx, hipEventRecord(d.wave_ev[4 * j + 1], sb));   // (the count pass' time includes its repairs)
             }
-            if ((h_tot[4 * j + 2] & 0xFFFFFFFFull) != 0 || getenv("SX_WAVE_FAIL")) {   // (SX_WAVE_FAIL: tests of the way back)
-                if (getenv("SX_TIMING")) fprintf(stderr, "[sx] wave replay mission %zu: %llu wavefronts assumed a wrong entry state: lane-per-region path\n", k, (unsigned long long)(h_tot[4 * j + 2] & 0xFFFFFFFFull));
+            if ((h_tot[4 * j + 2] & 0xFFFFFFFFull) != 0 || ctx->sw.wave_fail) {   // (SX_WAVE_FAIL: tests of the way back)
+                if (ctx->sw.timing) fprintf(stderr, "[sx] wave replay mission %zu: %llu wavefronts assumed a wrong entry state: lane-per-region path\n", k, (unsigned long long)(h_tot[4 * j + 2] & 0xFFFFFFFFull));
                 return abandon(SX_WAVE_FALLBACK);
             }
             const bool by_desc = P.desc && (h_tot[4 * j + 2] >> 32) == 0;   // every wavefront of the slab left all its descriptors
@@ -315,7 +315,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
             }
             if (P.desc && !by_desc) { std::lock_guard<std::mutex> g(ctx->mu); ctx->stats.wave_desc_overflows++; }
             const uint64_t nf = h_tot[4 * j], nb = h_tot[4 * j + 1];
-            if (getenv("SX_TIMING2")) fprintf(stderr, "[sx]   ... counted %llu findings, %llu bytes at +%.2f ms\n", (unsigned long long)nf, (unsigned long long)nb, now_ms() - t0);
+            if (ctx->sw.timing2) fprintf(stderr, "[sx]   ... counted %llu findings, %llu bytes at +%.2f ms\n", (unsigned long long)nf, (unsigned long long)nb, now_ms() - t0);
             final_state = (uint32_t)h_tot[4 * j + 3];
             const uint64_t nfh_j = j == 0 ? nfh : 0, nbh_j = j == 0 ? nbh : 0;   // the host's entry windows go in front of the first slab
             if (nb + nbh_j > 0xFFFFFFFFull) { ctx->set_err("more than 4 GiB of strings in one chunk"); return abandon(SX_E_NOMEM); }
@@ -354,7 +354,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
                 seg.ext_nf = nfh_j + nf; seg.ext_na = nbh_j + nb; seg.dev_copy = d_all;
             } else if (deferred) {
                 HIP_TRY(ctx, hipStreamSynchronize(sb));
-                if (getenv("SX_TIMING2")) fprintf(stderr, "[sx]   ... written (left on the device) at +%.2f ms\n", now_ms() - t0);
+                if (ctx->sw.timing2) fprintf(stderr, "[sx]   ... written (left on the device) at +%.2f ms\n", now_ms() - t0);
                 seg.dev_only = true; seg.ext_nf = nfh_j + nf; seg.ext_na = nbh_j + nb; seg.dev_copy = d_all;
             } else {
                 PinnedPool::Block blk = ctx->pool->take(out_bytes + 64);
@@ -401,7 +401,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
     out->replay_bytes += len;
     { std::lock_guard<std::mutex> g(ctx->mu); ctx->stats.wave_windows += g_all - g_lo; }
     // the next whole buffer of this Mission does without stage A (sx_schedule.cpp) as long as this one was string-dense
-    if (k < ctx->wave_pred.size()) ctx->wave_pred[k] = (nf_all + nfh) * wave_min_density_bytes(m.wave_family) * 2 > len ? 1 : 0;
+    if (k < ctx->wave_pred.size()) ctx->wave_pred[k] = (nf_all + nfh) * wave_min_density_bytes(ctx, m.wave_family) * 2 > len ? 1 : 0;
     if (k < ctx->wave_density.size() && len) ctx->wave_density[k] = (double)(nf_all + nfh) / (double)len;   // sizes the next buffer's descriptors
     const double t1 = now_ms();
 
@@ -444,7 +444,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         ctx->states[k] = fin;
     }
     if (end_pos) *end_pos = len;
-    if (getenv("SX_TIMING"))
+    if (ctx->sw.timing)
         fprintf(stderr, "[sx] wave replay mission %zu: %llu windows in %llu wavefronts, %zu slab(s): entry + count + write + d2h %.2f ms (%llu findings, %llu string bytes%s), state %.2f ms\n",
                 k, (unsigned long long)(g_all - g_lo), (unsigned long long)n_waves, segs.size(), t1 - t0, (unsigned long long)(nf_all + nfh),
                 (unsigned long long)(nb_all + nbh), deferred ? ", left on the device" : "", now_ms() - t1);

@@ -825,17 +825,17 @@ size_t wave_scratch_bytes(uint64_t n_waves) {
 
 // (a launch of wave_replay_kernel<M, F, W, C, GREP>: with or without -g)
 #define SX_WV_UNPACK(...) __VA_ARGS__
-#define SX_WV_LAUNCH(targs, grid, block, dyn, stream, Q)                                                        \
+#define SX_WV_LAUNCH(targs, grid, block, stream, Q)                                                        \
     do {                                                                                                       \
-        if ((Q).grep_char >= 0) hipLaunchKernelGGL((wave_replay_kernel<SX_WV_UNPACK targs, 1>), grid, block, dyn, stream, Q);   \
-        else hipLaunchKernelGGL((wave_replay_kernel<SX_WV_UNPACK targs, 0>), grid, block, dyn, stream, Q);                      \
+        if ((Q).grep_char >= 0) hipLaunchKernelGGL((wave_replay_kernel<SX_WV_UNPACK targs, 1>), grid, block, 0, stream, Q);   \
+        else hipLaunchKernelGGL((wave_replay_kernel<SX_WV_UNPACK targs, 0>), grid, block, 0, stream, Q);                      \
     } while (0)
 // (families 0 - 2: with -r as well)
-#define SX_WV_LAUNCH_S(targs, grid, block, dyn, stream, Q)                                                      \
+#define SX_WV_LAUNCH_S(targs, grid, block, stream, Q)                                                      \
     do {                                                                                                       \
-        if ((Q).same && (Q).grep_char >= 0) hipLaunchKernelGGL((wave_replay_kernel<SX_WV_UNPACK targs, 3>), grid, block, dyn, stream, Q);   \
-        else if ((Q).same) hipLaunchKernelGGL((wave_replay_kernel<SX_WV_UNPACK targs, 2>), grid, block, dyn, stream, Q);   \
-        else SX_WV_LAUNCH(targs, grid, block, dyn, stream, Q);                                                  \
+        if ((Q).same && (Q).grep_char >= 0) hipLaunchKernelGGL((wave_replay_kernel<SX_WV_UNPACK targs, 3>), grid, block, 0, stream, Q);   \
+        else if ((Q).same) hipLaunchKernelGGL((wave_replay_kernel<SX_WV_UNPACK targs, 2>), grid, block, 0, stream, Q);   \
+        else SX_WV_LAUNCH(targs, grid, block, stream, Q);                                                  \
     } while (0)
 // pass 1 of wavefronts [v0, v1): counts, their exclusive sums from v0 on (fbase[v], abase[v]), the verification against
 // wavefront v0 - 1 (an earlier launch on the same stream) and among themselves
@@ -845,16 +845,15 @@ hipError_t launch_wave_count(const WaveParams& P, uint64_t v0, uint64_t v1, uint
     const uint64_t n = v1 - v0;
     WaveParams Q = P;
     Q.v0 = v0; Q.v1 = v1;
-    const unsigned dyn = getenv("SX_WAVE_DYN_LDS") ? (unsigned)atoi(getenv("SX_WAVE_DYN_LDS")) : 0u;   // experiments: fewer wavefronts per CU
     if (P.wave_grid && !P.redo) { hipError_t ez = hipMemsetAsync(P.wave_grid + v0, 0, (size_t)n * 4, stream); if (ez != hipSuccess) return ez; }   // (a repair launch reads what the first one published)
-    if (P.family == 5) SX_WV_LAUNCH((0, 5, 4, 1), dim3((unsigned)((n + 3) / 4)), dim3(256), dyn, stream, Q);
-    else if (P.family == 4 && P.swar.cls) SX_WV_LAUNCH((0, 4, 4, 1), dim3((unsigned)((n + 3) / 4)), dim3(256), dyn, stream, Q);
-    else if (P.family == 4) SX_WV_LAUNCH((0, 4, 4, 0), dim3((unsigned)((n + 3) / 4)), dim3(256), dyn, stream, Q);
-    else if (P.family == 2) SX_WV_LAUNCH_S((0, 2, 1, 0), dim3((unsigned)n), dim3(64), dyn, stream, Q);
-    else if (P.family == 1 && P.swar.cls) SX_WV_LAUNCH_S((0, 1, 1, 1), dim3((unsigned)n), dim3(64), dyn, stream, Q);
-    else if (P.family == 1) SX_WV_LAUNCH_S((0, 1, 1, 0), dim3((unsigned)n), dim3(64), dyn, stream, Q);
-    else if (P.swar.cls) SX_WV_LAUNCH_S((0, 0, 1, 1), dim3((unsigned)n), dim3(64), dyn, stream, Q);
-    else SX_WV_LAUNCH_S((0, 0, 1, 0), dim3((unsigned)n), dim3(64), dyn, stream, Q);
+    if (P.family == 5) SX_WV_LAUNCH((0, 5, 4, 1), dim3((unsigned)((n + 3) / 4)), dim3(256), stream, Q);
+    else if (P.family == 4 && P.swar.cls) SX_WV_LAUNCH((0, 4, 4, 1), dim3((unsigned)((n + 3) / 4)), dim3(256), stream, Q);
+    else if (P.family == 4) SX_WV_LAUNCH((0, 4, 4, 0), dim3((unsigned)((n + 3) / 4)), dim3(256), stream, Q);
+    else if (P.family == 2) SX_WV_LAUNCH_S((0, 2, 1, 0), dim3((unsigned)n), dim3(64), stream, Q);
+    else if (P.family == 1 && P.swar.cls) SX_WV_LAUNCH_S((0, 1, 1, 1), dim3((unsigned)n), dim3(64), stream, Q);
+    else if (P.family == 1) SX_WV_LAUNCH_S((0, 1, 1, 0), dim3((unsigned)n), dim3(64), stream, Q);
+    else if (P.swar.cls) SX_WV_LAUNCH_S((0, 0, 1, 1), dim3((unsigned)n), dim3(64), stream, Q);
+    else SX_WV_LAUNCH_S((0, 0, 1, 0), dim3((unsigned)n), dim3(64), stream, Q);
     void* tmp = (void*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
     size_t tmp_bytes = scratch_bytes - (size_t)((uint8_t*)tmp - (uint8_t*)scratch);
     auto itf = rocprim::make_transform_iterator(rocprim::counting_iterator<u64>(0), U32ToU64{ P.wave_nf + v0 });
@@ -876,16 +875,15 @@ hipError_t launch_wave_write(const WaveParams& P, uint64_t v0, uint64_t v1, hipS
     if (v1 <= v0) return hipSuccess;
     WaveParams Q = P;
     Q.v0 = v0; Q.v1 = v1;
-    const unsigned dyn = getenv("SX_WAVE_DYN_LDS") ? (unsigned)atoi(getenv("SX_WAVE_DYN_LDS")) : 0u;
     if (P.wave_grid) { hipError_t ez = hipMemsetAsync(P.wave_grid + v0, 0, (size_t)(v1 - v0) * 4, stream); if (ez != hipSuccess) return ez; }
-    if (P.family == 5) SX_WV_LAUNCH((1, 5, 4, 1), dim3((unsigned)(((v1 - v0) + 3) / 4)), dim3(256), dyn, stream, Q);
-    else if (P.family == 4 && P.swar.cls) SX_WV_LAUNCH((1, 4, 4, 1), dim3((unsigned)(((v1 - v0) + 3) / 4)), dim3(256), dyn, stream, Q);
-    else if (P.family == 4) SX_WV_LAUNCH((1, 4, 4, 0), dim3((unsigned)(((v1 - v0) + 3) / 4)), dim3(256), dyn, stream, Q);
-    else if (P.family == 2) SX_WV_LAUNCH_S((1, 2, 1, 0), dim3((unsigned)(v1 - v0)), dim3(64), dyn, stream, Q);
-    else if (P.family == 1 && P.swar.cls) SX_WV_LAUNCH_S((1, 1, 1, 1), dim3((unsigned)(v1 - v0)), dim3(64), dyn, stream, Q);
-    else if (P.family == 1) SX_WV_LAUNCH_S((1, 1, 1, 0), dim3((unsigned)(v1 - v0)), dim3(64), dyn, stream, Q);
-    else if (P.swar.cls) SX_WV_LAUNCH_S((1, 0, 1, 1), dim3((unsigned)(v1 - v0)), dim3(64), dyn, stream, Q);
-    else SX_WV_LAUNCH_S((1, 0, 1, 0), dim3((unsigned)(v1 - v0)), dim3(64), dyn, stream, Q);
+    if (P.family == 5) SX_WV_LAUNCH((1, 5, 4, 1), dim3((unsigned)(((v1 - v0) + 3) / 4)), dim3(256), stream, Q);
+    else if (P.family == 4 && P.swar.cls) SX_WV_LAUNCH((1, 4, 4, 1), dim3((unsigned)(((v1 - v0) + 3) / 4)), dim3(256), stream, Q);
+    else if (P.family == 4) SX_WV_LAUNCH((1, 4, 4, 0), dim3((unsigned)(((v1 - v0) + 3) / 4)), dim3(256), stream, Q);
+    else if (P.family == 2) SX_WV_LAUNCH_S((1, 2, 1, 0), dim3((unsigned)(v1 - v0)), dim3(64), stream, Q);
+    else if (P.family == 1 && P.swar.cls) SX_WV_LAUNCH_S((1, 1, 1, 1), dim3((unsigned)(v1 - v0)), dim3(64), stream, Q);
+    else if (P.family == 1) SX_WV_LAUNCH_S((1, 1, 1, 0), dim3((unsigned)(v1 - v0)), dim3(64), stream, Q);
+    else if (P.swar.cls) SX_WV_LAUNCH_S((1, 0, 1, 1), dim3((unsigned)(v1 - v0)), dim3(64), stream, Q);
+    else SX_WV_LAUNCH_S((1, 0, 1, 0), dim3((unsigned)(v1 - v0)), dim3(64), stream, Q);
     return hipGetLastError();
 }
 

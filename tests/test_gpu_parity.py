@@ -295,13 +295,15 @@ def test_large_input_properties():
     r1 = sc.scan_device(d, n, file_id=1)
     a = r1.findings()
     sc.reset()
-    # pieces (scan kernels queued two deep) must not matter
+    # pieces (scan kernels queued two deep) must not matter (a Scanner of its own: the switches are read when it is created)
     import os
     os.environ["SX_PIECE_MIB"] = "96"
     try:
-        rp = sc.scan_device(d, n, file_id=1)
+        sc_p = sx.Scanner(ms, device=0)
+        rp = sc_p.scan_device(d, n, file_id=1)
         assert len(rp.segments()) > 1 and rp.findings() == a
         rp.free()
+        sc_p.close()
     finally:
         del os.environ["SX_PIECE_MIB"]
     sc.reset()

@@ -10,7 +10,8 @@ ENCS = ["utf-8", "ascii", "utf-16le", "utf-16be", "koi8-r", "ibm866", "windows-1
 ENCS_MORE = ["iso-8859-7", "windows-1255", "windows-874", "koi8-u", "macintosh", "iso-8859-6", "windows-1257", "x-mac-cyrillic"]
 AFS = [None, "All", "All-Ctrl", "All-Ctrl+Wsp", "None", "Wsp", "0x7ffffffe000000007ffffffe00000000"]
 UBFS = [None, "African", "All", "Common", "Cyrillic", "Latin", "Asian", "Uncommon", "None", "Hebrew", "Cjk", "Hangul", "Kana", "0x0000fffe00000000", "0x00003ffcfffffffc"]
-# alternative paths behind environment switches, read by the library at call time
+# alternative paths behind environment switches (stringsext_amd/csrc/sx_switches.hpp), read by the library when a context is created:
+# set them before the Scanner exists (run_cli_product makes one per call)
 SWITCH_SETS = [{}, {}, {}, {"SX_RESULT_ON_DEVICE": "1"}, {"SX_RESULT_ON_DEVICE": "1", "SX_WAVE_REPLAY": "1"}, {"SX_RESULT_ON_DEVICE": "1", "SX_DEVICE_JOIN_MIN": "1"}, {"SX_NO_REPLAY_CACHE": "1"}, {"SX_HOST_STITCH": "1"}, {"SX_NO_REPLAY_SKIP": "1"}, {"SX_REPLAY_CACHE_MIB": "0"},
                {"SX_REGION_CAP": "2"}, {"SX_REGION_CAP": "0"}, {"SX_DEVICE_JOIN_MIN": "1"}, {"SX_HOST_MERGE": "1"},
                {"SX_NO_REPLAY_CACHE": "1", "SX_NO_REPLAY_SKIP": "1"}, {"SX_HOST_STITCH": "1", "SX_DEVICE_JOIN_MIN": "1"},

@@ -187,7 +187,7 @@ enum {
     SX_OPT_MISSION_STREAMS = 16u, /* a scan stream per mission (default: one scan stream + one for everything else) */
     SX_OPT_NO_FUSED_SCAN = 64u,   /* (round 6) one scan launch per Mission, each reading the whole buffer (rounds 1-5), instead of ONE launch that
                                      reads it once for all Missions whose classifiers the fused kernel holds (csrc/sx_fused.hip) */
-    SX_OPT_RESULT_ON_DEVICE = 32u /* (round 5) a context with ONE Mission: a buffer's result that the device wrote in one block — a string-dense
+    SX_OPT_RESULT_ON_DEVICE = 32u /* A context with ONE Mission (round 5): a buffer's result that the device wrote in one block — a string-dense
                                      buffer (the wave path: text, `-e ascii -n 4` on binaries, where moving the findings to the host is what bounds
                                      the scan: sx_finding16 records) or a sparse one replayed on the device (sx_finding records) — stays in HBM:
                                      sx_result_segment_device() hands out device pointers to its records and strings, for hosts that go on
@@ -196,7 +196,20 @@ enum {
                                      is the context's).  The
                                      host accessors (sx_result_segment, ..._packed, sx_print_findings, ...) still work: the first one copies the
                                      segment to the host (SX_E_STATE if a later scan has overwritten it).  Every other result is in host memory
-                                     as without the flag; the sharded entry points ignore it. */
+                                     as without the flag; the sharded entry points ignore it.
+                                     A context with SEVERAL Missions, scanned with sx_scan / sx_scan_device (one buffer, one piece): the merged findings
+                                     stay in HBM — one segment per part of the merger, in print order, every segment on the device or none.  Records
+                                     are sx_finding16, with sx_segment_info as ever, where the merger packs: every Mission's -q <= 16000, SX_PACKED not 0;
+                                     else sx_finding.  LAYOUT of these segments: the strings lie back to back in record order — str_off[0] == 0,
+                                     str_off[i + 1] == str_off[i] + str_len[i], arena_len == sum(str_len) — so a consumer that walks the records reads
+                                     neighbouring bytes with neighbouring lanes; every part starts 256-byte aligned.  The scan call returns when the
+                                     kernels that write the result are done: the pointers may be read from any stream at once.  Lifetime and host
+                                     access as above; what the host accessors return is what a context without the flag returns (the host result keeps
+                                     its own string layout).  The result is in host memory, as without the flag, in these cases and only these: no
+                                     findings at all; Missions that do not count from the same origin (different counter_offset); the sharded entry
+                                     points; a call that accumulates several buffers into one result; pieces forced by SX_PIECE_MIB / SX_SEQ_PIECE_MIB
+                                     / SX_SEQ_PIECE_KIB; SX_HOST_MERGE; a host-only context; more than 16 Missions or 2^32 findings or more in one
+                                     part (the radix-sort merger); the device block cannot be allocated (the scan does not fail). */
 };
 
 /* ---- Mission front end (src/mission.rs:448-749, src/options.rs:12-33) ------------------------------
@@ -410,7 +423,8 @@ int  sx_transport_gather(sx_transport* t, const sx_result* mine, int root, uint6
 /* (round 5, SX_OPT_RESULT_ON_DEVICE) Segment i where it lies in HBM: *d_records = n records (sx_finding16 if *packed, else sx_finding;
  * what they share: *info), *d_arena = arena_len bytes of strings (str_off counts from there).  *d_records == NULL: the segment is in host
  * memory (read it with sx_result_segment / sx_result_segment_packed).  SX_E_STATE: a later scan has reused the memory.  One caller at a
- * time per result: the host accessors' first use of such a segment moves it to host memory. */
+ * time per result: the host accessors' first use of such a segment moves it to host memory (that segment only: the other segments'
+ * pointers stay valid).  Several Missions: one segment per merger part, strings back to back in record order (SX_OPT_RESULT_ON_DEVICE). */
 int               sx_result_segment_device(const sx_result* r, uint64_t i, const void** d_records, uint64_t* n_findings,
                                            const uint8_t** d_arena, uint64_t* arena_len, int* packed, sx_segment_info* info);
 uint64_t          sx_result_count(const sx_result* r);

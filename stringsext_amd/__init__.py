@@ -17,7 +17,7 @@ SX_OK, SX_E_INVALID, SX_E_NO_DEVICE, SX_E_HIP, SX_E_NOMEM, SX_E_STATE, SX_E_HALO
 SX_HOST_ONLY = -1
 SX_OPT_GENERIC_KERNELS, SX_OPT_DEVICE_REPLAY, SX_OPT_HOST_REPLAY = 1, 2, 4
 SX_OPT_NO_FUSED_SCAN = 64      # round 6: one scan launch per Mission instead of the fused one (one read of the buffer for several Missions)
-SX_OPT_RESULT_ON_DEVICE = 32   # round 5: a string-dense buffer's result stays in HBM (Result.device_segments)
+SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
        "iso-8859-3": 23, "iso-8859-4": 24, "iso-8859-6": 25, "iso-8859-7": 26, "iso-8859-8": 27,
@@ -299,7 +299,9 @@ class Result:
 
     def device_segments(self):
         """[(device pointer to the records or None, n, device pointer to the strings, bytes of strings, packed?, SegmentInfo)] —
-        SX_OPT_RESULT_ON_DEVICE: the segments that still lie in HBM (None: that segment is in host memory)"""
+        SX_OPT_RESULT_ON_DEVICE: the segments that still lie in HBM (None: that segment is in host memory).  With several Missions
+        there is one segment per part of the merger, all of them on the device or none, and a segment's strings lie back to back in
+        record order: str_off[0] == 0, str_off[i + 1] == str_off[i] + str_len[i] (include/stringsext_amd.h)."""
         L = lib()
         L.sx_result_segment_device.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(SegmentInfo)]
@@ -352,7 +354,9 @@ class Result:
 
 
 class Scanner:
-    """One sx_ctx: N missions bound to one HIP device (device=SX_HOST_ONLY: replay stage only)."""
+    """One sx_ctx: N missions bound to one HIP device (device=SX_HOST_ONLY: replay stage only).
+    result_on_device=True (SX_OPT_RESULT_ON_DEVICE): the result of scan() / scan_device() stays in HBM — Result.device_segments(),
+    Scanner.download() —, with one Mission or several; valid until the next buffer is scanned on this Scanner."""
 
     def __init__(self, mission_dicts, device=0, subchunk_bytes=0, record_capacity=0, generic_kernels=False,
                  replay_threads=0, device_replay=None, result_on_device=False, fused_scan=True):

@@ -386,6 +386,8 @@ void sx_destroy(sx_ctx* ctx) {
         if (ctx->post_stream) (void)hipStreamDestroy(ctx->post_stream);
         if (ctx->merge_copy_stream) (void)hipStreamDestroy(ctx->merge_copy_stream);
         if (ctx->d_merge) (void)hipFree(ctx->d_merge);
+        if (ctx->d_result) (void)hipFree(ctx->d_result);
+        if (ctx->d_result_up) (void)hipFree(ctx->d_result_up);
         for (hipEvent_t e : ctx->merge_ev) if (e) (void)hipEventDestroy(e);
         if (ctx->ev_interleaved) (void)hipEventDestroy(ctx->ev_interleaved);
         if (ctx->d_input) (void)hipFree(ctx->d_input);

@@ -161,6 +161,10 @@ struct sx_ctx {
     // device_merge's own memory (two output buffers of merge_out_room bytes each, then the sort's scratch): the copy of a part may
     // still read it while the next piece of the buffer is scanned and replayed (merge_async, scan_common's sequential pieces)
     uint8_t* d_merge = nullptr; uint64_t d_merge_cap = 0, merge_out_room = 0, merge_n_out = 0;
+    // SX_OPT_RESULT_ON_DEVICE with several Missions: the result block (one per buffer, grown only: a buffer's merged parts, each 256-byte
+    // aligned, stay here for the caller — valid while the epoch stands) and where Missions' lists that exist on the host only are uploaded
+    uint8_t* d_result = nullptr; uint64_t d_result_cap = 0;
+    uint8_t* d_result_up = nullptr; uint64_t d_result_up_cap = 0;
     bool merge_async = false;                           // device_merge returns with its last copies in flight; merge_drain() waits
     bool merge_copy_pending[2] = { false, false };      // a copy out of output buffer 0 / 1 was queued and not waited for
     uint64_t merge_parts = 0;                           // parts merged so far (their parity picks the output buffer)
@@ -301,6 +305,7 @@ int stage_a_launch(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
                    const std::vector<uint32_t>& parity, const std::vector<uint64_t>& min_chars, int si);
 struct ReplayJob;
 int ensure_copy_stream(sx_ctx* ctx);   // sx_stage_b.cpp
+bool result_stays_on_device(const sx_ctx* ctx, const ReplayJob& job);   // sx_stage_b.cpp: SX_OPT_RESULT_ON_DEVICE, several Missions: this call qualifies
 int merge_drain(sx_ctx* ctx);          // sx_stage_b.cpp: waits for what device_merge left in flight (merge_async)
 int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_bytes, uint64_t len,
                    const std::vector<uint32_t>& parity, const std::vector<uint64_t>& min_chars, int si,

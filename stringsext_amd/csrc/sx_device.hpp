@@ -251,12 +251,20 @@ hipError_t launch_wave_emit(const WaveParams& P, uint64_t v0, uint64_t v1, hipSt
 // interleave several missions' findings on the device (sx_sort.hip); every src and out = [findings][string bytes]
 hipError_t merge_findings_device_part(const sx_finding* const* f, const uint8_t* const* a, const uint64_t* nf, const uint64_t* nb,
                                       const uint32_t* off0, int n_missions, void* out, void* scratch, size_t scratch_bytes,
-                                      hipStream_t stream, int packed = 0);
+                                      hipStream_t stream, int packed = 0, int ordered = 0);
+// (ordered, SX_OPT_RESULT_ON_DEVICE with several Missions: the part's strings back to back in record order — the placement notes every
+//  record's source, order_part_strings (sx_result_dev.hip: a scan over str_len, then the gather of sx_result_core.hpp) replaces the
+//  per-Mission block copies; one-pass merger only)
 bool merge_part_can_pack(uint64_t n, int n_missions);   // the one-pass merger takes the part (else the radix sort, which writes sx_finding only)
 hipError_t launch_slab_cuts(const ReplayParams& P, uint32_t n_slabs, uint64_t* idx, uint64_t* hi, hipStream_t stream);
 hipError_t launch_merge_cuts(const sx_finding* f, uint64_t n, uint64_t nb, const uint64_t* cuts, uint32_t n_cuts, uint64_t* idx,
                              uint64_t* off, hipStream_t stream);
-size_t merge_findings_scratch_bytes(uint64_t n_findings, int n_missions);
+size_t merge_findings_scratch_bytes(uint64_t n_findings, int n_missions, int ordered = 0);
+// the strings of n placed records (recs; sx_finding16 if packed), each still at src[i], to their places in record order in `arena`,
+// str_off rewritten; scratch: order_strings_scratch_bytes(n), 256-aligned
+size_t order_strings_scratch_bytes(uint64_t n);
+hipError_t order_part_strings(void* recs, uint64_t n, int packed, const uint64_t* src, uint8_t* arena, void* scratch, size_t scratch_bytes,
+                              hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
 hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit

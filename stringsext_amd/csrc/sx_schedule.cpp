@@ -48,6 +48,9 @@ static uint64_t seq_piece_bytes(const sx_ctx* ctx, uint64_t len) {
         piece = (uint64_t)ctx->sw.seq_piece_mib << 20;
         if (piece == 0) return len;
     } else {
+        // (SX_OPT_RESULT_ON_DEVICE: the merged findings stay in HBM — no copy to hide behind the next piece's kernels, and pieces would send
+        //  the result to the host; as piece_bytes(): in one go unless a switch says otherwise)
+        if (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) return len;
         if (ctx->missions.size() < 2 || ctx->out_density <= 0) return len;
         const double out = ctx->out_density * (double)len;
         if (out < 4.0 * (double)(1ull << 30)) return len;
@@ -187,7 +190,8 @@ struct BufferScan {
             std::vector<std::thread>& t;
             ~Joiner() { for (auto& x : t) if (x.joinable()) x.join(); }
         } joiner{ wave_threads };
-        const uint64_t defer_all = nm >= 2 ? ctx->sw.defer_min_bytes : 0;
+        // (the merged result is to stay in HBM: then every Mission's output does, whatever its size — no early copy to the host)
+        const uint64_t defer_all = nm >= 2 ? (result_stays_on_device(ctx, job) ? 1 : ctx->sw.defer_min_bytes) : 0;
         if (nm >= 2 && ctx->sw.wave_threads) {
             if (ctx->wave_density.size() != nm) ctx->wave_density.assign(nm, 0.0);
             for (size_t k = 0; k < nm; k++) {

@@ -275,6 +275,8 @@ struct MergeLists {
     uint64_t nf[kMergeLists];
     uint64_t out_base[kMergeLists];   // unused by the placement (ranks are absolute), kept for the arena bases below
     uint32_t arena_adj[kMergeLists];  // added to str_off (mod 2^32)
+    const uint8_t* a[kMergeLists];    // ordered parts (merge_place_kernel's src): the list's strings, str_off counting from off0
+    uint32_t off0[kMergeLists];
     int n;
 };
 struct MergeRange { uint64_t base; uint32_t shift, pad; };
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(256) void merge_bounds_kernel(MergeLists L, uint32_
     bounds[i] = (uint32_t)v;
 }
 __global__ __launch_bounds__(256) void merge_place_kernel(MergeLists L, int m, uint32_t T, const MergeRange* rg, const uint32_t* bounds,
-                                                          void* out, int packed) {
+                                                          void* out, int packed, uint64_t* src) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= L.nf[m]) return;
     sx_finding f = L.f[m][i];
@@ -335,6 +337,8 @@ __global__ __launch_bounds__(256) void merge_place_kernel(MergeLists L, int m, u
         const uint64_t lo = b[0], hi = b[1];
         rank += o < m ? merge_upper(L.f[o], lo, hi, p) : merge_lower(L.f[o], lo, hi, p);
     }
+    // (an ordered part: the string stays where it is until order_part_strings has run — sx_result_dev.hip —, which also sets str_off)
+    if (src) src[rank] = (uint64_t)(uintptr_t)(L.a[m] + (uint32_t)(f.str_off - L.off0[m]));
     f.str_off += L.arena_adj[m];   // (mod 2^32: a part's base may be "negative", see merge_findings_device_part)
     if (packed) {   // include/stringsext_amd.h sx_finding16: what crosses PCIe is half the size
         sx_finding16 p;
@@ -369,19 +373,23 @@ static size_t merge_sort_scratch_bytes(uint64_t n) {
     return n * sizeof(sx_finding) + 4 * n * 8 + tmp + 2048;
 }
 bool merge_part_can_pack(uint64_t n, int n_missions) { return n_missions <= kMergeLists && n < 0xFFFFFFFFull; }
-size_t merge_findings_scratch_bytes(uint64_t n, int n_missions) {
+static size_t merge_tables_bytes(uint64_t n, int n_missions) { return (256 + ((size_t)merge_tiles(n) + 1) * 4 * (size_t)n_missions + 255) / 256 * 256; }
+size_t merge_findings_scratch_bytes(uint64_t n, int n_missions, int ordered) {
     if (n_missions > kMergeLists || n >= 0xFFFFFFFFull) return merge_sort_scratch_bytes(n);
+    // (ordered: + every placed record's source address, + the scan's offsets and storage)
+    if (ordered) return 512 + merge_tables_bytes(n, n_missions) + ((size_t)n * 8 + 255) / 256 * 256 + order_strings_scratch_bytes(n);
     return 512 + ((size_t)merge_tiles(n) + 1) * 4 * (size_t)n_missions + 256;
 }
 // One part of the interleave: of mission m the findings f[m][0 .. nf[m]) whose strings are a[m][0 .. nb[m]) and whose str_off
 // count from off0[m] (the part's first string); out = [sum nf findings][sum nb bytes].
 hipError_t merge_findings_device_part(const sx_finding* const* f, const uint8_t* const* a, const uint64_t* nf, const uint64_t* nb,
                                       const uint32_t* off0, int n_missions, void* out, void* scratch, size_t scratch_bytes,
-                                      hipStream_t stream, int packed) {
+                                      hipStream_t stream, int packed, int ordered) {
     uint64_t n = 0;
     for (int m = 0; m < n_missions; m++) n += nf[m];
     if (n == 0) return hipSuccess;
-    if (scratch_bytes < merge_findings_scratch_bytes(n, n_missions)) return hipErrorInvalidValue;
+    if (scratch_bytes < merge_findings_scratch_bytes(n, n_missions, ordered)) return hipErrorInvalidValue;
+    if (ordered && !(n_missions <= kMergeLists && n < 0xFFFFFFFFull)) return hipErrorInvalidValue;
     uint8_t* base = (uint8_t*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
     if (packed && !(n_missions <= kMergeLists && n < 0xFFFFFFFFull)) return hipErrorInvalidValue;   // (merge_part_can_pack)
     sx_finding* out_f = (sx_finding*)out;
@@ -392,7 +400,8 @@ hipError_t merge_findings_device_part(const sx_finding* const* f, const uint8_t*
         uint64_t ab = 0;
         for (int m = 0; m < n_missions; m++) {
             L.f[m] = f[m]; L.nf[m] = nf[m]; L.arena_adj[m] = (uint32_t)ab - off0[m];
-            if (nf[m] && nb[m]) {
+            L.a[m] = a[m]; L.off0[m] = off0[m];
+            if (nf[m] && nb[m] && !ordered) {
                 hipError_t e = hipMemcpyAsync(out_a + ab, a[m], nb[m], hipMemcpyDeviceToDevice, stream);
                 if (e != hipSuccess) return e;
             }
@@ -401,12 +410,17 @@ hipError_t merge_findings_device_part(const sx_finding* const* f, const uint8_t*
         const uint32_t T = merge_tiles(n);
         MergeRange* rg = (MergeRange*)base;
         uint32_t* bounds = (uint32_t*)(base + 256);
+        uint64_t* src = ordered ? (uint64_t*)(base + merge_tables_bytes(n, n_missions)) : nullptr;
         hipLaunchKernelGGL(merge_range_kernel, dim3(1), dim3(64), 0, stream, L, T, rg);
         const uint64_t nb_threads = ((uint64_t)T + 1) * (uint64_t)n_missions;
         hipLaunchKernelGGL(merge_bounds_kernel, dim3((unsigned)((nb_threads + 255) / 256)), dim3(256), 0, stream, L, T, rg, bounds);
         for (int m = 0; m < n_missions; m++)
             if (nf[m])
-                hipLaunchKernelGGL(merge_place_kernel, dim3((unsigned)((nf[m] + 255) / 256)), dim3(256), 0, stream, L, m, T, rg, bounds, (void*)out_f, packed);
+                hipLaunchKernelGGL(merge_place_kernel, dim3((unsigned)((nf[m] + 255) / 256)), dim3(256), 0, stream, L, m, T, rg, bounds, (void*)out_f, packed, src);
+        if (ordered) {
+            uint8_t* rest = (uint8_t*)src + ((size_t)n * 8 + 255) / 256 * 256;
+            return order_part_strings(out, n, packed, src, out_a, rest, scratch_bytes - (size_t)(rest - (uint8_t*)scratch), stream);
+        }
         return hipGetLastError();
     }
     sx_finding* all = (sx_finding*)base;

@@ -488,6 +488,52 @@ static int fetch_deferred(sx_ctx* ctx, MissionFindings& mf) {
     return SX_OK;
 }
 
+// SX_OPT_RESULT_ON_DEVICE with several Missions: does this call's merged result stay in HBM?  (What only shows later — no findings,
+// Missions that count from different origins, no memory for the block — is device_merge's to see.)
+bool result_stays_on_device(const sx_ctx* ctx, const ReplayJob& job) {
+    return (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) && ctx->missions.size() >= 2 && merge_part_can_pack(1, (int)ctx->missions.size()) && !ctx->host_only &&
+           job.d_bytes && job.commit_state && !ctx->sharded_call && ctx->single_piece && !ctx->sw.host_merge;
+}
+
+// ... then a Mission's list that exists on the host only (few runs: the host replayed it; ISO-2022-JP's sequential pass; regions the device
+// gave back) joins the merge as a device list: [records][strings] of all such lists through one pinned block, one copy, into memory of
+// the context's.  SX_E_NOMEM without an error text: no memory for it, the result goes to the host.
+static int upload_host_lists(sx_ctx* ctx, std::vector<MissionFindings>& per, std::vector<char>& uploaded) {
+    uint64_t need = 0;
+    for (auto& mf : per) {
+        if (!mf.count() || mf.dev_copy) continue;
+        if (!mf.more.empty() || mf.packed) return SX_E_NOMEM;   // (a single Mission's forms)
+        need += (mf.count() * sizeof(sx_finding) + mf.strings_len() + 255) & ~(uint64_t)255;
+    }
+    if (!need) return SX_OK;
+    if (ctx->d_result_up_cap < need) {
+        if (ctx->d_result_up) HIP_TRY(ctx, hipFree(ctx->d_result_up));
+        ctx->d_result_up = nullptr; ctx->d_result_up_cap = 0;
+        if (hipMalloc((void**)&ctx->d_result_up, need) != hipSuccess) { (void)hipGetLastError(); ctx->d_result_up = nullptr; return SX_E_NOMEM; }
+        ctx->d_result_up_cap = need;
+    }
+    PinnedPool::Block blk = ctx->pool->take(need);
+    if (!blk.p) return SX_E_NOMEM;
+    uint64_t at = 0;
+    for (size_t k = 0; k < per.size(); k++) {
+        MissionFindings& mf = per[k];
+        if (!mf.count() || mf.dev_copy) continue;
+        const uint64_t fb = mf.count() * sizeof(sx_finding);
+        memcpy((uint8_t*)blk.p + at, mf.data(), fb);
+        memcpy((uint8_t*)blk.p + at + fb, mf.strings(), mf.strings_len());
+        mf.dev_copy = ctx->d_result_up + at; uploaded[k] = 1;
+        at += (fb + mf.strings_len() + 255) & ~(uint64_t)255;
+    }
+    hipError_t e = hipMemcpyAsync(ctx->d_result_up, blk.p, need, hipMemcpyHostToDevice, ctx->post_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->post_stream);
+    ctx->pool->give(blk);
+    if (e != hipSuccess) {
+        for (size_t k = 0; k < per.size(); k++) if (uploaded[k]) { per[k].dev_copy = nullptr; uploaded[k] = 0; }
+        HIP_TRY(ctx, e);
+    }
+    return SX_OK;
+}
+
 int merge_drain(sx_ctx* ctx) {
     std::lock_guard<std::recursive_mutex> g(ctx->grow_mu);   // (a wave Mission's thread may get here through ensure_rp)
     if (ctx->post_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->post_stream));
@@ -503,6 +549,10 @@ int merge_drain(sx_ctx* ctx) {
 // boundaries into parts (each at most SX_MERGE_PART_MIB of strings and SX_MERGE_PART_FINDINGS findings) that become one segment
 // of the result each; the copy of part j runs while part j+1 is interleaved.  If the conditions do not hold the host merges
 // (merge_findings).
+// SX_OPT_RESULT_ON_DEVICE (result_stays_on_device): the parts are written one behind the other, each 256-byte aligned, into the context's
+// result block and stay there — no pinned block, no copy; each becomes a segment the caller reads through sx_result_segment_device.
+// Their strings lie back to back in record order (merge_findings_device_part's `ordered`).  Small results and a single Mission with
+// findings among several take this way too, lists on the host are uploaded first; all segments of a result are on the device or none is.
 static int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFindings>& per, Result* into) {
     const size_t nm = per.size();
     size_t with = 0, on_dev = 0, deferred = 0;
@@ -516,11 +566,22 @@ static int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFi
         total += per[k].count(); bytes += per[k].strings_len();
         same_origin = same_origin && job.consumed0[k] == job.consumed0[0];
     }
+    std::vector<char> uploaded(nm, 0);
     auto give_up = [&]() -> int {
+        for (size_t k = 0; k < nm; k++) if (uploaded[k]) { per[k].dev_copy = nullptr; uploaded[k] = 0; }   // (the host's copy is the list again)
         for (auto& mf : per) { if (mf.keep_on_device) continue; int rc = fetch_deferred(ctx, mf); if (rc != SX_OK) return rc; }   // (SX_OPT_RESULT_ON_DEVICE: it stays)
         return SX_OK;
     };
-    if (!(with >= 2 && on_dev == with && same_origin && total >= 4096 && !ctx->sw.host_merge)) return give_up();
+    bool keep = result_stays_on_device(ctx, job) && total > 0 && same_origin;
+    if (keep && on_dev != with) {
+        const int rc = upload_host_lists(ctx, per, uploaded);
+        if (rc == SX_E_NOMEM) keep = false;
+        else if (rc != SX_OK) return rc;
+        else on_dev = with;
+    }
+    // (the way to the host: worth it for two lists or more of some size, all of them still in HBM)
+    auto host_way_ok = [&]() { return with >= 2 && on_dev == with && same_origin && total >= 4096 && !ctx->sw.host_merge; };
+    if (!keep && !host_way_ok()) return give_up();
     const double tm0 = now_ms();
     // The records cross PCIe as sx_finding16 (include/stringsext_amd.h): half the bytes of what bounds this path.  Not with lines of
     // more than 16 000 chars (str_len has 16 bits there), nor where the one-pass merger does not apply (SX_PACKED=0: tests).
@@ -584,11 +645,30 @@ static int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFi
         for (size_t k = 0; k < nm; k++) { pb += off[k][j + 1] - off[k][j]; pf += idx[k][j + 1] - idx[k][j]; }
         max_out = std::max(max_out, pf * sizeof(sx_finding) + pb); max_n = std::max(max_n, pf);
     }
+    if (keep) {   // the result block: every part's [records][strings], 256-byte aligned; the merger's scratch is the context's
+        uint64_t need = 0;
+        for (uint64_t j = 0; j < K && keep; j++) {
+            uint64_t pb = 0, pf = 0;
+            for (size_t k = 0; k < nm; k++) { pb += off[k][j + 1] - off[k][j]; pf += idx[k][j + 1] - idx[k][j]; }
+            if (!pf) continue;
+            keep = merge_part_can_pack(pf, (int)nm);   // (else the radix sort, whose arena is grouped by Mission: to the host as ever)
+            need += (pf * (pack ? sizeof(sx_finding16) : sizeof(sx_finding)) + pb + 255) & ~(uint64_t)255;
+        }
+        if (keep) { const int rc = ensure_scratch(ctx, merge_findings_scratch_bytes(max_n, (int)nm, 1) + 512); if (rc != SX_OK) return rc; }
+        if (keep && ctx->d_result_cap < need) {
+            if (ctx->d_result) HIP_TRY(ctx, hipFree(ctx->d_result));   // (what it held went with the epoch)
+            ctx->d_result = nullptr; ctx->d_result_cap = 0;
+            if (hipMalloc((void**)&ctx->d_result, need) != hipSuccess) { (void)hipGetLastError(); ctx->d_result = nullptr; keep = false; }   // no room: the host result
+            else ctx->d_result_cap = need;
+        }
+        if (!keep && !host_way_ok()) return give_up();
+    }
+    uint64_t result_at = 0;
     const size_t out_room = (max_out + 511) & ~(size_t)255;
     const size_t n_out = (K > 1 || ctx->merge_async) ? 2 : 1;
     const size_t tmp_need = merge_findings_scratch_bytes(max_n, (int)nm) + 512;
     { int rc = ensure_copy_stream(ctx); if (rc != SX_OK) return rc; }
-    if (ctx->merge_out_room < out_room || ctx->merge_n_out < n_out || ctx->d_merge_cap < ctx->merge_n_out * ctx->merge_out_room + tmp_need) {
+    if (!keep && (ctx->merge_out_room < out_room || ctx->merge_n_out < n_out || ctx->d_merge_cap < ctx->merge_n_out * ctx->merge_out_room + tmp_need)) {
         // (the copy of an earlier call's last part may still read the buffers that are about to go)
         int rc = merge_drain(ctx);
         if (rc != SX_OK) return rc;
@@ -631,6 +711,18 @@ static int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFi
             pf += pnf[k]; pb += pnb[k];
         }
         if (!pf) continue;
+        if (keep) {
+            const bool pack_part = pack;   // (merge_part_can_pack: checked above)
+            uint8_t* d_part = ctx->d_result + result_at;
+            HIP_TRY(ctx, merge_findings_device_part(fp.data(), ap.data(), pnf.data(), pnb.data(), off0.data(), (int)nm, d_part, ctx->d_scratch, ctx->d_scratch_cap, s, pack_part ? 1 : 0, 1));
+            result_at += (pf * (pack_part ? sizeof(sx_finding16) : sizeof(sx_finding)) + pb + 255) & ~(uint64_t)255;
+            outs.emplace_back();
+            MissionFindings& o = outs.back();
+            o.dev_only = true; o.keep_on_device = true; o.dev_epoch_ref = ctx->dev_epoch; o.dev_epoch = ctx->dev_epoch->load();
+            o.ext_nf = pf; o.ext_na = pb; o.dev_copy = d_part;
+            if (pack_part) { o.packed = true; o.info = seg_info; }
+            continue;
+        }
         const unsigned ob = ctx->merge_n_out == 2 ? (unsigned)(ctx->merge_parts & 1) : 0u;   // (parts of all calls in turn: merge_async)
         ctx->merge_parts++;
         uint8_t* d_out = ctx->d_merge + ob * ctx->merge_out_room;
@@ -659,6 +751,7 @@ static int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFi
         outs.back().ext = blk; outs.back().ext_nf = pf; outs.back().ext_na = pb;
         if (pack_part) { outs.back().packed = true; outs.back().info = seg_info; }
     }
+    if (keep) HIP_TRY(ctx, hipStreamSynchronize(s));   // (the pointers may be read from any stream once the call returns)
     if (ctx->merge_async) {   // a Mission whose stage B writes on a stream of its own waits for this before it overwrites its findings
         if (!ctx->ev_interleaved) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_interleaved, hipEventDisableTiming));
         HIP_TRY(ctx, hipEventRecord(ctx->ev_interleaved, s));

@@ -68,7 +68,7 @@ struct Switches {
     int64_t seq_piece_mib = -1;        // SX_SEQ_PIECE_MIB=n: the same in MiB; -1 unset: sized from the last buffer's output (tests)
     bool debug_entry = false;          // SX_DEBUG_ENTRY presence: prints a double-byte Mission's entry state per buffer (experiments)
     int busiest_last = 0;              // SX_BUSIEST_LAST=1 / 2: the busiest Mission's scan is queued last / second to last (tests)
-    uint64_t defer_min_bytes = 256ull << 20;   // SX_DEFER_MIN_BYTES=n: with several Missions, an output from n bytes on stays on the device for the merge.  Two
+    uint64_t defer_min_bytes = 256ull << 20;   // SX_DEFER_MIN_BYTES=n: with several Missions, an output from n bytes on stays on the device for the merge (every output does when the merged result is to stay in HBM: SX_OPT_RESULT_ON_DEVICE).  Two
                                        // sites, one meaning: "nm >= 2 ? n : 0" (tests)
     bool wave_threads = true;          // SX_WAVE_THREADS on / off: unscanned string-dense Missions replay on a host thread and stream each (tests)
     int timeline = 0;                  // SX_TIMELINE=1: host-side marks on stderr, g_tl_on (measurements)

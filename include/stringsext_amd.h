@@ -194,7 +194,8 @@ enum {
                                      working there.  Valid until the NEXT buffer is scanned on the context — every chunk of sx_scan_stream / sx_scan_file is one; a
                                      call that accumulates its chunks into one result keeps them in host memory — or the context is destroyed (the memory
                                      is the context's).  The
-                                     host accessors (sx_result_segment, ..._packed, sx_print_findings, ...) still work: the first one copies the
+                                     host accessors (sx_result_segment, ..._packed, sx_print_findings, ...) still work (sx_print_findings_device formats the
+                                     findings where they lie, without moving them): the first one copies the
                                      segment to the host (SX_E_STATE if a later scan has overwritten it).  Every other result is in host memory
                                      as without the flag; the sharded entry points ignore it.
                                      A context with SEVERAL Missions, scanned with sx_scan / sx_scan_device (one buffer, one piece): the merged findings
@@ -454,6 +455,20 @@ void              sx_result_free(sx_result* r);
 #define SX_OUTPUT_BOM "\xEF\xBB\xBF"
 int sx_print_findings(const sx_ctx* ctx, const sx_result* r, int n_inputs, int radix,
                       int no_metadata, uint8_t** out, uint64_t* out_len);
+/* Finding::print for every finding of a result whose segments ALL lie in HBM (SX_OPT_RESULT_ON_DEVICE), written by the device
+ * (csrc/sx_print_dev.hip): *d_text = *text_len bytes in HBM, byte for byte what sx_print_findings(ctx, r, n_inputs, radix, no_metadata, ...)
+ * returns — same framing contract: no BOM, no final "\n"; the caller adds them.  text_len has 64 bits and so have all offsets behind
+ * it: a result's text may exceed 4 GiB.  The text block is the context's memory (grown on demand, reused): valid until the next
+ * sx_print_findings_device or sx_scan* call on the context or sx_destroy — the epoch rule of the result block.  The call returns
+ * when the kernels that write the text are done: the pointer may be read from any stream at once.  The result is NOT moved: every
+ * segment is still on the device afterwards (sx_result_segment_device returns the same pointers) and the host accessors work as
+ * before.  SX_E_STATE — and *d_text = NULL, *text_len = 0 — if any segment of the result is in host memory (every case of
+ * SX_OPT_RESULT_ON_DEVICE's "the result is in host memory" list, a result without findings among them; a segment a host accessor
+ * has already moved; a context without the flag; a host-only context) or a later scan has reused the memory: the caller then
+ * uses sx_print_findings.  SX_E_INVALID for a radix other than 0 / 'x' / 'd' / 'o'; SX_E_NOMEM if the text block cannot be
+ * allocated (the result stays usable). */
+int sx_print_findings_device(sx_ctx* ctx, const sx_result* r, int n_inputs, int radix, int no_metadata,
+                             const uint8_t** d_text, uint64_t* text_len);
 
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);

@@ -34,7 +34,7 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_scan_stream", "sx_scan_file", "sx_missions_from_flags", "sx_parse_enc_opt", "sx_encoding_for_label", "sx_encoding_name",
            "sx_decoder_table", "sx_wave_classes", "sx_scan_classifier", "sx_result_segment_packed", "sx_wave_swar", "sx_wave_pair_codes2", "sx_wave_pair_codes", "sx_shard_bounds", "sx_scan_sharded", "sx_shard_splice", "sx_shard_splice_segs", "sx_transport_rccl_id", "sx_transport_rccl_create", "sx_transport_destroy", "sx_transport_last_error", "sx_transport_allgather", "sx_transport_gather",
            "sx_result_count", "sx_result_segments", "sx_result_segment", "sx_result_segment_device", "sx_result_findings", "sx_result_arena",
-           "sx_result_free", "sx_print_findings", "sx_get_stats", "sx_free", "sx_fill_background_device",
+           "sx_result_free", "sx_print_findings", "sx_print_findings_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
 
@@ -230,6 +230,7 @@ def lib():
                                     C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(u64)]
     L.sx_print_findings.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_uint8)),
                                     C.POINTER(u64)]
+    L.sx_print_findings_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(u64)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -341,6 +342,18 @@ class Result:
         lib().sx_free(out)
         return b
 
+    def printed_device(self, n_inputs=1, radix=None, no_metadata=False):
+        """(device pointer, length): the same text as printed(), written by the device into the Scanner's text block in HBM
+        (sx_print_findings_device) — for a result whose segments all lie there (result_on_device=True); the result is not moved.
+        Valid until the next printed_device() or scan on the Scanner.  Raises SxError (SX_E_STATE) if any segment is in host
+        memory, a later scan has reused the memory or the Scanner is closed: use printed() then."""
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        p, n = C.c_void_p(), C.c_uint64()
+        self._s._chk(lib().sx_print_findings_device(self._s.h, self.h, n_inputs, ord(radix) if radix else 0, int(no_metadata),
+                                                    C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def free(self):
         if self.h:
             lib().sx_result_free(self.h)
@@ -356,7 +369,8 @@ class Result:
 class Scanner:
     """One sx_ctx: N missions bound to one HIP device (device=SX_HOST_ONLY: replay stage only).
     result_on_device=True (SX_OPT_RESULT_ON_DEVICE): the result of scan() / scan_device() stays in HBM — Result.device_segments(),
-    Scanner.download() —, with one Mission or several; valid until the next buffer is scanned on this Scanner."""
+    Scanner.download() —, with one Mission or several; valid until the next buffer is scanned on this Scanner.
+    Result.printed_device() formats such a result on the device: the reference's text as one block in HBM."""
 
     def __init__(self, mission_dicts, device=0, subchunk_bytes=0, record_capacity=0, generic_kernels=False,
                  replay_threads=0, device_replay=None, result_on_device=False, fused_scan=True):

@@ -1,6 +1,7 @@
 // sx_api.cpp — the C-ABI of include/stringsext_amd.h: context and HIP resources, the lower-level
 // stages as entry points, results, utilities.  (sx_scan* live in sx_ingest.cpp.)
 #include "sx_ctx.hpp"
+#include "sx_print_core.hpp"
 
 using namespace sx;
 
@@ -388,6 +389,9 @@ void sx_destroy(sx_ctx* ctx) {
         if (ctx->d_merge) (void)hipFree(ctx->d_merge);
         if (ctx->d_result) (void)hipFree(ctx->d_result);
         if (ctx->d_result_up) (void)hipFree(ctx->d_result_up);
+        if (ctx->d_text) (void)hipFree(ctx->d_text);
+        if (ctx->d_print_scratch) (void)hipFree(ctx->d_print_scratch);
+        if (ctx->d_print_missions) (void)hipFree(ctx->d_print_missions);
         for (hipEvent_t e : ctx->merge_ev) if (e) (void)hipEventDestroy(e);
         if (ctx->ev_interleaved) (void)hipEventDestroy(ctx->ev_interleaved);
         if (ctx->d_input) (void)hipFree(ctx->d_input);
@@ -603,6 +607,96 @@ int sx_print_findings(const sx_ctx* ctx, const sx_result* r, int n_inputs, int r
     if (!*out) return SX_E_NOMEM;
     memcpy(*out, s.data(), s.size());
     *out_len = s.size();
+    return SX_OK;
+}
+
+// Finding::print where the findings lie (sx_print_dev.hip): pass 1 of every segment, one wait for the segments' text bytes, the text
+// block, pass 2 of every segment at its 64-bit base, one more wait.  The result is read, never moved.
+int sx_print_findings_device(sx_ctx* ctx, const sx_result* r, int n_inputs, int radix, int no_metadata, const uint8_t** d_text,
+                             uint64_t* text_len) {
+    if (d_text) *d_text = nullptr;
+    if (text_len) *text_len = 0;
+    if (!ctx || !r || !d_text || !text_len) return SX_E_INVALID;
+    if (radix != 0 && radix != 'x' && radix != 'd' && radix != 'o') { ctx->set_err("radix must be 0, 'x', 'd' or 'o'"); return SX_E_INVALID; }
+    if (ctx->host_only) { ctx->set_err("host-only context: no device print"); return SX_E_STATE; }
+    if (r->r.segs.empty()) { ctx->set_err("the result is in host memory: sx_print_findings"); return SX_E_STATE; }
+    for (const MissionFindings& s : r->r.segs) {
+        if (!s.dev_only || !s.keep_on_device || s.ext_nf == 0) { ctx->set_err("the result is in host memory: sx_print_findings"); return SX_E_STATE; }
+        if (s.dev_epoch_ref != ctx->dev_epoch || ctx->dev_epoch->load() != s.dev_epoch) {
+            ctx->set_err("a later scan has reused the result's device memory");
+            return SX_E_STATE;
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    if (!ctx->d_print_missions) {
+        std::vector<PrintMission> tab(256);
+        memset(tab.data(), 0, tab.size() * sizeof(PrintMission));
+        for (size_t k = ctx->missions.size(); k-- > 0;) {   // (print_findings takes the first Mission of an id)
+            const Mission& m = ctx->missions[k];
+            const char* name = m.c.print_encoding_as_ascii ? "ascii" : m.encoding_name();
+            const std::string label = name ? name : "";
+            PrintMission& t = tab[m.c.mission_id];
+            if (label.size() > sizeof t.label) { ctx->set_err("encoding label longer than 14 bytes"); return SX_E_STATE; }
+            t.present = 1; t.len = (uint8_t)label.size();
+            memcpy(t.label, label.data(), label.size());
+        }
+        uint8_t* p = nullptr;
+        if (hipMalloc((void**)&p, tab.size() * sizeof(PrintMission)) != hipSuccess) { (void)hipGetLastError(); ctx->set_err("device print: no memory for the Mission table"); return SX_E_NOMEM; }
+        const hipError_t e = hipMemcpy(p, tab.data(), tab.size() * sizeof(PrintMission), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(p); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
+        ctx->d_print_missions = p;
+    }
+    const size_t ns = r->r.segs.size();
+    uint64_t scratch = 0;
+    for (const MissionFindings& s : r->r.segs) scratch += print_scratch_bytes(s.ext_nf);
+    if (scratch > ctx->d_print_scratch_cap) {
+        if (ctx->d_print_scratch) (void)hipFree(ctx->d_print_scratch);
+        ctx->d_print_scratch = nullptr; ctx->d_print_scratch_cap = 0;
+        if (hipMalloc((void**)&ctx->d_print_scratch, scratch) != hipSuccess) { (void)hipGetLastError(); ctx->d_print_scratch = nullptr; ctx->set_err("device print: no memory for the offsets"); return SX_E_NOMEM; }
+        ctx->d_print_scratch_cap = scratch;
+    }
+    std::vector<PrintParams> P(ns);
+    std::vector<const uint64_t*> d_total(ns);
+    uint64_t at = 0;
+    for (size_t i = 0; i < ns; i++) {
+        const MissionFindings& s = r->r.segs[i];
+        PrintParams& p = P[i];
+        memset(&p, 0, sizeof p);
+        p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
+        p.file_id = s.packed && s.info ? s.info->file_id : -1;
+        p.several_inputs = n_inputs > 1; p.radix = (uint32_t)radix; p.no_metadata = no_metadata != 0; p.several_missions = ctx->missions.size() > 1;
+        p.missions = (const PrintMission*)ctx->d_print_missions;
+        const size_t bytes = print_scratch_bytes(s.ext_nf);
+        HIP_TRY(ctx, print_measure(p, ctx->d_print_scratch + at, bytes, st, &p.wbase, &d_total[i]));
+        at += bytes;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    uint64_t total = 0;
+    for (size_t i = 0; i < ns; i++) {
+        uint64_t t = 0;
+        HIP_TRY(ctx, hipMemcpy(&t, d_total[i], sizeof t, hipMemcpyDeviceToHost));
+        P[i].base = total;
+        total += t;
+    }
+    if (total > ctx->d_text_cap) {
+        if (ctx->d_text) (void)hipFree(ctx->d_text);
+        ctx->d_text = nullptr; ctx->d_text_cap = 0;
+        if (hipMalloc((void**)&ctx->d_text, total) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->d_text = nullptr;
+            ctx->set_err("device print: no memory for " + std::to_string(total) + " bytes of text");
+            return SX_E_NOMEM;
+        }
+        ctx->d_text_cap = total;
+    }
+    for (size_t i = 0; i < ns; i++) {
+        P[i].text = ctx->d_text;
+        HIP_TRY(ctx, print_write(P[i], st));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    *d_text = ctx->d_text;
+    *text_len = total;
     return SX_OK;
 }
 

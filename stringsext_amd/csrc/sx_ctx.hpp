@@ -165,6 +165,11 @@ struct sx_ctx {
     // aligned, stay here for the caller — valid while the epoch stands) and where Missions' lists that exist on the host only are uploaded
     uint8_t* d_result = nullptr; uint64_t d_result_cap = 0;
     uint8_t* d_result_up = nullptr; uint64_t d_result_up_cap = 0;
+    // sx_print_findings_device: the text block (grown on demand, reused: the caller's until the next print or scan call), the two
+    // passes' scratch and the Mission table (by mission_id; uploaded by the first call)
+    uint8_t* d_text = nullptr; uint64_t d_text_cap = 0;
+    uint8_t* d_print_scratch = nullptr; uint64_t d_print_scratch_cap = 0;
+    uint8_t* d_print_missions = nullptr;
     bool merge_async = false;                           // device_merge returns with its last copies in flight; merge_drain() waits
     bool merge_copy_pending[2] = { false, false };      // a copy out of output buffer 0 / 1 was queued and not waited for
     uint64_t merge_parts = 0;                           // parts merged so far (their parity picks the output buffer)

@@ -265,6 +265,13 @@ size_t merge_findings_scratch_bytes(uint64_t n_findings, int n_missions, int ord
 size_t order_strings_scratch_bytes(uint64_t n);
 hipError_t order_part_strings(void* recs, uint64_t n, int packed, const uint64_t* src, uint8_t* arena, void* scratch, size_t scratch_bytes,
                               hipStream_t stream);
+// Finding::print on the device (sx_print_dev.hip, PrintParams: sx_print_core.hpp), a segment at a time.  print_measure: pass 1 —
+// *wbase = the wavefronts' offsets into the segment's text, *total = the device word with its text bytes, both inside `scratch`
+// (print_scratch_bytes(n), 256-aligned) and valid once `stream` has got there; print_write: the lines to P.text + P.base
+struct PrintParams;
+size_t print_scratch_bytes(uint64_t n);
+hipError_t print_measure(const PrintParams& P, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint64_t** wbase, const uint64_t** total);
+hipError_t print_write(const PrintParams& P, hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
 hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit

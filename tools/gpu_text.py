@@ -54,5 +54,15 @@ for flags, data in cases:
         res = sc.scan_device(d, len(data), file_id=1)
         dts.append(time.perf_counter() - t0); n = len(res); res.free()
     dt = sorted(dts[2:])[len(dts[2:]) // 2]
-    print(flags["encodings"], "-r" if flags.get("same_unicode_block") else "", f"-g {flags['grep_char']}" if flags.get("grep_char") else "", f"{mib} MiB {what}: {dt*1e3:.1f} ms = {mib/1024/dt:.2f} GiB/s (median of 6; min {min(dts)*1e3:.1f}, max {max(dts[2:])*1e3:.1f} ms), {n} findings, wave windows {sc.stats().wave_windows}")
+    dev_print = ""
+    if os.environ.get("RESULT_ON_DEVICE"):   # ... and the reference's text written where they lie (sx_print_findings_device; the second call: the text block has its size)
+        sc.reset(); res = sc.scan_device(d, len(data), file_id=1)
+        try:
+            for _ in range(2):
+                t0 = time.perf_counter(); _, tn = res.printed_device(n_inputs=1, radix="x"); tp = time.perf_counter() - t0
+            dev_print = f", device print {tp*1e3:.2f} ms for {tn} text bytes"
+        except sx.SxError:
+            dev_print = ", device print: the result is in host memory"
+        res.free()
+    print(flags["encodings"], "-r" if flags.get("same_unicode_block") else "", f"-g {flags['grep_char']}" if flags.get("grep_char") else "", f"{mib} MiB {what}: {dt*1e3:.1f} ms = {mib/1024/dt:.2f} GiB/s (median of 6; min {min(dts)*1e3:.1f}, max {max(dts[2:])*1e3:.1f} ms), {n} findings, wave windows {sc.stats().wave_windows}{dev_print}")
     sc.free(d); sc.close()

@@ -470,6 +470,37 @@ int sx_print_findings(const sx_ctx* ctx, const sx_result* r, int n_inputs, int r
 int sx_print_findings_device(sx_ctx* ctx, const sx_result* r, int n_inputs, int radix, int no_metadata,
                              const uint8_t** d_text, uint64_t* text_len);
 
+/* The findings of a result whose segments ALL lie in HBM (SX_OPT_RESULT_ON_DEVICE), selected by substring where they lie
+ * (csrc/sx_select_dev.hip) — what `grep -F -f patterns` keeps of the printed lines when only the string part of a line is looked at.
+ * Finding i MATCHES if some pattern p equals s[o, o + len_p) for some 0 <= o <= str_len - len_p: bytes compared as bytes (the
+ * strings are UTF-8, a pattern is raw bytes), or after the ASCII fold with SX_SELECT_ASCII_NOCASE.  A match never spans two findings; a
+ * finding shorter than the pattern does not match.  Finding i is selected iff (matches) XOR (SX_SELECT_INVERT).
+ * *out is a new result (sx_result_free) whose segments all lie in HBM: every source segment with at least one selected finding gives
+ * one segment, source order and record order kept; the record type (sx_finding16 / sx_finding) and the sx_segment_info are the
+ * source segment's and every record is unchanged except str_off.  A segment is [records][strings], 256-byte aligned, its strings back
+ * to back in record order — the layout of the merged segments: str_off[0] == 0, str_off[i + 1] == str_off[i] + str_len[i],
+ * arena_len == sum(str_len).  Nothing selected: *out is an empty result (sx_result_count 0, no segments: "no findings -> host memory").
+ * The source may be any result sx_print_findings_device accepts (both record types, any layout of the strings: they are addressed
+ * by str_off), the result of an earlier selection among them: selecting from a selection is AND (grep a | grep b).  The source is
+ * read, never moved: its device pointers are the same afterwards and its host accessors work as before.
+ * Memory: two selection blocks of the context, grown on demand and used in turn: a selected result is valid until the SECOND
+ * sx_result_select_device call after the one that made it (a call that returns SX_E_INVALID or SX_E_STATE writes nothing and does not count), or
+ * sx_destroy.  A scan call does not invalidate it — the blocks are not the result block: a host can work on the selection of buffer
+ * N while buffer N + 1 is scanned.  Afterwards the accessors answer SX_E_STATE, as for any result on the device.  The call returns
+ * when the kernels that write the block are done.  sx_print_findings_device, sx_result_segment_device and the host accessors take a
+ * selected result as they take a scan's.
+ * SX_E_INVALID: n_patterns outside 1..SX_SELECT_MAX_PATTERNS, a len outside 1..SX_SELECT_MAX_PATTERN_BYTES, a NULL pointer, unknown
+ * flag bits.  SX_E_STATE — and *out = NULL — wherever sx_print_findings_device would refuse the source (a segment in host memory, a
+ * result without findings, a later scan or selection that reused the memory, a context without the flag, a host-only context): the
+ * caller then filters on the host.  SX_E_NOMEM: the block cannot be allocated (the source stays usable). */
+#define SX_SELECT_MAX_PATTERNS 16
+#define SX_SELECT_MAX_PATTERN_BYTES 64
+enum { SX_SELECT_ASCII_NOCASE = 1u,   /* bytes 'A'..'Z' of strings and patterns compare as 'a'..'z'; no other byte is folded */
+       SX_SELECT_INVERT = 2u };       /* keep the findings that match NO pattern (grep -v) */
+typedef struct sx_pattern { const uint8_t* bytes; uint32_t len; } sx_pattern;   /* raw bytes; the strings are UTF-8 */
+int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns,
+                            uint32_t flags, sx_result** out);
+
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);
 

@@ -17,6 +17,8 @@ SX_OK, SX_E_INVALID, SX_E_NO_DEVICE, SX_E_HIP, SX_E_NOMEM, SX_E_STATE, SX_E_HALO
 SX_HOST_ONLY = -1
 SX_OPT_GENERIC_KERNELS, SX_OPT_DEVICE_REPLAY, SX_OPT_HOST_REPLAY = 1, 2, 4
 SX_OPT_NO_FUSED_SCAN = 64      # round 6: one scan launch per Mission instead of the fused one (one read of the buffer for several Missions)
+SX_SELECT_MAX_PATTERNS, SX_SELECT_MAX_PATTERN_BYTES = 16, 64   # sx_result_select_device (Result.select_device)
+SX_SELECT_ASCII_NOCASE, SX_SELECT_INVERT = 1, 2
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -34,7 +36,7 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_scan_stream", "sx_scan_file", "sx_missions_from_flags", "sx_parse_enc_opt", "sx_encoding_for_label", "sx_encoding_name",
            "sx_decoder_table", "sx_wave_classes", "sx_scan_classifier", "sx_result_segment_packed", "sx_wave_swar", "sx_wave_pair_codes2", "sx_wave_pair_codes", "sx_shard_bounds", "sx_scan_sharded", "sx_shard_splice", "sx_shard_splice_segs", "sx_transport_rccl_id", "sx_transport_rccl_create", "sx_transport_destroy", "sx_transport_last_error", "sx_transport_allgather", "sx_transport_gather",
            "sx_result_count", "sx_result_segments", "sx_result_segment", "sx_result_segment_device", "sx_result_findings", "sx_result_arena",
-           "sx_result_free", "sx_print_findings", "sx_print_findings_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
+           "sx_result_free", "sx_print_findings", "sx_print_findings_device", "sx_result_select_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
 
@@ -159,6 +161,10 @@ class SegmentInfo(C.Structure):   # sx_segment_info
                 ("position0", C.c_uint64 * 256)]
 
 
+class Pattern(C.Structure):   # sx_pattern
+    _fields_ = [("bytes", C.c_char_p), ("len", C.c_uint32)]
+
+
 class Run(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("chars", C.c_uint64)]
 
@@ -231,6 +237,7 @@ def lib():
     L.sx_print_findings.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_uint8)),
                                     C.POINTER(u64)]
     L.sx_print_findings_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(u64)]
+    L.sx_result_select_device.argtypes = [vp, vp, C.POINTER(Pattern), C.c_int, C.c_uint32, C.POINTER(vp)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -354,6 +361,24 @@ class Result:
                                                     C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def select_device(self, patterns, ignore_case=False, invert=False):
+        """The findings whose string holds one of `patterns` (bytes, or a list of 1..16 bytes objects of 1..64 bytes each) as a
+        substring — `grep -F` over the strings —, selected on the device (sx_result_select_device) out of a result whose segments
+        all lie in HBM (result_on_device=True): a new Result on the device, record order kept, strings back to back, which
+        device_segments(), printed_device(), select_device() (AND) and the host accessors take like a scan's.  ignore_case: 'A'..'Z'
+        compare as 'a'..'z' (no other byte is folded); invert: the findings that hold NO pattern.  This Result is not moved.  The
+        selection is valid until the second select_device() on the Scanner after this one (a scan does not invalidate it) or
+        close().  Raises SxError: SX_E_INVALID for bad patterns, SX_E_STATE wherever printed_device() would refuse this Result."""
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        pats = [patterns] if isinstance(patterns, (bytes, bytearray, memoryview)) else list(patterns)
+        pats = [bytes(p) for p in pats]
+        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        flags = (SX_SELECT_ASCII_NOCASE if ignore_case else 0) | (SX_SELECT_INVERT if invert else 0)
+        out = C.c_void_p()
+        self._s._chk(lib().sx_result_select_device(self._s.h, self.h, arr, len(pats), flags, C.byref(out)))
+        return Result(self._s, out)
+
     def free(self):
         if self.h:
             lib().sx_result_free(self.h)
@@ -370,7 +395,8 @@ class Scanner:
     """One sx_ctx: N missions bound to one HIP device (device=SX_HOST_ONLY: replay stage only).
     result_on_device=True (SX_OPT_RESULT_ON_DEVICE): the result of scan() / scan_device() stays in HBM — Result.device_segments(),
     Scanner.download() —, with one Mission or several; valid until the next buffer is scanned on this Scanner.
-    Result.printed_device() formats such a result on the device: the reference's text as one block in HBM."""
+    Result.printed_device() formats such a result on the device: the reference's text as one block in HBM;
+    Result.select_device() selects its findings by substring there (grep -F): a new Result in HBM."""
 
     def __init__(self, mission_dicts, device=0, subchunk_bytes=0, record_capacity=0, generic_kernels=False,
                  replay_threads=0, device_replay=None, result_on_device=False, fused_scan=True):

@@ -2,6 +2,7 @@
 // stages as entry points, results, utilities.  (sx_scan* live in sx_ingest.cpp.)
 #include "sx_ctx.hpp"
 #include "sx_print_core.hpp"
+#include "sx_select_core.hpp"
 
 using namespace sx;
 
@@ -347,6 +348,7 @@ void sx_destroy(sx_ctx* ctx) {
     // results may outlive the context (they share the pinned pool and the epoch word): what they left in HBM is freed below, so the
     // accessors must answer SX_E_STATE from here on
     ctx->dev_epoch->fetch_add(1);
+    for (auto& e : ctx->select_epoch) e->fetch_add(1);
     if (!ctx->host_only && ctx->device >= 0) {
         (void)hipSetDevice(ctx->device);
         for (auto& d : ctx->dev) {
@@ -392,6 +394,9 @@ void sx_destroy(sx_ctx* ctx) {
         if (ctx->d_text) (void)hipFree(ctx->d_text);
         if (ctx->d_print_scratch) (void)hipFree(ctx->d_print_scratch);
         if (ctx->d_print_missions) (void)hipFree(ctx->d_print_missions);
+        for (uint8_t* p : ctx->d_select) if (p) (void)hipFree(p);
+        if (ctx->d_select_scratch) (void)hipFree(ctx->d_select_scratch);
+        if (ctx->d_select_scratch2) (void)hipFree(ctx->d_select_scratch2);
         for (hipEvent_t e : ctx->merge_ev) if (e) (void)hipEventDestroy(e);
         if (ctx->ev_interleaved) (void)hipEventDestroy(ctx->ev_interleaved);
         if (ctx->d_input) (void)hipFree(ctx->d_input);
@@ -610,6 +615,22 @@ int sx_print_findings(const sx_ctx* ctx, const sx_result* r, int n_inputs, int r
     return SX_OK;
 }
 
+// What sx_print_findings_device and sx_result_select_device ask of a result: every segment in HBM, in memory of this context — the result
+// block of the last scan call or one of the two selection blocks — that has not been written again since.
+static int result_on_device(sx_ctx* ctx, const sx_result* r, const char* host_call) {
+    const std::string in_host = std::string("the result is in host memory: ") + host_call;
+    if (r->r.segs.empty()) { ctx->set_err(in_host); return SX_E_STATE; }
+    for (const MissionFindings& s : r->r.segs) {
+        if (!s.dev_only || !s.keep_on_device || s.ext_nf == 0) { ctx->set_err(in_host); return SX_E_STATE; }
+        const bool ours = s.dev_epoch_ref && (s.dev_epoch_ref == ctx->dev_epoch || s.dev_epoch_ref == ctx->select_epoch[0] || s.dev_epoch_ref == ctx->select_epoch[1]);
+        if (!ours || s.dev_epoch_ref->load() != s.dev_epoch) {
+            ctx->set_err("a later scan or selection has reused the result's device memory");
+            return SX_E_STATE;
+        }
+    }
+    return SX_OK;
+}
+
 // Finding::print where the findings lie (sx_print_dev.hip): pass 1 of every segment, one wait for the segments' text bytes, the text
 // block, pass 2 of every segment at its 64-bit base, one more wait.  The result is read, never moved.
 int sx_print_findings_device(sx_ctx* ctx, const sx_result* r, int n_inputs, int radix, int no_metadata, const uint8_t** d_text,
@@ -619,14 +640,7 @@ int sx_print_findings_device(sx_ctx* ctx, const sx_result* r, int n_inputs, int 
     if (!ctx || !r || !d_text || !text_len) return SX_E_INVALID;
     if (radix != 0 && radix != 'x' && radix != 'd' && radix != 'o') { ctx->set_err("radix must be 0, 'x', 'd' or 'o'"); return SX_E_INVALID; }
     if (ctx->host_only) { ctx->set_err("host-only context: no device print"); return SX_E_STATE; }
-    if (r->r.segs.empty()) { ctx->set_err("the result is in host memory: sx_print_findings"); return SX_E_STATE; }
-    for (const MissionFindings& s : r->r.segs) {
-        if (!s.dev_only || !s.keep_on_device || s.ext_nf == 0) { ctx->set_err("the result is in host memory: sx_print_findings"); return SX_E_STATE; }
-        if (s.dev_epoch_ref != ctx->dev_epoch || ctx->dev_epoch->load() != s.dev_epoch) {
-            ctx->set_err("a later scan has reused the result's device memory");
-            return SX_E_STATE;
-        }
-    }
+    { const int rc = result_on_device(ctx, r, "sx_print_findings"); if (rc != SX_OK) return rc; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->post_stream;
     if (!ctx->d_print_missions) {
@@ -697,6 +711,94 @@ int sx_print_findings_device(sx_ctx* ctx, const sx_result* r, int n_inputs, int 
     HIP_TRY(ctx, hipStreamSynchronize(st));
     *d_text = ctx->d_text;
     *text_len = total;
+    return SX_OK;
+}
+
+// (a grow-only device buffer of the selection: SX_E_NOMEM leaves it empty)
+static int grow_device(sx_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t bytes, const char* what) {
+    if (bytes <= *cap) return SX_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    if (hipMalloc((void**)p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        ctx->set_err(std::string("device select: no memory for ") + std::to_string(bytes) + " bytes of " + what);
+        return SX_E_NOMEM;
+    }
+    *cap = bytes;
+    return SX_OK;
+}
+
+// grep -F where the findings lie (sx_select_dev.hip): pass 1 of every segment, one wait for the segments' totals, the selection block,
+// pass 2 of every segment that has selected findings, one more wait.  The source is read, never moved.
+int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, uint32_t flags, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !patterns || !out) return SX_E_INVALID;
+    if (n_patterns < 1 || n_patterns > SX_SELECT_MAX_PATTERNS) { ctx->set_err("n_patterns must be 1..16"); return SX_E_INVALID; }
+    if (flags & ~(uint32_t)(SX_SELECT_ASCII_NOCASE | SX_SELECT_INVERT)) { ctx->set_err("unknown selection flags"); return SX_E_INVALID; }
+    for (int p = 0; p < n_patterns; p++)
+        if (!patterns[p].bytes || patterns[p].len < 1 || patterns[p].len > SX_SELECT_MAX_PATTERN_BYTES) { ctx->set_err("a pattern must have 1..64 bytes"); return SX_E_INVALID; }
+    if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
+    { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
+    // the block this call writes: a source that lies there was made two selections ago
+    const int slot = (int)(ctx->select_calls & 1u);
+    for (const MissionFindings& s : r->r.segs)
+        if (s.dev_epoch_ref == ctx->select_epoch[slot]) { ctx->set_err("this selection reuses the source's device memory: it was selected two calls ago"); return SX_E_STATE; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    const size_t ns = r->r.segs.size();
+    uint64_t scratch = 0;
+    for (const MissionFindings& s : r->r.segs) scratch += select_scratch_bytes(s.ext_nf);
+    { const int rc = grow_device(ctx, &ctx->d_select_scratch, &ctx->d_select_scratch_cap, scratch, "wavefront tables"); if (rc != SX_OK) return rc; }
+    std::vector<SelectParams> P(ns);
+    std::vector<const uint32_t*> d_count(ns);
+    std::vector<const uint64_t*> d_bytes(ns);
+    uint64_t at = 0;
+    for (size_t i = 0; i < ns; i++) {
+        const MissionFindings& s = r->r.segs[i];
+        SelectParams& p = P[i];
+        memset(&p, 0, sizeof p);
+        p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
+        select_fill_patterns(&p.pat, patterns, n_patterns, flags);
+        const size_t bytes = select_scratch_bytes(s.ext_nf);
+        HIP_TRY(ctx, select_measure(&p, ctx->d_select_scratch + at, bytes, st, &d_count[i], &d_bytes[i]));
+        at += bytes;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::vector<uint64_t> n_sel(ns), b_sel(ns), base(ns);
+    uint64_t block = 0, scratch2 = 0;
+    for (size_t i = 0; i < ns; i++) {
+        uint32_t c = 0;
+        HIP_TRY(ctx, hipMemcpy(&c, d_count[i], sizeof c, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(&b_sel[i], d_bytes[i], sizeof(uint64_t), hipMemcpyDeviceToHost));
+        n_sel[i] = c;
+        if (!c) continue;
+        base[i] = block;
+        block += (c * r->r.segs[i].rec_size() + b_sel[i] + 255) / 256 * 256;
+        scratch2 = std::max<uint64_t>(scratch2, select_place_scratch_bytes(c));
+    }
+    // from here on the call counts: the block of the selection before the last one is written again
+    ctx->select_epoch[slot]->fetch_add(1);
+    ctx->select_calls++;
+    ResultHolder res;
+    res.r->r.pool = ctx->pool;
+    if (block) {
+        { const int rc = grow_device(ctx, &ctx->d_select[slot], &ctx->d_select_cap[slot], block, "selected findings"); if (rc != SX_OK) return rc; }
+        { const int rc = grow_device(ctx, &ctx->d_select_scratch2, &ctx->d_select_scratch2_cap, scratch2, "string offsets"); if (rc != SX_OK) return rc; }
+        for (size_t i = 0; i < ns; i++) {
+            if (!n_sel[i]) continue;
+            const MissionFindings& s = r->r.segs[i];
+            uint8_t* recs = ctx->d_select[slot] + base[i];
+            HIP_TRY(ctx, select_place(P[i], recs, n_sel[i], recs + n_sel[i] * s.rec_size(), ctx->d_select_scratch2, select_place_scratch_bytes(n_sel[i]), st));
+            MissionFindings o;
+            o.ext_nf = n_sel[i]; o.ext_na = b_sel[i]; o.dev_copy = recs; o.dev_only = true; o.keep_on_device = true;
+            o.dev_epoch_ref = ctx->select_epoch[slot]; o.dev_epoch = ctx->select_epoch[slot]->load();
+            o.packed = s.packed; o.info = s.info;
+            res.r->r.segs.push_back(std::move(o));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    *out = res.release();
     return SX_OK;
 }
 

@@ -170,6 +170,14 @@ struct sx_ctx {
     uint8_t* d_text = nullptr; uint64_t d_text_cap = 0;
     uint8_t* d_print_scratch = nullptr; uint64_t d_print_scratch_cap = 0;
     uint8_t* d_print_missions = nullptr;
+    // sx_result_select_device: two selection blocks, used in turn (a selected result lives until the second call after the one that made
+    // it; scan calls leave them alone), each with an epoch word of its own of the kind dev_epoch is (advanced when the block is written
+    // again and by sx_destroy); pass 1's per-wavefront tables for all segments, and pass 2's string sources and scan, a segment at a time
+    uint8_t* d_select[2] = { nullptr, nullptr }; uint64_t d_select_cap[2] = { 0, 0 };
+    std::shared_ptr<std::atomic<uint64_t>> select_epoch[2] = { std::make_shared<std::atomic<uint64_t>>(0), std::make_shared<std::atomic<uint64_t>>(0) };
+    uint64_t select_calls = 0;
+    uint8_t* d_select_scratch = nullptr; uint64_t d_select_scratch_cap = 0;
+    uint8_t* d_select_scratch2 = nullptr; uint64_t d_select_scratch2_cap = 0;
     bool merge_async = false;                           // device_merge returns with its last copies in flight; merge_drain() waits
     bool merge_copy_pending[2] = { false, false };      // a copy out of output buffer 0 / 1 was queued and not waited for
     uint64_t merge_parts = 0;                           // parts merged so far (their parity picks the output buffer)

@@ -272,6 +272,15 @@ struct PrintParams;
 size_t print_scratch_bytes(uint64_t n);
 hipError_t print_measure(const PrintParams& P, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint64_t** wbase, const uint64_t** total);
 hipError_t print_write(const PrintParams& P, hipStream_t stream);
+// The substring selection on the device (sx_select_dev.hip, SelectParams: sx_select_core.hpp), a segment at a time.  select_measure:
+// pass 1 — fills P's per-wavefront tables inside `scratch` (select_scratch_bytes(n), 256-aligned); *count, *bytes = the device words with
+// the selected records' number and string bytes, valid once `stream` has got there; select_place: the selected records to out_recs, their
+// strings back to back to out_arena (scratch: select_place_scratch_bytes(n_sel), 256-aligned; order_part_strings inside)
+struct SelectParams;
+size_t select_scratch_bytes(uint64_t n);
+hipError_t select_measure(SelectParams* P, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes);
+size_t select_place_scratch_bytes(uint64_t n_sel);
+hipError_t select_place(const SelectParams& P, void* out_recs, uint64_t n_sel, uint8_t* out_arena, void* scratch, size_t scratch_bytes, hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
 hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit

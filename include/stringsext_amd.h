@@ -501,6 +501,37 @@ typedef struct sx_pattern { const uint8_t* bytes; uint32_t len; } sx_pattern;   
 int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns,
                             uint32_t flags, sx_result** out);
 
+/* The same selection by a keyword LIST — `grep -F -f keywords.txt` with hundreds to tens of thousands of entries —, compiled once
+ * and used on buffer after buffer.  sx_select_set_create builds, on the host, the Aho-Corasick automaton of the patterns as a full
+ * table (csrc/sx_selset_build.hpp: byte classes, states numbered breadth first, every state that ends a pattern collapsed into one
+ * "matched" state) and puts it into HBM on the context's device; the cost of a string byte is then one table look-up, however many
+ * patterns there are and whatever bytes they begin with.  flags: 0 or SX_SELECT_ASCII_NOCASE — the fold is compiled into the set.
+ * Duplicate patterns are allowed.  The set owns its device memory and does not depend on the context's lifetime: it may be freed
+ * before or after sx_destroy, and used with any context on the same HIP device (another device: SX_E_INVALID).
+ * SX_E_INVALID: n_patterns outside 1..SX_SELECT_SET_MAX_PATTERNS, a len outside 1..SX_SELECT_SET_MAX_PATTERN_BYTES, lengths that sum
+ * to more than SX_SELECT_SET_MAX_TOTAL_BYTES, a NULL pointer, any other flag bit.  SX_E_STATE: a host-only context.  SX_E_NOMEM: the
+ * table cannot be allocated.  *out = NULL on every error.
+ * sx_select_set_info_get: what was built — table_bytes lie in HBM, the rows of the first lds_states states are what the kernel
+ * (csrc/sx_selset_dev.hip) keeps in LDS, the other rows it reads through L2.
+ * sx_result_select_set_device: flags 0 or SX_SELECT_INVERT; in everything else the contract of sx_result_select_device, word for
+ * word — the match rule, the output layout, the empty result, the source that is read and never moved, the sources accepted (a
+ * result of either kind of selection among them: AND), the errors.  It writes the same two selection blocks: calls of both kinds
+ * count together for "valid until the SECOND selection after the one that made it". */
+#define SX_SELECT_SET_MAX_PATTERNS      65536u
+#define SX_SELECT_SET_MAX_PATTERN_BYTES 255u
+#define SX_SELECT_SET_MAX_TOTAL_BYTES   (1u << 20)     /* sum of the patterns' lengths */
+typedef struct sx_select_set sx_select_set;
+typedef struct sx_select_set_info {
+    uint32_t n_patterns, states, classes, nocase;
+    uint64_t table_bytes;     /* in HBM */
+    uint32_t lds_states;      /* states whose rows the kernel keeps in LDS */
+    uint32_t reserved;
+} sx_select_set_info;
+int  sx_select_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_set** out);
+int  sx_select_set_info_get(const sx_select_set* set, sx_select_set_info* out);
+void sx_select_set_free(sx_select_set* set);
+int  sx_result_select_set_device(sx_ctx* ctx, const sx_result* r, const sx_select_set* set, uint32_t flags, sx_result** out);
+
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);
 

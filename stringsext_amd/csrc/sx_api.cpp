@@ -3,8 +3,18 @@
 #include "sx_ctx.hpp"
 #include "sx_print_core.hpp"
 #include "sx_select_core.hpp"
+#include "sx_selset_build.hpp"
+#include "sx_selset_core.hpp"
 
 using namespace sx;
+
+// sx_select_set_create: a compiled keyword list; `mem` = [the class map][the table], device memory of its own
+struct sx_select_set {
+    int device = 0;
+    uint8_t* mem = nullptr;
+    SelsetDevice dev{};
+    sx_select_set_info info{};
+};
 
 namespace sx {
 PinnedPool::Block PinnedPool::take(size_t bytes) {
@@ -729,15 +739,10 @@ static int grow_device(sx_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t bytes, 
     return SX_OK;
 }
 
-// grep -F where the findings lie (sx_select_dev.hip): pass 1 of every segment, one wait for the segments' totals, the selection block,
-// pass 2 of every segment that has selected findings, one more wait.  The source is read, never moved.
-int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, uint32_t flags, sx_result** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !r || !patterns || !out) return SX_E_INVALID;
-    if (n_patterns < 1 || n_patterns > SX_SELECT_MAX_PATTERNS) { ctx->set_err("n_patterns must be 1..16"); return SX_E_INVALID; }
-    if (flags & ~(uint32_t)(SX_SELECT_ASCII_NOCASE | SX_SELECT_INVERT)) { ctx->set_err("unknown selection flags"); return SX_E_INVALID; }
-    for (int p = 0; p < n_patterns; p++)
-        if (!patterns[p].bytes || patterns[p].len < 1 || patterns[p].len > SX_SELECT_MAX_PATTERN_BYTES) { ctx->set_err("a pattern must have 1..64 bytes"); return SX_E_INVALID; }
+// grep -F where the findings lie (sx_select_dev.hip), for both entry points, whose arguments are checked: pass 1 of every segment —
+// select_match_kernel with `patterns`, or selset_match_kernel with the compiled `set` —, one wait for the segments' totals, the
+// selection block, pass 2 of every segment that has selected findings, one more wait.  The source is read, never moved.
+static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, const SelsetDevice* set, uint32_t flags, sx_result** out) {
     if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
     { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
     // the block this call writes: a source that lies there was made two selections ago
@@ -759,9 +764,10 @@ int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* p
         SelectParams& p = P[i];
         memset(&p, 0, sizeof p);
         p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
-        select_fill_patterns(&p.pat, patterns, n_patterns, flags);
+        if (set) p.pat.invert = (flags & SX_SELECT_INVERT) ? 1u : 0u;
+        else select_fill_patterns(&p.pat, patterns, n_patterns, flags);
         const size_t bytes = select_scratch_bytes(s.ext_nf);
-        HIP_TRY(ctx, select_measure(&p, ctx->d_select_scratch + at, bytes, st, &d_count[i], &d_bytes[i]));
+        HIP_TRY(ctx, select_measure(&p, set, ctx->d_select_scratch + at, bytes, st, &d_count[i], &d_bytes[i]));
         at += bytes;
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -800,6 +806,64 @@ int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* p
     }
     *out = res.release();
     return SX_OK;
+}
+
+int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, uint32_t flags, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !patterns || !out) return SX_E_INVALID;
+    if (n_patterns < 1 || n_patterns > SX_SELECT_MAX_PATTERNS) { ctx->set_err("n_patterns must be 1..16"); return SX_E_INVALID; }
+    if (flags & ~(uint32_t)(SX_SELECT_ASCII_NOCASE | SX_SELECT_INVERT)) { ctx->set_err("unknown selection flags"); return SX_E_INVALID; }
+    for (int p = 0; p < n_patterns; p++)
+        if (!patterns[p].bytes || patterns[p].len < 1 || patterns[p].len > SX_SELECT_MAX_PATTERN_BYTES) { ctx->set_err("a pattern must have 1..64 bytes"); return SX_E_INVALID; }
+    return select_on_device(ctx, r, patterns, n_patterns, nullptr, flags, out);
+}
+
+int sx_select_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_set** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !out) return SX_E_INVALID;
+    SelsetTable T;
+    std::string err;
+    { const int rc = selset_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("pattern set: " + err); return rc; } }
+    if (ctx->host_only) { ctx->set_err("host-only context: no device for the pattern set"); return SX_E_STATE; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t table = (T.next.size() + 15) / 16 * 16;   // (selset_match_kernel copies the LDS rows in 16-byte chunks)
+    uint8_t* mem = nullptr;
+    if (hipMalloc((void**)&mem, sizeof T.map + table) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->set_err("pattern set: no device memory for " + std::to_string(sizeof T.map + table) + " bytes of table");
+        return SX_E_NOMEM;
+    }
+    hipError_t e = hipMemcpy(mem, T.map, sizeof T.map, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mem + sizeof T.map, T.next.data(), T.next.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(mem); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
+    sx_select_set* set = new (std::nothrow) sx_select_set;
+    if (!set) { (void)hipFree(mem); return SX_E_NOMEM; }
+    set->device = ctx->device; set->mem = mem;
+    set->dev = SelsetDevice{ mem, mem + sizeof T.map, T.states, T.classes, T.lds_states, T.matched, T.entry_bytes, 0 };
+    set->info = sx_select_set_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)T.next.size(), T.lds_states, 0 };
+    *out = set;
+    return SX_OK;
+}
+
+int sx_select_set_info_get(const sx_select_set* set, sx_select_set_info* out) {
+    if (!set || !out) return SX_E_INVALID;
+    *out = set->info;
+    return SX_OK;
+}
+
+void sx_select_set_free(sx_select_set* set) {
+    if (!set) return;
+    (void)hipFree(set->mem);
+    delete set;
+}
+
+int sx_result_select_set_device(sx_ctx* ctx, const sx_result* r, const sx_select_set* set, uint32_t flags, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !set || !out) return SX_E_INVALID;
+    if (flags & ~(uint32_t)SX_SELECT_INVERT) { ctx->set_err("a pattern set is selected with SX_SELECT_INVERT or no flag: the fold is compiled into the set"); return SX_E_INVALID; }
+    if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
+    if (set->device != ctx->device) { ctx->set_err("the pattern set lies on another device"); return SX_E_INVALID; }
+    return select_on_device(ctx, r, nullptr, 0, &set->dev, flags, out);
 }
 
 int sx_get_stats(const sx_ctx* ctx, sx_stats* out) {

@@ -77,7 +77,9 @@ static inline void select_fill_patterns(SelectPatterns* out, const sx_pattern* p
     }
 }
 
-SXD void select_string(const SelectParams& P, uint64_t i, uint64_t* off, uint32_t* len) {
+// (PP: SelectParams, or the SelsetParams of sx_selset_core.hpp)
+template <class PP>
+SXD void select_string(const PP& P, uint64_t i, uint64_t* off, uint32_t* len) {
     if (P.packed) { const sx_finding16 p = ((const sx_finding16*)P.recs)[i]; *off = p.str_off; *len = p.str_len; }
     else { const sx_finding f = ((const sx_finding*)P.recs)[i]; *off = f.str_off; *len = f.str_len; }
 }

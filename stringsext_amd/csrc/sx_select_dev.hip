@@ -60,8 +60,9 @@ size_t select_scratch_bytes(uint64_t n) {
 
 // Pass 1 of a segment (P.wbase, P.out_recs, P.out_src are not read): fills P.wmask / wcount / wbytes / wbase with places inside
 // `scratch`; *count and *bytes: the device words that will hold the number of selected records and their string bytes, valid when
-// `stream` has run this far.
-hipError_t select_measure(SelectParams* P, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes) {
+// `stream` has run this far.  set: NULL = P.pat's patterns (select_match_kernel); else a compiled set, whose kernel
+// (sx_selset_dev.hip) fills the same per-wavefront words, and of P.pat only `invert` counts.
+hipError_t select_measure(SelectParams* P, const SelsetDevice* set, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes) {
     if (P->n == 0 || P->n >= 0xFFFFFFFFull || scratch_bytes < select_scratch_bytes(P->n) || ((uintptr_t)scratch & 255)) return hipErrorInvalidValue;
     const uint64_t waves = (P->n + kSelectRecs - 1) / kSelectRecs;
     const size_t w8 = up256((size_t)(waves + 1) * 8), w4 = up256((size_t)(waves + 1) * 4);
@@ -72,8 +73,12 @@ hipError_t select_measure(SelectParams* P, void* scratch, size_t scratch_bytes, 
     P->wcount = (uint32_t*)at; at += w4;
     uint32_t* wbase = (uint32_t*)at; at += w4;
     size_t tmp_bytes = scratch_bytes - (size_t)(at - (uint8_t*)scratch);
-    hipLaunchKernelGGL(select_match_kernel, dim3((unsigned)((waves + 1 + kSelectWaves - 1) / kSelectWaves)), dim3(64 * kSelectWaves), 0, stream, *P, waves);
-    hipError_t e = hipGetLastError();
+    hipError_t e;
+    if (set) e = selset_launch_match(*P, *set, waves, stream);
+    else {
+        hipLaunchKernelGGL(select_match_kernel, dim3((unsigned)((waves + 1 + kSelectWaves - 1) / kSelectWaves)), dim3(64 * kSelectWaves), 0, stream, *P, waves);
+        e = hipGetLastError();
+    }
     if (e != hipSuccess) return e;
     e = rocprim::exclusive_scan(at, tmp_bytes, (const uint32_t*)P->wcount, wbase, 0u, (size_t)(waves + 1), rocprim::plus<uint32_t>(), stream);
     if (e != hipSuccess) return e;

@@ -532,6 +532,78 @@ int  sx_select_set_info_get(const sx_select_set* set, sx_select_set_info* out);
 void sx_select_set_free(sx_select_set* set);
 int  sx_result_select_set_device(sx_ctx* ctx, const sx_result* r, const sx_select_set* set, uint32_t flags, sx_result** out);
 
+/* The same selection by REGULAR EXPRESSION — `grep -E -f patterns` over the string part of the lines: URLs, e-mail addresses, dotted
+ * quads, registry paths, card-number shapes —, compiled once and used on buffer after buffer.  sx_select_regex_create builds, on
+ * the host, ONE minimal DFA for "some pattern matches somewhere in the string" (csrc/sx_selre_build.hpp: parser, NFA with the
+ * counted repeats unrolled, subset construction, minimisation, byte classes, states numbered breadth first) and puts its table into
+ * HBM on the context's device; a string byte costs one table look-up, and a lane stops early where the string has matched for good
+ * or can match no more.  A set holds 1..SX_SELECT_REGEX_MAX_PATTERNS patterns of 1..SX_SELECT_REGEX_MAX_PATTERN_BYTES bytes; a
+ * finding MATCHES if any pattern is found anywhere in its string (re.search, not fullmatch), and is selected iff (matches) XOR
+ * (SX_SELECT_INVERT).  A match never spans two findings.
+ * THE PATTERN LANGUAGE is a byte regex: patterns are raw bytes, the strings are UTF-8, a byte >= 0x80 is a literal byte and a
+ * quantifier behind it binds that one byte.  The governing rule: every pattern this library accepts means what Python 3's `re`
+ * means by it as a bytes pattern, with `$` read as `\Z` — Python's re.search is the tests' oracle —, and whatever would need a
+ * different reading is refused:
+ *   literals                              accepted
+ *   .                                     any byte except 0x0A
+ *   \t \n \r \f \v \xHH                   accepted; \x needs two hex digits
+ *   backslash + non-alphanumeric byte     that byte as a literal
+ *   \d \D \w \W \s \S                     Python's bytes-mode ASCII sets: \s = space \t \n \r \f \v, \w = [A-Za-z0-9_]; allowed
+ *                                         inside a class, but not as a range end
+ *   [...] [^...]                          ranges a-z need lo <= hi; `-` is a literal when first, last or escaped
+ *   ] directly behind [ or [^             refused: escape it
+ *   an unescaped [ inside a class         refused
+ *   (...) (?:...)                         the same thing: nothing is captured; any other (? is refused
+ *   |                                     empty alternatives and () are allowed and match the empty string
+ *   * + ? {m} {m,} {m,n} {,n}             m <= n <= SX_SELECT_REGEX_MAX_REPEAT
+ *   a trailing ? on a quantifier (lazy)   accepted and ignored: only existence is asked
+ *   a second quantifier, *+               refused
+ *   a quantifier with nothing in front of it, or on ^ or $        refused
+ *   a { that does not begin a well-formed bound                   refused: escape it
+ *   ^                                     matches only in front of the string's first byte
+ *   $                                     matches only behind its last byte; there is no "in front of a trailing newline" rule:
+ *                                         this is the line rule of grep, and a finding is a line
+ *   ^ or $ in mid-pattern                 legal: (^a|b)c, a$|b; a^b is legal and matches nothing
+ *   every other backslash + alphanumeric (\b \B \A \Z \1 \e ...)  refused
+ * Refused means SX_E_INVALID, and sx_last_error names the pattern's index, the byte offset and the reason.  Not in the language:
+ * Unicode-aware classes and folding ([а-я] is a byte class), \b, lookaround, back-references, captures, where the match lies, which
+ * pattern matched.
+ * flags: 0 or SX_SELECT_ASCII_NOCASE — the fold is compiled into the set, and it is re.IGNORECASE on a bytes pattern: a literal
+ * letter matches both cases, a class holds a letter's other case too and negation applies after that ([Z-a] matches z and A,
+ * [^Z-a] matches neither); no byte >= 0x80 is folded.
+ * The compiled object owns its device memory and does not depend on the context's lifetime: it may be freed before or after
+ * sx_destroy, and used with any context on the same HIP device (another device: SX_E_INVALID).
+ * sx_select_regex_create: SX_E_INVALID for n_patterns outside 1..SX_SELECT_REGEX_MAX_PATTERNS, a len outside
+ * 1..SX_SELECT_REGEX_MAX_PATTERN_BYTES, a NULL pointer, any other flag bit, a refused pattern, or a limit passed — a repeat count
+ * above SX_SELECT_REGEX_MAX_REPEAT, more than SX_SELECT_REGEX_MAX_POSITIONS positions (every byte set, anchor and empty branch is
+ * one, counted with the repeats unrolled, all patterns together), more than SX_SELECT_REGEX_MAX_STATES states in the subset
+ * construction (it runs before the minimisation and stops at the first state above the limit), or that construction's bound on its
+ * own memory: its states are kept as lists of positions, and 32 Mi positions in all of them are the most (an unanchored a{51000}
+ * meets it, its k-th state holding k positions, though its minimal DFA has 51 001 states; ^a{51000} compiles) —: the text says
+ * which.  SX_E_STATE: a host-only context.  SX_E_NOMEM: the table cannot be allocated.  *out = NULL on every error.
+ * sx_select_regex_info_get: what was built — table_bytes (states * classes * 2) lie in HBM, the rows of the first lds_states states
+ * are what the kernel (csrc/sx_selre_dev.hip) keeps in LDS, the other rows it reads through L2; end_states come from `$`.
+ * sx_result_select_regex_device: flags 0 or SX_SELECT_INVERT; in everything else the contract of sx_result_select_set_device, word
+ * for word — the output layout, the empty result, the source that is read and never moved, the sources accepted (a result of any
+ * of the three kinds of selection among them: AND), the errors.  It writes the same two selection blocks: calls of all three kinds
+ * count together for "valid until the SECOND selection after the one that made it". */
+#define SX_SELECT_REGEX_MAX_PATTERNS      64u
+#define SX_SELECT_REGEX_MAX_PATTERN_BYTES 1024u
+#define SX_SELECT_REGEX_MAX_REPEAT        255u
+#define SX_SELECT_REGEX_MAX_POSITIONS     65536u  /* NFA positions once counted repeats are unrolled, all patterns together */
+#define SX_SELECT_REGEX_MAX_STATES        65536u  /* DFA states: an entry always has 2 bytes */
+typedef struct sx_select_regex sx_select_regex;
+typedef struct sx_select_regex_info {
+    uint32_t n_patterns, states, classes, nocase;
+    uint64_t table_bytes;   /* in HBM */
+    uint32_t lds_states;    /* states whose rows the kernel keeps in LDS */
+    uint32_t end_states;    /* states that select a string only if it ENDS there */
+} sx_select_regex_info;
+int  sx_select_regex_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_regex** out);
+int  sx_select_regex_info_get(const sx_select_regex* re, sx_select_regex_info* out);
+void sx_select_regex_free(sx_select_regex* re);
+int  sx_result_select_regex_device(sx_ctx* ctx, const sx_result* r, const sx_select_regex* re, uint32_t flags, sx_result** out);
+
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);
 

@@ -20,6 +20,9 @@ SX_OPT_NO_FUSED_SCAN = 64      # round 6: one scan launch per Mission instead of
 SX_SELECT_MAX_PATTERNS, SX_SELECT_MAX_PATTERN_BYTES = 16, 64   # sx_result_select_device (Result.select_device)
 SX_SELECT_ASCII_NOCASE, SX_SELECT_INVERT = 1, 2
 SX_SELECT_SET_MAX_PATTERNS, SX_SELECT_SET_MAX_PATTERN_BYTES, SX_SELECT_SET_MAX_TOTAL_BYTES = 65536, 255, 1 << 20   # sx_select_set_create (Scanner.pattern_set)
+# sx_select_regex_create (Scanner.regex_set)
+SX_SELECT_REGEX_MAX_PATTERNS, SX_SELECT_REGEX_MAX_PATTERN_BYTES, SX_SELECT_REGEX_MAX_REPEAT = 64, 1024, 255
+SX_SELECT_REGEX_MAX_POSITIONS, SX_SELECT_REGEX_MAX_STATES = 65536, 65536
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -38,7 +41,8 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_decoder_table", "sx_wave_classes", "sx_scan_classifier", "sx_result_segment_packed", "sx_wave_swar", "sx_wave_pair_codes2", "sx_wave_pair_codes", "sx_shard_bounds", "sx_scan_sharded", "sx_shard_splice", "sx_shard_splice_segs", "sx_transport_rccl_id", "sx_transport_rccl_create", "sx_transport_destroy", "sx_transport_last_error", "sx_transport_allgather", "sx_transport_gather",
            "sx_result_count", "sx_result_segments", "sx_result_segment", "sx_result_segment_device", "sx_result_findings", "sx_result_arena",
            "sx_result_free", "sx_print_findings", "sx_print_findings_device", "sx_result_select_device",
-           "sx_select_set_create", "sx_select_set_info_get", "sx_select_set_free", "sx_result_select_set_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
+           "sx_select_set_create", "sx_select_set_info_get", "sx_select_set_free", "sx_result_select_set_device", "sx_select_regex_create", "sx_select_regex_info_get", "sx_select_regex_free",
+           "sx_result_select_regex_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
 
@@ -172,6 +176,11 @@ class SelectSetInfo(C.Structure):   # sx_select_set_info
                 ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SelectRegexInfo(C.Structure):   # sx_select_regex_info
+    _fields_ = [("n_patterns", C.c_uint32), ("states", C.c_uint32), ("classes", C.c_uint32), ("nocase", C.c_uint32),
+                ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32), ("end_states", C.c_uint32)]
+
+
 class Run(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("chars", C.c_uint64)]
 
@@ -249,6 +258,10 @@ def lib():
     L.sx_select_set_info_get.argtypes = [vp, C.POINTER(SelectSetInfo)]
     L.sx_select_set_free.argtypes, L.sx_select_set_free.restype = [vp], None
     L.sx_result_select_set_device.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.sx_select_regex_create.argtypes = [vp, C.POINTER(Pattern), C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.sx_select_regex_info_get.argtypes = [vp, C.POINTER(SelectRegexInfo)]
+    L.sx_select_regex_free.argtypes, L.sx_select_regex_free.restype = [vp], None
+    L.sx_result_select_regex_device.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(vp)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -381,7 +394,19 @@ class Result:
         selection is valid until the second select_device() on the Scanner after this one (a scan does not invalidate it) or
         close().  Raises SxError: SX_E_INVALID for bad patterns, SX_E_STATE wherever printed_device() would refuse this Result.
         `patterns` may also be a PatternSet (Scanner.pattern_set: a compiled keyword list of up to 65536 patterns, grep -F -f): the
-        same selection by sx_result_select_set_device; the fold belongs to the set then, and ignore_case=True raises ValueError."""
+        same selection by sx_result_select_set_device; the fold belongs to the set then, and ignore_case=True raises ValueError.
+        Or a RegexSet (Scanner.regex_set: up to 64 byte regular expressions, grep -E -f): sx_result_select_regex_device, with the
+        same rule for the fold."""
+        if isinstance(patterns, RegexSet):
+            if ignore_case:
+                raise ValueError("ignore_case belongs to the RegexSet: Scanner.regex_set(patterns, ignore_case=True)")
+            if not self._s.h:
+                raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+            if not patterns.h:
+                raise SxError(SX_E_INVALID, "the RegexSet has been freed")
+            out = C.c_void_p()
+            self._s._chk(lib().sx_result_select_regex_device(self._s.h, self.h, patterns.h, SX_SELECT_INVERT if invert else 0, C.byref(out)))
+            return Result(self._s, out)
         if isinstance(patterns, PatternSet):
             if ignore_case:
                 raise ValueError("ignore_case belongs to the PatternSet: Scanner.pattern_set(patterns, ignore_case=True)")
@@ -441,6 +466,34 @@ class PatternSet:
             pass
 
 
+class RegexSet:
+    """Byte regular expressions compiled for the device (sx_select_regex_create; Scanner.regex_set makes it): Result.select_device()
+    takes it in place of a list, on result after result.  It owns its device memory: free() it before or after the Scanner's
+    close()."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    def info(self):
+        """sx_select_regex_info as a dict: n_patterns, states, classes, nocase, table_bytes (in HBM), lds_states, end_states"""
+        i = SelectRegexInfo()
+        rc = lib().sx_select_regex_info_get(self.h, C.byref(i))
+        if rc != SX_OK:
+            raise SxError(rc, "the RegexSet has been freed")
+        return {k: getattr(i, k) for k, _ in SelectRegexInfo._fields_}
+
+    def free(self):
+        if self.h:
+            lib().sx_select_regex_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Scanner:
     """One sx_ctx: N missions bound to one HIP device (device=SX_HOST_ONLY: replay stage only).
     result_on_device=True (SX_OPT_RESULT_ON_DEVICE): the result of scan() / scan_device() stays in HBM — Result.device_segments(),
@@ -481,6 +534,17 @@ class Scanner:
         out = C.c_void_p()
         self._chk(lib().sx_select_set_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
         return PatternSet(out)
+
+    def regex_set(self, patterns, ignore_case=False):
+        """sx_select_regex_create: `patterns` (1..64 bytes objects of 1..1024 bytes: the byte regex language of
+        include/stringsext_amd.h, which means what Python's `re` means with `$` read as `\\Z`) compiled into one DFA in HBM on this
+        Scanner's device, for Result.select_device().  ignore_case: re.IGNORECASE on a bytes pattern, compiled in.  A refused
+        pattern raises SxError (SX_E_INVALID) whose text names the pattern's index, the offset and the reason."""
+        pats = [bytes(p) for p in patterns]
+        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        out = C.c_void_p()
+        self._chk(lib().sx_select_regex_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        return RegexSet(out)
 
     def scan(self, data, file_id=-1, is_last=False):
         """sx_scan: replaces the loop src/main.rs:153-168 for one chunk held in host memory."""

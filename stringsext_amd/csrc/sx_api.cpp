@@ -5,6 +5,8 @@
 #include "sx_select_core.hpp"
 #include "sx_selset_build.hpp"
 #include "sx_selset_core.hpp"
+#include "sx_selre_build.hpp"
+#include "sx_selre_core.hpp"
 
 using namespace sx;
 
@@ -14,6 +16,14 @@ struct sx_select_set {
     uint8_t* mem = nullptr;
     SelsetDevice dev{};
     sx_select_set_info info{};
+};
+
+// sx_select_regex_create: compiled regular expressions; `mem` as a set's
+struct sx_select_regex {
+    int device = 0;
+    uint8_t* mem = nullptr;
+    SelreDevice dev{};
+    sx_select_regex_info info{};
 };
 
 namespace sx {
@@ -739,10 +749,10 @@ static int grow_device(sx_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t bytes, 
     return SX_OK;
 }
 
-// grep -F where the findings lie (sx_select_dev.hip), for both entry points, whose arguments are checked: pass 1 of every segment —
-// select_match_kernel with `patterns`, or selset_match_kernel with the compiled `set` —, one wait for the segments' totals, the
+// grep where the findings lie (sx_select_dev.hip), for the three entry points, whose arguments are checked: pass 1 of every segment —
+// select_match_kernel with `patterns`, selset_match_kernel with the compiled `set`, or selre_match_kernel with the compiled `re` —, one wait for the segments' totals, the
 // selection block, pass 2 of every segment that has selected findings, one more wait.  The source is read, never moved.
-static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, const SelsetDevice* set, uint32_t flags, sx_result** out) {
+static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, const SelsetDevice* set, const SelreDevice* re, uint32_t flags, sx_result** out) {
     if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
     { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
     // the block this call writes: a source that lies there was made two selections ago
@@ -764,10 +774,10 @@ static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* p
         SelectParams& p = P[i];
         memset(&p, 0, sizeof p);
         p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
-        if (set) p.pat.invert = (flags & SX_SELECT_INVERT) ? 1u : 0u;
+        if (set || re) p.pat.invert = (flags & SX_SELECT_INVERT) ? 1u : 0u;
         else select_fill_patterns(&p.pat, patterns, n_patterns, flags);
         const size_t bytes = select_scratch_bytes(s.ext_nf);
-        HIP_TRY(ctx, select_measure(&p, set, ctx->d_select_scratch + at, bytes, st, &d_count[i], &d_bytes[i]));
+        HIP_TRY(ctx, select_measure(&p, set, re, ctx->d_select_scratch + at, bytes, st, &d_count[i], &d_bytes[i]));
         at += bytes;
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -815,7 +825,7 @@ int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* p
     if (flags & ~(uint32_t)(SX_SELECT_ASCII_NOCASE | SX_SELECT_INVERT)) { ctx->set_err("unknown selection flags"); return SX_E_INVALID; }
     for (int p = 0; p < n_patterns; p++)
         if (!patterns[p].bytes || patterns[p].len < 1 || patterns[p].len > SX_SELECT_MAX_PATTERN_BYTES) { ctx->set_err("a pattern must have 1..64 bytes"); return SX_E_INVALID; }
-    return select_on_device(ctx, r, patterns, n_patterns, nullptr, flags, out);
+    return select_on_device(ctx, r, patterns, n_patterns, nullptr, nullptr, flags, out);
 }
 
 int sx_select_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_set** out) {
@@ -863,7 +873,55 @@ int sx_result_select_set_device(sx_ctx* ctx, const sx_result* r, const sx_select
     if (flags & ~(uint32_t)SX_SELECT_INVERT) { ctx->set_err("a pattern set is selected with SX_SELECT_INVERT or no flag: the fold is compiled into the set"); return SX_E_INVALID; }
     if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
     if (set->device != ctx->device) { ctx->set_err("the pattern set lies on another device"); return SX_E_INVALID; }
-    return select_on_device(ctx, r, nullptr, 0, &set->dev, flags, out);
+    return select_on_device(ctx, r, nullptr, 0, &set->dev, nullptr, flags, out);
+}
+
+int sx_select_regex_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_regex** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !out) return SX_E_INVALID;
+    SelreTable T;
+    std::string err;
+    { const int rc = selre_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("regex set: " + err); return rc; } }
+    if (ctx->host_only) { ctx->set_err("host-only context: no device for the regex set"); return SX_E_STATE; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = T.next.size() * sizeof(uint16_t), table = (bytes + 15) / 16 * 16;   // (selre_match_kernel copies the LDS rows in 16-byte chunks)
+    uint8_t* mem = nullptr;
+    if (hipMalloc((void**)&mem, sizeof T.map + table) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->set_err("regex set: no device memory for " + std::to_string(sizeof T.map + table) + " bytes of table");
+        return SX_E_NOMEM;
+    }
+    hipError_t e = hipMemcpy(mem, T.map, sizeof T.map, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mem + sizeof T.map, T.next.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(mem); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
+    sx_select_regex* re = new (std::nothrow) sx_select_regex;
+    if (!re) { (void)hipFree(mem); return SX_E_NOMEM; }
+    re->device = ctx->device; re->mem = mem;
+    re->dev = SelreDevice{ mem, (const uint16_t*)(mem + sizeof T.map), T.states, T.classes, T.lds_states, T.end_first, T.stop_first, T.matched, T.root_end, 0 };
+    re->info = sx_select_regex_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)bytes, T.lds_states, T.end_states };
+    *out = re;
+    return SX_OK;
+}
+
+int sx_select_regex_info_get(const sx_select_regex* re, sx_select_regex_info* out) {
+    if (!re || !out) return SX_E_INVALID;
+    *out = re->info;
+    return SX_OK;
+}
+
+void sx_select_regex_free(sx_select_regex* re) {
+    if (!re) return;
+    (void)hipFree(re->mem);
+    delete re;
+}
+
+int sx_result_select_regex_device(sx_ctx* ctx, const sx_result* r, const sx_select_regex* re, uint32_t flags, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !re || !out) return SX_E_INVALID;
+    if (flags & ~(uint32_t)SX_SELECT_INVERT) { ctx->set_err("a regex set is selected with SX_SELECT_INVERT or no flag: the fold is compiled into the set"); return SX_E_INVALID; }
+    if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
+    if (re->device != ctx->device) { ctx->set_err("the regex set lies on another device"); return SX_E_INVALID; }
+    return select_on_device(ctx, r, nullptr, 0, nullptr, &re->dev, flags, out);
 }
 
 int sx_get_stats(const sx_ctx* ctx, sx_stats* out) {

@@ -276,12 +276,15 @@ hipError_t print_write(const PrintParams& P, hipStream_t stream);
 // pass 1 — fills P's per-wavefront tables inside `scratch` (select_scratch_bytes(n), 256-aligned); *count, *bytes = the device words with
 // the selected records' number and string bytes, valid once `stream` has got there; select_place: the selected records to out_recs, their
 // strings back to back to out_arena (scratch: select_place_scratch_bytes(n_sel), 256-aligned; order_part_strings inside)
-// (set: NULL, or a compiled keyword set — sx_selset_core.hpp —, whose selset_match_kernel then is pass 1: sx_selset_dev.hip)
+// (set: NULL, or a compiled keyword set — sx_selset_core.hpp —, whose selset_match_kernel then is pass 1: sx_selset_dev.hip; re: NULL, or
+// a compiled regex set — sx_selre_core.hpp —, whose selre_match_kernel then is pass 1: sx_selre_dev.hip; not both)
 struct SelectParams;
 struct SelsetDevice;
+struct SelreDevice;
 size_t select_scratch_bytes(uint64_t n);
 hipError_t selset_launch_match(const SelectParams& P, const SelsetDevice& set, uint64_t waves, hipStream_t stream);
-hipError_t select_measure(SelectParams* P, const SelsetDevice* set, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes);
+hipError_t selre_launch_match(const SelectParams& P, const SelreDevice& re, uint64_t waves, hipStream_t stream);
+hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreDevice* re, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes);
 size_t select_place_scratch_bytes(uint64_t n_sel);
 hipError_t select_place(const SelectParams& P, void* out_recs, uint64_t n_sel, uint8_t* out_arena, void* scratch, size_t scratch_bytes, hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)

@@ -604,6 +604,59 @@ int  sx_select_regex_info_get(const sx_select_regex* re, sx_select_regex_info* o
 void sx_select_regex_free(sx_select_regex* re);
 int  sx_result_select_regex_device(sx_ctx* ctx, const sx_result* r, const sx_select_regex* re, uint32_t flags, sx_result** out);
 
+/* The keyword TALLY of a result whose segments ALL lie in HBM: which entries of an indicator list occur in the findings' strings, how
+ * often, and where first — what the three selections throw away —, counted where the findings lie (csrc/sx_seltally_dev.hip), one pass
+ * over the strings for up to 65536 keywords.  sx_tally_set_create builds, on the host, the Aho-Corasick automaton of the patterns as
+ * a full table with output links (csrc/sx_seltally_build.hpp: byte classes, a state per distinct prefix of the keywords, numbered
+ * breadth first, NOT collapsed; per state the keyword that ends there and the next state on the failure chain that ends one) and puts
+ * it into HBM on the context's device, with two counters per keyword.  The limits and flags are sx_select_set_create's: 1..
+ * SX_SELECT_SET_MAX_PATTERNS patterns of 1..SX_SELECT_SET_MAX_PATTERN_BYTES bytes, SX_SELECT_SET_MAX_TOTAL_BYTES in all; flags 0 or
+ * SX_SELECT_ASCII_NOCASE — the fold is compiled into the set.  Duplicate patterns are allowed.  The errors are the same: SX_E_INVALID
+ * for a limit passed, a NULL pointer or any other flag bit, SX_E_STATE for a host-only context, SX_E_NOMEM if the tables cannot be
+ * allocated; *out = NULL on every error.  The set owns its device memory, tables and counters, and does not depend on the context's
+ * lifetime: it may be freed before or after sx_destroy, and used with any context on the same HIP device (another device:
+ * SX_E_INVALID).
+ * THE HIT RULE.  A HIT of keyword k is a pair (finding i, offset o) with s_i[o, o + len_k) == p_k: bytes compared as bytes, after the
+ * ASCII fold of both sides if the set is nocase.  Occurrences of one keyword that overlap themselves all count ("aa" has 3 hits in
+ * "aaaa").  A hit never spans two findings.
+ * THE COUNTERS, per keyword, read after one or more sx_result_tally_device calls: hits[k] = the number of hits of pattern k;
+ * first[k] = the smallest (ordinal_base + index of the finding in the result's print order) among its hits — the print order is
+ * segment 0's records, then segment 1's, and so on —, or SX_TALLY_NEVER if there is none.  Patterns that are equal after the fold are
+ * one keyword (sx_tally_set_info.unique counts those) and report the same pair.  A new set is reset.
+ * sx_result_tally_device ADDS the hits of r's findings to the counters: a stream scanned buffer by buffer gives one tally of the whole
+ * stream if the caller passes the number of findings of the buffers before as ordinal_base.  *n_findings (may be NULL) = the number
+ * of findings walked.  The call returns when the kernels are done.  The sources are exactly what sx_print_findings_device accepts — both
+ * record types, any layout of the strings, the result of any of the three selections (the tally of a regex selection: "which
+ * indicators sit on lines that look like URLs") —, and SX_E_STATE comes back wherever that function would refuse the source; that is
+ * decided for ALL segments before anything is launched, and a refused call adds nothing.  The source is read, never moved.  The call
+ * writes neither the result block nor the selection blocks: it does NOT count towards "valid until the SECOND selection after the one
+ * that made it" and invalidates nothing.  SX_E_INVALID: a NULL ctx, r or set, a set on another device.
+ * sx_tally_set_reset: every hits = 0, every first = SX_TALLY_NEVER.  sx_tally_set_read: hits and first per INPUT pattern (either array
+ * may be NULL); n_patterns must be the set's (else SX_E_INVALID).  sx_tally_set_counters_device: the counters where they lie, in HBM,
+ * indexed by UNIQUE id (*unique entries each), and *d_unique_of_pattern = n_patterns words that map an input pattern to its unique id,
+ * for hosts that stay on the GPU; any of the four may be NULL; valid until sx_tally_set_free.
+ * sx_tally_set_info_get: what was built — states (the distinct prefixes, the empty one included), entries of entry_bytes (2 while
+ * states <= 32768, else 4), table_bytes in HBM (everything but the counters), the rows of the first lds_states states are what the
+ * kernel keeps in LDS, the other rows it reads through L2.
+ * Not thread-safe: one sx_result_tally_device call per set at a time, and no reset or read during it.
+ * Not built: the number of FINDINGS per keyword (grep -c) and where in a string a hit lies. */
+typedef struct sx_tally_set sx_tally_set;
+typedef struct sx_tally_set_info {
+    uint32_t n_patterns, unique;   /* unique: distinct keywords after the fold */
+    uint32_t states, classes, nocase, entry_bytes;   /* entry_bytes 2 or 4 */
+    uint64_t table_bytes;          /* everything the set holds in HBM except the counters */
+    uint32_t lds_states, reserved;
+} sx_tally_set_info;               /* 40 bytes */
+#define SX_TALLY_NEVER UINT64_MAX
+int  sx_tally_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_tally_set** out);
+int  sx_tally_set_info_get(const sx_tally_set* set, sx_tally_set_info* out);
+void sx_tally_set_free(sx_tally_set* set);
+int  sx_tally_set_reset(sx_tally_set* set);
+int  sx_result_tally_device(sx_ctx* ctx, const sx_result* r, sx_tally_set* set, uint64_t ordinal_base, uint64_t* n_findings);
+int  sx_tally_set_read(const sx_tally_set* set, uint64_t* hits, uint64_t* first, uint32_t n_patterns);
+int  sx_tally_set_counters_device(const sx_tally_set* set, const uint64_t** d_hits, const uint64_t** d_first,
+                                  const uint32_t** d_unique_of_pattern, uint32_t* unique);
+
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);
 

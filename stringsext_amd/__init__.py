@@ -23,6 +23,7 @@ SX_SELECT_SET_MAX_PATTERNS, SX_SELECT_SET_MAX_PATTERN_BYTES, SX_SELECT_SET_MAX_T
 # sx_select_regex_create (Scanner.regex_set)
 SX_SELECT_REGEX_MAX_PATTERNS, SX_SELECT_REGEX_MAX_PATTERN_BYTES, SX_SELECT_REGEX_MAX_REPEAT = 64, 1024, 255
 SX_SELECT_REGEX_MAX_POSITIONS, SX_SELECT_REGEX_MAX_STATES = 65536, 65536
+SX_TALLY_NEVER = (1 << 64) - 1   # sx_tally_set_read: first[k] of a keyword without a hit
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -42,7 +43,8 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_result_count", "sx_result_segments", "sx_result_segment", "sx_result_segment_device", "sx_result_findings", "sx_result_arena",
            "sx_result_free", "sx_print_findings", "sx_print_findings_device", "sx_result_select_device",
            "sx_select_set_create", "sx_select_set_info_get", "sx_select_set_free", "sx_result_select_set_device", "sx_select_regex_create", "sx_select_regex_info_get", "sx_select_regex_free",
-           "sx_result_select_regex_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
+           "sx_result_select_regex_device", "sx_tally_set_create", "sx_tally_set_info_get", "sx_tally_set_free", "sx_tally_set_reset",
+           "sx_result_tally_device", "sx_tally_set_read", "sx_tally_set_counters_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
 
@@ -181,6 +183,12 @@ class SelectRegexInfo(C.Structure):   # sx_select_regex_info
                 ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32), ("end_states", C.c_uint32)]
 
 
+class TallySetInfo(C.Structure):   # sx_tally_set_info
+    _fields_ = [("n_patterns", C.c_uint32), ("unique", C.c_uint32), ("states", C.c_uint32), ("classes", C.c_uint32),
+                ("nocase", C.c_uint32), ("entry_bytes", C.c_uint32), ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class Run(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("chars", C.c_uint64)]
 
@@ -262,6 +270,13 @@ def lib():
     L.sx_select_regex_info_get.argtypes = [vp, C.POINTER(SelectRegexInfo)]
     L.sx_select_regex_free.argtypes, L.sx_select_regex_free.restype = [vp], None
     L.sx_result_select_regex_device.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.sx_tally_set_create.argtypes = [vp, C.POINTER(Pattern), C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.sx_tally_set_info_get.argtypes = [vp, C.POINTER(TallySetInfo)]
+    L.sx_tally_set_free.argtypes, L.sx_tally_set_free.restype = [vp], None
+    L.sx_tally_set_reset.argtypes = [vp]
+    L.sx_result_tally_device.argtypes = [vp, vp, vp, u64, pu64]
+    L.sx_tally_set_read.argtypes = [vp, pu64, pu64, C.c_uint32]
+    L.sx_tally_set_counters_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint32)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -427,6 +442,19 @@ class Result:
         self._s._chk(lib().sx_result_select_device(self._s.h, self.h, arr, len(pats), flags, C.byref(out)))
         return Result(self._s, out)
 
+    def tally_device(self, tally, ordinal_base=0):
+        """sx_result_tally_device: the hits of `tally`'s keywords (a TallySet: Scanner.tally_set) in this Result's strings, ADDED to
+        the set's counters on the device; a hit's ordinal is ordinal_base + the finding's index in this Result's print order.
+        Returns the number of findings walked.  This Result is read, not moved, and no selection ages.  Raises SxError: SX_E_STATE
+        wherever printed_device() would refuse this Result (nothing is added then), SX_E_INVALID for a freed set."""
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        if not isinstance(tally, TallySet) or not tally.h:
+            raise SxError(SX_E_INVALID, "the TallySet has been freed" if isinstance(tally, TallySet) else "tally_device takes a TallySet")
+        n = C.c_uint64()
+        self._s._chk(lib().sx_result_tally_device(self._s.h, self.h, tally.h, ordinal_base, C.byref(n)))
+        return n.value
+
     def free(self):
         if self.h:
             lib().sx_result_free(self.h)
@@ -494,6 +522,62 @@ class RegexSet:
             pass
 
 
+class TallySet:
+    """A keyword list compiled for counting on the device (sx_tally_set_create; Scanner.tally_set makes it), with its counters:
+    Result.tally_device() adds a result's hits to them, on result after result.  It owns its device memory: free() it before or
+    after the Scanner's close()."""
+
+    def __init__(self, handle, n_patterns):
+        self.h, self.n_patterns = handle, n_patterns
+
+    def _handle(self):
+        if not self.h:
+            raise SxError(SX_E_INVALID, "the TallySet has been freed")
+        return self.h
+
+    def info(self):
+        """sx_tally_set_info as a dict: n_patterns, unique, states, classes, nocase, entry_bytes, table_bytes (in HBM), lds_states"""
+        i = TallySetInfo()
+        rc = lib().sx_tally_set_info_get(self._handle(), C.byref(i))
+        if rc != SX_OK:
+            raise SxError(rc, "sx_tally_set_info_get")
+        return {k: getattr(i, k) for k, _ in TallySetInfo._fields_ if k != "reserved"}
+
+    def read(self):
+        """(hits, first): two lists with an entry per input pattern; first[k] is SX_TALLY_NEVER where hits[k] is 0"""
+        hits, first = (C.c_uint64 * self.n_patterns)(), (C.c_uint64 * self.n_patterns)()
+        rc = lib().sx_tally_set_read(self._handle(), hits, first, self.n_patterns)
+        if rc != SX_OK:
+            raise SxError(rc, "sx_tally_set_read")
+        return list(hits), list(first)
+
+    def reset(self):
+        """every hits = 0, every first = SX_TALLY_NEVER"""
+        rc = lib().sx_tally_set_reset(self._handle())
+        if rc != SX_OK:
+            raise SxError(rc, "sx_tally_set_reset")
+
+    def counters_device(self):
+        """(d_hits, d_first, d_unique_of_pattern, unique): device addresses — two arrays of `unique` uint64 indexed by unique id, and
+        n_patterns uint32 that map an input pattern to its unique id"""
+        h, f, m, u = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32()
+        rc = lib().sx_tally_set_counters_device(self._handle(), C.byref(h), C.byref(f), C.byref(m), C.byref(u))
+        if rc != SX_OK:
+            raise SxError(rc, "sx_tally_set_counters_device")
+        return h.value, f.value, m.value, u.value
+
+    def free(self):
+        if self.h:
+            lib().sx_tally_set_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Scanner:
     """One sx_ctx: N missions bound to one HIP device (device=SX_HOST_ONLY: replay stage only).
     result_on_device=True (SX_OPT_RESULT_ON_DEVICE): the result of scan() / scan_device() stays in HBM — Result.device_segments(),
@@ -534,6 +618,15 @@ class Scanner:
         out = C.c_void_p()
         self._chk(lib().sx_select_set_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
         return PatternSet(out)
+
+    def tally_set(self, patterns, ignore_case=False):
+        """sx_tally_set_create: `patterns` (the limits of pattern_set) compiled into an automaton with output links and two counters
+        per keyword in HBM on this Scanner's device, for Result.tally_device().  ignore_case: 'A'..'Z' as 'a'..'z', compiled in."""
+        pats = [bytes(p) for p in patterns]
+        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        out = C.c_void_p()
+        self._chk(lib().sx_tally_set_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        return TallySet(out, len(pats))
 
     def regex_set(self, patterns, ignore_case=False):
         """sx_select_regex_create: `patterns` (1..64 bytes objects of 1..1024 bytes: the byte regex language of

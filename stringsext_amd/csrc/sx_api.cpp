@@ -7,6 +7,8 @@
 #include "sx_selset_core.hpp"
 #include "sx_selre_build.hpp"
 #include "sx_selre_core.hpp"
+#include "sx_seltally_build.hpp"
+#include "sx_seltally_core.hpp"
 
 using namespace sx;
 
@@ -24,6 +26,17 @@ struct sx_select_regex {
     uint8_t* mem = nullptr;
     SelreDevice dev{};
     sx_select_regex_info info{};
+};
+
+// sx_tally_set_create: a keyword list compiled for the tally; `mem` = [the class map][the table][own][dict][pattern -> unique id]
+// [hits][first], device memory of its own
+struct sx_tally_set {
+    int device = 0;
+    uint8_t* mem = nullptr;
+    SeltallyDevice dev{};
+    const uint32_t* d_unique_of_pattern = nullptr;
+    std::vector<uint32_t> unique_of_pattern;
+    sx_tally_set_info info{};
 };
 
 namespace sx {
@@ -922,6 +935,116 @@ int sx_result_select_regex_device(sx_ctx* ctx, const sx_result* r, const sx_sele
     if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
     if (re->device != ctx->device) { ctx->set_err("the regex set lies on another device"); return SX_E_INVALID; }
     return select_on_device(ctx, r, nullptr, 0, nullptr, &re->dev, flags, out);
+}
+
+int sx_tally_set_reset(sx_tally_set* set) {
+    if (!set) return SX_E_INVALID;
+    if (hipSetDevice(set->device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    hipError_t e = hipMemset(set->dev.hits, 0, (size_t)set->dev.unique * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMemset(set->dev.first, 0xFF, (size_t)set->dev.unique * sizeof(uint64_t));   // SX_TALLY_NEVER
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (a device memset may return before it is done, and the tally runs on a stream that does not wait for this one)
+    if (e != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    return SX_OK;
+}
+
+int sx_tally_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_tally_set** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !out) return SX_E_INVALID;
+    SeltallyTable T;
+    std::string err;
+    { const int rc = seltally_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("tally set: " + err); return rc; } }
+    if (ctx->host_only) { ctx->set_err("host-only context: no device for the tally set"); return SX_E_STATE; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t table = (T.next.size() + 15) / 16 * 16;   // (seltally_kernel copies the LDS rows in 16-byte chunks)
+    const size_t per_state = (size_t)T.states * sizeof(uint32_t), map_words = (((size_t)T.n_patterns + 1) & ~(size_t)1) * sizeof(uint32_t);
+    const size_t counters = (size_t)T.unique * sizeof(uint64_t);
+    const size_t at_own = sizeof T.map + table, at_dict = at_own + per_state, at_map = at_dict + per_state;
+    const size_t at_hits = (at_map + map_words + 7) / 8 * 8, bytes = at_hits + 2 * counters;
+    uint8_t* mem = nullptr;
+    if (hipMalloc((void**)&mem, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->set_err("tally set: no device memory for " + std::to_string(bytes) + " bytes of tables and counters");
+        return SX_E_NOMEM;
+    }
+    hipError_t e = hipMemcpy(mem, T.map, sizeof T.map, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mem + sizeof T.map, T.next.data(), T.next.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mem + at_own, T.own.data(), per_state, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mem + at_dict, T.dict.data(), per_state, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mem + at_map, T.unique_of_pattern.data(), (size_t)T.n_patterns * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(mem); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
+    sx_tally_set* set = new (std::nothrow) sx_tally_set;
+    if (!set) { (void)hipFree(mem); return SX_E_NOMEM; }
+    set->device = ctx->device; set->mem = mem;
+    set->dev = SeltallyDevice{ mem, mem + sizeof T.map, (const uint32_t*)(mem + at_own), (const uint32_t*)(mem + at_dict),
+                               (uint64_t*)(mem + at_hits), (uint64_t*)(mem + at_hits + counters),
+                               T.states, T.classes, T.lds_states, T.entry_bytes, T.unique, T.unique < kSeltallyLdsIds ? T.unique : kSeltallyLdsIds };
+    set->d_unique_of_pattern = (const uint32_t*)(mem + at_map);
+    set->info = sx_tally_set_info{ T.n_patterns, T.unique, T.states, T.classes, T.nocase, T.entry_bytes,
+                                   (uint64_t)(sizeof T.map + T.next.size() + 2 * per_state + (size_t)T.n_patterns * sizeof(uint32_t)), T.lds_states, 0 };
+    set->unique_of_pattern = std::move(T.unique_of_pattern);
+    if (sx_tally_set_reset(set) != SX_OK) { ctx->set_err("tally set: the counters could not be reset"); sx_tally_set_free(set); return SX_E_HIP; }
+    *out = set;
+    return SX_OK;
+}
+
+int sx_tally_set_info_get(const sx_tally_set* set, sx_tally_set_info* out) {
+    if (!set || !out) return SX_E_INVALID;
+    *out = set->info;
+    return SX_OK;
+}
+
+void sx_tally_set_free(sx_tally_set* set) {
+    if (!set) return;
+    (void)hipFree(set->mem);
+    delete set;
+}
+
+// The tally where the findings lie (sx_seltally_dev.hip): the source is checked as a whole, then one kernel per segment, each with the
+// ordinal of its first record, on the selections' stream, and one wait.  Only the set's counters are written.
+int sx_result_tally_device(sx_ctx* ctx, const sx_result* r, sx_tally_set* set, uint64_t ordinal_base, uint64_t* n_findings) {
+    if (n_findings) *n_findings = 0;
+    if (!ctx || !r || !set) return SX_E_INVALID;
+    if (ctx->host_only) { ctx->set_err("host-only context: no device tally"); return SX_E_STATE; }
+    if (set->device != ctx->device) { ctx->set_err("the tally set lies on another device"); return SX_E_INVALID; }
+    { const int rc = result_on_device(ctx, r, "count on the host"); if (rc != SX_OK) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    uint64_t walked = 0;
+    for (const MissionFindings& s : r->r.segs) {
+        SeltallyParams p;
+        memset(&p, 0, sizeof p);
+        p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
+        p.ordinal = ordinal_base + walked;
+        p.set = set->dev;
+        HIP_TRY(ctx, seltally_launch(p, st));
+        walked += s.ext_nf;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (n_findings) *n_findings = walked;
+    return SX_OK;
+}
+
+int sx_tally_set_read(const sx_tally_set* set, uint64_t* hits, uint64_t* first, uint32_t n_patterns) {
+    if (!set || n_patterns != set->info.n_patterns) return SX_E_INVALID;
+    if (hipSetDevice(set->device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    std::vector<uint64_t> u(set->dev.unique);
+    for (int k = 0; k < 2; k++) {
+        uint64_t* out = k ? first : hits;
+        if (!out) continue;
+        if (hipMemcpy(u.data(), k ? set->dev.first : set->dev.hits, u.size() * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+        for (uint32_t p = 0; p < n_patterns; p++) out[p] = u[set->unique_of_pattern[p]];
+    }
+    return SX_OK;
+}
+
+int sx_tally_set_counters_device(const sx_tally_set* set, const uint64_t** d_hits, const uint64_t** d_first,
+                                 const uint32_t** d_unique_of_pattern, uint32_t* unique) {
+    if (!set) return SX_E_INVALID;
+    if (d_hits) *d_hits = set->dev.hits;
+    if (d_first) *d_first = set->dev.first;
+    if (d_unique_of_pattern) *d_unique_of_pattern = set->d_unique_of_pattern;
+    if (unique) *unique = set->dev.unique;
+    return SX_OK;
 }
 
 int sx_get_stats(const sx_ctx* ctx, sx_stats* out) {

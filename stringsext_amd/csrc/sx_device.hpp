@@ -287,6 +287,10 @@ hipError_t selre_launch_match(const SelectParams& P, const SelreDevice& re, uint
 hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreDevice* re, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes);
 size_t select_place_scratch_bytes(uint64_t n_sel);
 hipError_t select_place(const SelectParams& P, void* out_recs, uint64_t n_sel, uint8_t* out_arena, void* scratch, size_t scratch_bytes, hipStream_t stream);
+// The keyword tally on the device (sx_seltally_dev.hip, SeltallyParams: sx_seltally_core.hpp), a segment at a time: seltally_kernel adds
+// the segment's hits to the set's counters; nothing else is written, and the counters are valid once `stream` has got there
+struct SeltallyParams;
+hipError_t seltally_launch(const SeltallyParams& P, hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
 hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit

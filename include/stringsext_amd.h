@@ -566,8 +566,8 @@ int  sx_result_select_set_device(sx_ctx* ctx, const sx_result* r, const sx_selec
  *   ^ or $ in mid-pattern                 legal: (^a|b)c, a$|b; a^b is legal and matches nothing
  *   every other backslash + alphanumeric (\b \B \A \Z \1 \e ...)  refused
  * Refused means SX_E_INVALID, and sx_last_error names the pattern's index, the byte offset and the reason.  Not in the language:
- * Unicode-aware classes and folding ([а-я] is a byte class), \b, lookaround, back-references, captures, where the match lies, which
- * pattern matched.
+ * Unicode-aware classes and folding ([а-я] is a byte class), \b, lookaround, back-references, captures, which pattern matched.
+ * (Where the matches lie: sx_result_extract_regex_device, below.)
  * flags: 0 or SX_SELECT_ASCII_NOCASE — the fold is compiled into the set, and it is re.IGNORECASE on a bytes pattern: a literal
  * letter matches both cases, a class holds a letter's other case too and negation applies after that ([Z-a] matches z and A,
  * [^Z-a] matches neither); no byte >= 0x80 is folded.
@@ -603,6 +603,56 @@ int  sx_select_regex_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_
 int  sx_select_regex_info_get(const sx_select_regex* re, sx_select_regex_info* out);
 void sx_select_regex_free(sx_select_regex* re);
 int  sx_result_select_regex_device(sx_ctx* ctx, const sx_result* r, const sx_select_regex* re, uint32_t flags, sx_result** out);
+
+/* The regex MATCHES of a result whose segments ALL lie in HBM, cut out where they lie (csrc/sx_extract_dev.hip) — `grep -oE -f patterns`
+ * over the string part of the lines: the URLs, e-mail addresses, dotted quads themselves, not the lines that hold them.  The three
+ * selections answer WHETHER a finding's string holds something; this answers WHERE, and yields a new device-resident result whose
+ * findings are the matches, back to back in HBM, which prints, downloads, selects and tallies like any other.
+ * PATTERNS AND FLAGS.  An extract set holds 1..SX_SELECT_REGEX_MAX_PATTERNS patterns.  The language is exactly the regex set's, above:
+ * the same refusals, the same limits (SX_SELECT_REGEX_MAX_*, the bound on the construction's memory), the same error texts; flags: 0 or
+ * SX_SELECT_ASCII_NOCASE, compiled into the set.  Lazy quantifiers are accepted and ignored: the longest match is taken.
+ * sx_extract_regex_create builds, on the host, an ANCHORED minimal DFA (csrc/sx_extract_build.hpp: the regex set's parser and NFA, no
+ * re-entry in front of later bytes, one start state for offset 0 and one for every later offset, per state whether a match may end
+ * there) and puts its table into HBM on the context's device.  It is an object of its own: a regex set compiles nothing more than
+ * before.  It owns its device memory and does not depend on the context's lifetime: it may be freed before or after sx_destroy, and
+ * used with any context on the same HIP device (another device: SX_E_INVALID).  Errors as sx_select_regex_create's; *out = NULL on
+ * every error.  sx_extract_regex_info_get: what was built — table_bytes (states * classes * 2) lie in HBM, the rows of the first
+ * lds_states states are what the kernels keep in LDS, the other rows they read through L2.
+ * MATCHING.  For a finding with the string s of n bytes the matches are found as `grep -oE` finds them — leftmost start, longest end
+ * over all patterns, non-overlapping, non-empty:
+ *   o = 0; while o < n: let e be the largest end in (o, n] such that some pattern matches exactly s[o, e);
+ *                       if there is such an e: emit (o, e) and o = e; otherwise o = o + 1.
+ * `^` holds only at offset 0 of the string and `$` only at offset n, for every match in the string, not only the first: nothing
+ * outside the record's own bytes is looked at.  Patterns that can match the empty string (a*) are legal; empty matches are never
+ * emitted.  A match never spans two findings.
+ * OUTPUT.  Every match gives one output record, in source order, and in offset order within a finding.  The output record is the
+ * source record unchanged except for str_off and str_len: `position`, the precision, completes_previous, mission_id and the rest are
+ * the FINDING's, not the match's — the byte offset of a match in the input cannot be derived from an offset into the UTF-8 string of
+ * a UTF-16 finding, and is not given.
+ * sx_result_extract_regex_device: flags 0; output layout, empty result, memory and lifetime follow the contract of
+ * sx_result_select_regex_device, word for word: one output segment per source segment that has at least one match, source order
+ * kept; the record type (sx_finding16 / sx_finding) and the sx_segment_info are the source segment's; a segment is [records][strings],
+ * 256-byte aligned, its strings back to back in record order (str_off[0] == 0, str_off[i + 1] == str_off[i] + str_len[i], arena_len ==
+ * sum(str_len)); no match anywhere: *out is the empty result.  The source is read, never moved.  The call writes the same two
+ * selection blocks and counts as a selection for "valid until the SECOND selection after the one that made it".  The sources
+ * accepted are exactly those sx_print_findings_device accepts, any selection and any earlier extraction among them.  The output may
+ * have MORE records than the source; its strings never have more bytes than the source's.  SX_E_STATE wherever
+ * sx_print_findings_device would refuse the source; SX_E_NOMEM if the block cannot be had; SX_E_INVALID for a NULL pointer, a flag, a
+ * set on another device, or — with sx_last_error text — a segment whose match count does not fit the 32-bit per-segment counters.
+ * COST.  A byte that cannot begin a match costs one table look-up.  A walk that runs far and then fails is repeated from the next
+ * start: the worst case is QUADRATIC in a string's length (a*b over a long run of a).  There is no linear-time guarantee.
+ * Not built: which pattern matched, captures, the input-byte positions of the matches. */
+typedef struct sx_extract_regex sx_extract_regex;
+typedef struct sx_extract_regex_info {
+    uint32_t n_patterns, states, classes, nocase;
+    uint64_t table_bytes;   /* in HBM */
+    uint32_t lds_states;    /* states whose rows the kernels keep in LDS */
+    uint32_t reserved;
+} sx_extract_regex_info;
+int  sx_extract_regex_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_extract_regex** out);
+int  sx_extract_regex_info_get(const sx_extract_regex* ex, sx_extract_regex_info* out);
+void sx_extract_regex_free(sx_extract_regex* ex);
+int  sx_result_extract_regex_device(sx_ctx* ctx, const sx_result* r, const sx_extract_regex* ex, uint32_t flags, sx_result** out);
 
 /* The keyword TALLY of a result whose segments ALL lie in HBM: which entries of an indicator list occur in the findings' strings, how
  * often, and where first — what the three selections throw away —, counted where the findings lie (csrc/sx_seltally_dev.hip), one pass

@@ -43,7 +43,8 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_result_count", "sx_result_segments", "sx_result_segment", "sx_result_segment_device", "sx_result_findings", "sx_result_arena",
            "sx_result_free", "sx_print_findings", "sx_print_findings_device", "sx_result_select_device",
            "sx_select_set_create", "sx_select_set_info_get", "sx_select_set_free", "sx_result_select_set_device", "sx_select_regex_create", "sx_select_regex_info_get", "sx_select_regex_free",
-           "sx_result_select_regex_device", "sx_tally_set_create", "sx_tally_set_info_get", "sx_tally_set_free", "sx_tally_set_reset",
+           "sx_result_select_regex_device", "sx_extract_regex_create", "sx_extract_regex_info_get", "sx_extract_regex_free",
+           "sx_result_extract_regex_device", "sx_tally_set_create", "sx_tally_set_info_get", "sx_tally_set_free", "sx_tally_set_reset",
            "sx_result_tally_device", "sx_tally_set_read", "sx_tally_set_counters_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
@@ -183,6 +184,11 @@ class SelectRegexInfo(C.Structure):   # sx_select_regex_info
                 ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32), ("end_states", C.c_uint32)]
 
 
+class ExtractRegexInfo(C.Structure):   # sx_extract_regex_info
+    _fields_ = [("n_patterns", C.c_uint32), ("states", C.c_uint32), ("classes", C.c_uint32), ("nocase", C.c_uint32),
+                ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class TallySetInfo(C.Structure):   # sx_tally_set_info
     _fields_ = [("n_patterns", C.c_uint32), ("unique", C.c_uint32), ("states", C.c_uint32), ("classes", C.c_uint32),
                 ("nocase", C.c_uint32), ("entry_bytes", C.c_uint32), ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32),
@@ -270,6 +276,10 @@ def lib():
     L.sx_select_regex_info_get.argtypes = [vp, C.POINTER(SelectRegexInfo)]
     L.sx_select_regex_free.argtypes, L.sx_select_regex_free.restype = [vp], None
     L.sx_result_select_regex_device.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.sx_extract_regex_create.argtypes = [vp, C.POINTER(Pattern), C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.sx_extract_regex_info_get.argtypes = [vp, C.POINTER(ExtractRegexInfo)]
+    L.sx_extract_regex_free.argtypes, L.sx_extract_regex_free.restype = [vp], None
+    L.sx_result_extract_regex_device.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(vp)]
     L.sx_tally_set_create.argtypes = [vp, C.POINTER(Pattern), C.c_uint32, C.c_uint32, C.POINTER(vp)]
     L.sx_tally_set_info_get.argtypes = [vp, C.POINTER(TallySetInfo)]
     L.sx_tally_set_free.argtypes, L.sx_tally_set_free.restype = [vp], None
@@ -411,7 +421,9 @@ class Result:
         `patterns` may also be a PatternSet (Scanner.pattern_set: a compiled keyword list of up to 65536 patterns, grep -F -f): the
         same selection by sx_result_select_set_device; the fold belongs to the set then, and ignore_case=True raises ValueError.
         Or a RegexSet (Scanner.regex_set: up to 64 byte regular expressions, grep -E -f): sx_result_select_regex_device, with the
-        same rule for the fold."""
+        same rule for the fold.  An ExtractSet is no selection (extract_device takes it): TypeError."""
+        if isinstance(patterns, ExtractSet):
+            raise TypeError("select_device takes patterns, a PatternSet or a RegexSet; an ExtractSet goes to extract_device")
         if isinstance(patterns, RegexSet):
             if ignore_case:
                 raise ValueError("ignore_case belongs to the RegexSet: Scanner.regex_set(patterns, ignore_case=True)")
@@ -440,6 +452,25 @@ class Result:
         flags = (SX_SELECT_ASCII_NOCASE if ignore_case else 0) | (SX_SELECT_INVERT if invert else 0)
         out = C.c_void_p()
         self._s._chk(lib().sx_result_select_device(self._s.h, self.h, arr, len(pats), flags, C.byref(out)))
+        return Result(self._s, out)
+
+    def extract_device(self, extract_set):
+        """The regex MATCHES in this Result's strings, cut out on the device (sx_result_extract_regex_device; `extract_set`: an
+        ExtractSet, Scanner.extract_set) — `grep -oE` over the strings: per finding the leftmost, longest, non-overlapping, non-empty
+        matches, each one a finding of the new Result, which is the source's record with another str_off and str_len (`position` and
+        the rest stay the finding's).  The new Result lies on the device like a selection — strings back to back, possibly MORE
+        findings than this one has —, counts as one for "valid until the second select_device() after this one", and
+        device_segments(), printed_device(), select_device(), tally_device(), extract_device() and the host accessors take it.  This
+        Result is not moved.  Raises TypeError for anything but an ExtractSet (a RegexSet selects, it does not extract), SxError
+        SX_E_STATE wherever printed_device() would refuse this Result."""
+        if not isinstance(extract_set, ExtractSet):
+            raise TypeError("extract_device takes an ExtractSet (Scanner.extract_set)")
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        if not extract_set.h:
+            raise SxError(SX_E_INVALID, "the ExtractSet has been freed")
+        out = C.c_void_p()
+        self._s._chk(lib().sx_result_extract_regex_device(self._s.h, self.h, extract_set.h, 0, C.byref(out)))
         return Result(self._s, out)
 
     def tally_device(self, tally, ordinal_base=0):
@@ -513,6 +544,34 @@ class RegexSet:
     def free(self):
         if self.h:
             lib().sx_select_regex_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ExtractSet:
+    """Byte regular expressions compiled for the extraction on the device (sx_extract_regex_create; Scanner.extract_set makes it):
+    Result.extract_device() takes it, on result after result.  It owns its device memory: free() it before or after the Scanner's
+    close()."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    def info(self):
+        """sx_extract_regex_info as a dict: n_patterns, states, classes, nocase, table_bytes (in HBM), lds_states"""
+        i = ExtractRegexInfo()
+        rc = lib().sx_extract_regex_info_get(self.h, C.byref(i))
+        if rc != SX_OK:
+            raise SxError(rc, "the ExtractSet has been freed")
+        return {k: getattr(i, k) for k, _ in ExtractRegexInfo._fields_ if k != "reserved"}
+
+    def free(self):
+        if self.h:
+            lib().sx_extract_regex_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -638,6 +697,16 @@ class Scanner:
         out = C.c_void_p()
         self._chk(lib().sx_select_regex_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
         return RegexSet(out)
+
+    def extract_set(self, patterns, ignore_case=False):
+        """sx_extract_regex_create: `patterns` (the language and the limits of regex_set) compiled into one anchored DFA in HBM on
+        this Scanner's device, for Result.extract_device().  ignore_case: re.IGNORECASE on a bytes pattern, compiled in.  A refused
+        pattern raises SxError (SX_E_INVALID) whose text names the pattern's index, the offset and the reason."""
+        pats = [bytes(p) for p in patterns]
+        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        out = C.c_void_p()
+        self._chk(lib().sx_extract_regex_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        return ExtractSet(out)
 
     def scan(self, data, file_id=-1, is_last=False):
         """sx_scan: replaces the loop src/main.rs:153-168 for one chunk held in host memory."""

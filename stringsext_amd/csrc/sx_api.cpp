@@ -7,6 +7,8 @@
 #include "sx_selset_core.hpp"
 #include "sx_selre_build.hpp"
 #include "sx_selre_core.hpp"
+#include "sx_extract_build.hpp"
+#include "sx_extract_core.hpp"
 #include "sx_seltally_build.hpp"
 #include "sx_seltally_core.hpp"
 
@@ -26,6 +28,14 @@ struct sx_select_regex {
     uint8_t* mem = nullptr;
     SelreDevice dev{};
     sx_select_regex_info info{};
+};
+
+// sx_extract_regex_create: regular expressions compiled for the extraction; `mem` as a set's
+struct sx_extract_regex {
+    int device = 0;
+    uint8_t* mem = nullptr;
+    ExtractDevice dev{};
+    sx_extract_regex_info info{};
 };
 
 // sx_tally_set_create: a keyword list compiled for the tally; `mem` = [the class map][the table][own][dict][pattern -> unique id]
@@ -765,7 +775,9 @@ static int grow_device(sx_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t bytes, 
 // grep where the findings lie (sx_select_dev.hip), for the three entry points, whose arguments are checked: pass 1 of every segment —
 // select_match_kernel with `patterns`, selset_match_kernel with the compiled `set`, or selre_match_kernel with the compiled `re` —, one wait for the segments' totals, the
 // selection block, pass 2 of every segment that has selected findings, one more wait.  The source is read, never moved.
-static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, const SelsetDevice* set, const SelreDevice* re, uint32_t flags, sx_result** out) {
+// grep -o (sx_extract_dev.hip), for the fourth: with the compiled `ex` the two passes are extract_measure and extract_place, an output
+// record is a match, not a finding, and a segment may get more records than it had; the blocks, their turns and the epochs are the same.
+static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, const SelsetDevice* set, const SelreDevice* re, const ExtractDevice* ex, uint32_t flags, sx_result** out) {
     if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
     { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
     // the block this call writes: a source that lies there was made two selections ago
@@ -776,14 +788,25 @@ static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* p
     hipStream_t st = ctx->post_stream;
     const size_t ns = r->r.segs.size();
     uint64_t scratch = 0;
-    for (const MissionFindings& s : r->r.segs) scratch += select_scratch_bytes(s.ext_nf);
+    for (const MissionFindings& s : r->r.segs) scratch += ex ? extract_scratch_bytes(s.ext_nf) : select_scratch_bytes(s.ext_nf);
     { const int rc = grow_device(ctx, &ctx->d_select_scratch, &ctx->d_select_scratch_cap, scratch, "wavefront tables"); if (rc != SX_OK) return rc; }
-    std::vector<SelectParams> P(ns);
+    std::vector<SelectParams> P(ex ? 0 : ns);
+    std::vector<ExtractParams> X(ex ? ns : 0);
     std::vector<const uint32_t*> d_count(ns);
-    std::vector<const uint64_t*> d_bytes(ns);
+    std::vector<const uint64_t*> d_count64(ns), d_bytes(ns);
     uint64_t at = 0;
     for (size_t i = 0; i < ns; i++) {
         const MissionFindings& s = r->r.segs[i];
+        if (ex) {
+            ExtractParams& x = X[i];
+            memset(&x, 0, sizeof x);
+            x.recs = s.dev_copy; x.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); x.n = s.ext_nf; x.packed = s.packed ? 1u : 0u;
+            x.ex = *ex;
+            const size_t bytes = extract_scratch_bytes(s.ext_nf);
+            HIP_TRY(ctx, extract_measure(&x, ctx->d_select_scratch + at, bytes, st, &d_count64[i], &d_bytes[i]));
+            at += bytes;
+            continue;
+        }
         SelectParams& p = P[i];
         memset(&p, 0, sizeof p);
         p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
@@ -797,14 +820,19 @@ static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* p
     std::vector<uint64_t> n_sel(ns), b_sel(ns), base(ns);
     uint64_t block = 0, scratch2 = 0;
     for (size_t i = 0; i < ns; i++) {
-        uint32_t c = 0;
-        HIP_TRY(ctx, hipMemcpy(&c, d_count[i], sizeof c, hipMemcpyDeviceToHost));
+        uint64_t c = 0;
+        if (ex) HIP_TRY(ctx, hipMemcpy(&c, d_count64[i], sizeof c, hipMemcpyDeviceToHost));
+        else { uint32_t c32 = 0; HIP_TRY(ctx, hipMemcpy(&c32, d_count[i], sizeof c32, hipMemcpyDeviceToHost)); c = c32; }
         HIP_TRY(ctx, hipMemcpy(&b_sel[i], d_bytes[i], sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (c >= 0xFFFFFFFFull) {      // (an extraction: a selection has no more records than its source)
+            ctx->set_err("segment " + std::to_string(i) + " has " + std::to_string(c) + " matches: more than the 32-bit counters of a segment hold");
+            return SX_E_INVALID;
+        }
         n_sel[i] = c;
         if (!c) continue;
         base[i] = block;
         block += (c * r->r.segs[i].rec_size() + b_sel[i] + 255) / 256 * 256;
-        scratch2 = std::max<uint64_t>(scratch2, select_place_scratch_bytes(c));
+        scratch2 = std::max<uint64_t>(scratch2, ex ? extract_place_scratch_bytes(c) : select_place_scratch_bytes(c));
     }
     // from here on the call counts: the block of the selection before the last one is written again
     ctx->select_epoch[slot]->fetch_add(1);
@@ -818,7 +846,8 @@ static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* p
             if (!n_sel[i]) continue;
             const MissionFindings& s = r->r.segs[i];
             uint8_t* recs = ctx->d_select[slot] + base[i];
-            HIP_TRY(ctx, select_place(P[i], recs, n_sel[i], recs + n_sel[i] * s.rec_size(), ctx->d_select_scratch2, select_place_scratch_bytes(n_sel[i]), st));
+            if (ex) HIP_TRY(ctx, extract_place(X[i], recs, n_sel[i], recs + n_sel[i] * s.rec_size(), ctx->d_select_scratch2, extract_place_scratch_bytes(n_sel[i]), st));
+            else HIP_TRY(ctx, select_place(P[i], recs, n_sel[i], recs + n_sel[i] * s.rec_size(), ctx->d_select_scratch2, select_place_scratch_bytes(n_sel[i]), st));
             MissionFindings o;
             o.ext_nf = n_sel[i]; o.ext_na = b_sel[i]; o.dev_copy = recs; o.dev_only = true; o.keep_on_device = true;
             o.dev_epoch_ref = ctx->select_epoch[slot]; o.dev_epoch = ctx->select_epoch[slot]->load();
@@ -838,7 +867,7 @@ int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* p
     if (flags & ~(uint32_t)(SX_SELECT_ASCII_NOCASE | SX_SELECT_INVERT)) { ctx->set_err("unknown selection flags"); return SX_E_INVALID; }
     for (int p = 0; p < n_patterns; p++)
         if (!patterns[p].bytes || patterns[p].len < 1 || patterns[p].len > SX_SELECT_MAX_PATTERN_BYTES) { ctx->set_err("a pattern must have 1..64 bytes"); return SX_E_INVALID; }
-    return select_on_device(ctx, r, patterns, n_patterns, nullptr, nullptr, flags, out);
+    return select_on_device(ctx, r, patterns, n_patterns, nullptr, nullptr, nullptr, flags, out);
 }
 
 int sx_select_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_set** out) {
@@ -886,7 +915,7 @@ int sx_result_select_set_device(sx_ctx* ctx, const sx_result* r, const sx_select
     if (flags & ~(uint32_t)SX_SELECT_INVERT) { ctx->set_err("a pattern set is selected with SX_SELECT_INVERT or no flag: the fold is compiled into the set"); return SX_E_INVALID; }
     if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
     if (set->device != ctx->device) { ctx->set_err("the pattern set lies on another device"); return SX_E_INVALID; }
-    return select_on_device(ctx, r, nullptr, 0, &set->dev, nullptr, flags, out);
+    return select_on_device(ctx, r, nullptr, 0, &set->dev, nullptr, nullptr, flags, out);
 }
 
 int sx_select_regex_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_regex** out) {
@@ -934,7 +963,55 @@ int sx_result_select_regex_device(sx_ctx* ctx, const sx_result* r, const sx_sele
     if (flags & ~(uint32_t)SX_SELECT_INVERT) { ctx->set_err("a regex set is selected with SX_SELECT_INVERT or no flag: the fold is compiled into the set"); return SX_E_INVALID; }
     if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
     if (re->device != ctx->device) { ctx->set_err("the regex set lies on another device"); return SX_E_INVALID; }
-    return select_on_device(ctx, r, nullptr, 0, nullptr, &re->dev, flags, out);
+    return select_on_device(ctx, r, nullptr, 0, nullptr, &re->dev, nullptr, flags, out);
+}
+
+int sx_extract_regex_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_extract_regex** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !out) return SX_E_INVALID;
+    ExtractTable T;
+    std::string err;
+    { const int rc = extract_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("extract set: " + err); return rc; } }
+    if (ctx->host_only) { ctx->set_err("host-only context: no device for the extract set"); return SX_E_STATE; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = T.next.size() * sizeof(uint16_t), table = (bytes + 15) / 16 * 16;   // (the kernels copy the LDS rows in 16-byte chunks)
+    uint8_t* mem = nullptr;
+    if (hipMalloc((void**)&mem, sizeof T.map + table) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->set_err("extract set: no device memory for " + std::to_string(sizeof T.map + table) + " bytes of table");
+        return SX_E_NOMEM;
+    }
+    hipError_t e = hipMemcpy(mem, T.map, sizeof T.map, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mem + sizeof T.map, T.next.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(mem); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
+    sx_extract_regex* ex = new (std::nothrow) sx_extract_regex;
+    if (!ex) { (void)hipFree(mem); return SX_E_NOMEM; }
+    ex->device = ctx->device; ex->mem = mem;
+    ex->dev = ExtractDevice{ mem, (const uint16_t*)(mem + sizeof T.map), T.states, T.classes, T.lds_states, T.end_first, T.here_first, T.dead_first, T.start0, T.start1 };
+    ex->info = sx_extract_regex_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)bytes, T.lds_states, 0 };
+    *out = ex;
+    return SX_OK;
+}
+
+int sx_extract_regex_info_get(const sx_extract_regex* ex, sx_extract_regex_info* out) {
+    if (!ex || !out) return SX_E_INVALID;
+    *out = ex->info;
+    return SX_OK;
+}
+
+void sx_extract_regex_free(sx_extract_regex* ex) {
+    if (!ex) return;
+    (void)hipFree(ex->mem);
+    delete ex;
+}
+
+int sx_result_extract_regex_device(sx_ctx* ctx, const sx_result* r, const sx_extract_regex* ex, uint32_t flags, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !ex || !out) return SX_E_INVALID;
+    if (flags) { ctx->set_err("an extraction takes no flag: the fold is compiled into the set"); return SX_E_INVALID; }
+    if (ctx->host_only) { ctx->set_err("host-only context: no device extraction"); return SX_E_STATE; }
+    if (ex->device != ctx->device) { ctx->set_err("the extract set lies on another device"); return SX_E_INVALID; }
+    return select_on_device(ctx, r, nullptr, 0, nullptr, nullptr, &ex->dev, flags, out);
 }
 
 int sx_tally_set_reset(sx_tally_set* set) {

@@ -287,6 +287,16 @@ hipError_t selre_launch_match(const SelectParams& P, const SelreDevice& re, uint
 hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreDevice* re, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes);
 size_t select_place_scratch_bytes(uint64_t n_sel);
 hipError_t select_place(const SelectParams& P, void* out_recs, uint64_t n_sel, uint8_t* out_arena, void* scratch, size_t scratch_bytes, hipStream_t stream);
+// The regex extraction on the device (sx_extract_dev.hip, ExtractParams: sx_extract_core.hpp), a segment at a time, in the shape of the
+// selection's two passes.  extract_measure: pass 1 — fills P's per-record and per-wavefront tables inside `scratch`
+// (extract_scratch_bytes(n), 256-aligned); *count, *bytes = the device words with the number of matches and their bytes, valid once
+// `stream` has got there; extract_place: one record per match to out_recs, the matches' bytes back to back to out_arena (scratch:
+// extract_place_scratch_bytes(n_out), 256-aligned; order_part_strings inside)
+struct ExtractParams;
+size_t extract_scratch_bytes(uint64_t n);
+hipError_t extract_measure(ExtractParams* P, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint64_t** count, const uint64_t** bytes);
+size_t extract_place_scratch_bytes(uint64_t n_out);
+hipError_t extract_place(const ExtractParams& P, void* out_recs, uint64_t n_out, uint8_t* out_arena, void* scratch, size_t scratch_bytes, hipStream_t stream);
 // The keyword tally on the device (sx_seltally_dev.hip, SeltallyParams: sx_seltally_core.hpp), a segment at a time: seltally_kernel adds
 // the segment's hits to the set's counters; nothing else is written, and the counters are valid once `stream` has got there
 struct SeltallyParams;

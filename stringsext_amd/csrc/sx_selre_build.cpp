@@ -1,8 +1,7 @@
-// sx_selre_build.cpp — see sx_selre_build.hpp.  Five steps: the parser (a syntax tree per pattern; whatever Python's `re` would read
-// differently is refused with the offset), the count of the positions with the repeats unrolled (on the tree: nothing is
-// allocated for a pattern that is refused for it), the Thompson NFA, the subset construction over the byte classes that the
-// patterns' byte sets tell apart, Hopcroft's minimisation — which also merges the byte classes whose columns have become equal
-// and leaves one `matched` and one `dead` state at the most — and the numbering.
+// sx_selre_build.cpp — see sx_selre_build.hpp.  Five steps: the parser, the count of the positions with the repeats unrolled, the
+// Thompson NFA (all three in sx_selre_front.hpp, which sx_extract_build.cpp shares), the subset construction over the byte classes
+// that the patterns' byte sets tell apart, Hopcroft's minimisation — which also merges the byte classes whose columns have become
+// equal and leaves one `matched` and one `dead` state at the most — and the numbering.
 #include "sx_selre_build.hpp"
 
 #include <string.h>
@@ -11,380 +10,21 @@
 #include <new>
 #include <unordered_map>
 
+#include "sx_selre_front.hpp"
+
 namespace sx {
 
-namespace {
-
-struct ByteSet {
-    uint64_t w[4] = { 0, 0, 0, 0 };
-    void add(uint32_t x) { w[x >> 6] |= (uint64_t)1 << (x & 63u); }
-    void add_range(uint32_t lo, uint32_t hi) { for (uint32_t x = lo; x <= hi; x++) add(x); }
-    bool has(uint32_t x) const { return (w[x >> 6] >> (x & 63u)) & 1u; }
-    void join(const ByteSet& o) { for (int i = 0; i < 4; i++) w[i] |= o.w[i]; }
-    void negate() { for (int i = 0; i < 4; i++) w[i] = ~w[i]; }
-    bool operator==(const ByteSet& o) const { return !memcmp(w, o.w, sizeof w); }
-};
-
-struct Refused { uint32_t off; const char* why; };
-
-enum NodeKind : uint8_t { kSet, kBol, kEol, kEmpty, kCat, kAlt, kRep };
-constexpr uint32_t kInf = 0xFFFFFFFFu;
-struct Node {
-    NodeKind kind;
-    uint32_t set = 0;              // kSet: index into the sets
-    uint32_t lo = 0, hi = 0;       // kRep: the bounds, hi == kInf: none
-    std::vector<uint32_t> kids;    // kCat, kAlt: all; kRep: one
-};
-
-bool is_alnum(uint32_t x) { return x - '0' < 10u || (x | 0x20u) - 'a' < 26u; }
-int hex_of(uint32_t x) { return x - '0' < 10u ? (int)(x - '0') : (x | 0x20u) - 'a' < 6u ? (int)((x | 0x20u) - 'a' + 10) : -1; }
-
-// \d \w \s and their complements; false: `x` is no shorthand
-bool shorthand(uint32_t x, ByteSet* out) {
-    ByteSet s;
-    switch (x) {
-    case 'd': case 'D': s.add_range('0', '9'); break;
-    case 'w': case 'W': s.add_range('0', '9'); s.add_range('A', 'Z'); s.add_range('a', 'z'); s.add('_'); break;
-    case 's': case 'S': s.add(' '); s.add_range('\t', '\r'); break;
-    default: return false;
-    }
-    if (!(x & 0x20u)) s.negate();
-    *out = s;
-    return true;
-}
-
-struct Parser {
-    const uint8_t* p;
-    uint32_t len, at = 0;
-    bool nocase;
-    std::vector<Node>& nodes;
-    std::vector<ByteSet>& sets;
-
-    uint32_t node(Node&& n) { nodes.push_back(std::move(n)); return (uint32_t)nodes.size() - 1; }
-    uint32_t leaf(NodeKind k) { Node n; n.kind = k; return node(std::move(n)); }
-    uint32_t set_leaf(ByteSet s, bool negated) {
-        if (nocase)
-            for (uint32_t x = 'a'; x <= 'z'; x++)
-                if (s.has(x) || s.has(x - 32)) { s.add(x); s.add(x - 32); }
-        if (negated) s.negate();
-        uint32_t i = 0;
-        while (i < sets.size() && !(sets[i] == s)) i++;
-        if (i == sets.size()) sets.push_back(s);
-        Node n; n.kind = kSet; n.set = i;
-        return node(std::move(n));
-    }
-
-    // behind a backslash (at: the byte behind it): one byte, or a shorthand's set (*is_set)
-    uint32_t escape(ByteSet* set, bool* is_set) {
-        *is_set = false;
-        if (at >= len) throw Refused{ at - 1, "a backslash at the end of the pattern" };
-        const uint32_t x = p[at++];
-        if (!is_alnum(x)) return x;
-        switch (x) {
-        case 't': return '\t';
-        case 'n': return '\n';
-        case 'r': return '\r';
-        case 'f': return '\f';
-        case 'v': return '\v';
-        case 'x': {
-            if (at + 2 > len || hex_of(p[at]) < 0 || hex_of(p[at + 1]) < 0) throw Refused{ at - 2, "\\x needs two hex digits" };
-            const uint32_t v = (uint32_t)(hex_of(p[at]) * 16 + hex_of(p[at + 1]));
-            at += 2;
-            return v;
-        }
-        default: break;
-        }
-        if (shorthand(x, set)) { *is_set = true; return 0; }
-        throw Refused{ at - 2, "an escape that is not supported (of backslash + letter or digit only \\t \\n \\r \\f \\v \\xHH \\d \\D \\w \\W \\s \\S are)" };
-    }
-
-    // behind '['
-    uint32_t klass() {
-        const uint32_t open = at - 1;
-        ByteSet s;
-        bool negated = false;
-        if (at < len && p[at] == '^') { negated = true; at++; }
-        if (at < len && p[at] == ']') throw Refused{ at, "']' directly behind '[' or '[^': escape it" };
-        for (;;) {
-            if (at >= len) throw Refused{ open, "a class without its ']'" };
-            uint32_t x = p[at++];
-            if (x == ']') break;
-            if (x == '[') throw Refused{ at - 1, "an unescaped '[' inside a class" };
-            ByteSet sh; bool is_set = false;
-            const uint32_t item = at - 1;
-            if (x == '\\') x = escape(&sh, &is_set);
-            if (at + 1 < len && p[at] == '-' && p[at + 1] != ']') {     // a range (a '-' in front of ']' is a literal)
-                if (is_set) throw Refused{ item, "a shorthand class as a range end" };
-                at++;
-                uint32_t y = p[at++];
-                const uint32_t hi_at = at - 1;
-                if (y == '[') throw Refused{ hi_at, "an unescaped '[' inside a class" };
-                bool y_set = false;
-                if (y == '\\') y = escape(&sh, &y_set);
-                if (y_set) throw Refused{ hi_at, "a shorthand class as a range end" };
-                if (x > y) throw Refused{ item, "a range whose ends are in the wrong order" };
-                s.add_range(x, y);
-            } else if (is_set) s.join(sh);
-            else s.add(x);
-        }
-        return set_leaf(s, negated);
-    }
-
-    // behind '{' (at: the byte behind it): the bounds
-    void bounds(uint32_t* lo, uint32_t* hi) {
-        const uint32_t open = at - 1;
-        auto number = [&](uint32_t* v) {
-            uint32_t digits = 0; *v = 0;
-            while (at < len && (uint32_t)p[at] - '0' < 10u) { if (*v < 100000u) *v = *v * 10 + ((uint32_t)p[at] - '0'); at++; digits++; }
-            return digits != 0;
-        };
-        const bool has_lo = number(lo);
-        bool comma = false, has_hi = false;
-        if (at < len && p[at] == ',') { comma = true; at++; has_hi = number(hi); }
-        if (at >= len || p[at] != '}' || (!has_lo && !has_hi)) throw Refused{ open, "a '{' that does not begin a bound {m}, {m,}, {m,n} or {,n}: escape it" };
-        at++;
-        if (!has_lo) *lo = 0;
-        if (!comma) *hi = *lo;
-        else if (!has_hi) *hi = kInf;
-        if (*lo > SX_SELECT_REGEX_MAX_REPEAT || (*hi != kInf && *hi > SX_SELECT_REGEX_MAX_REPEAT)) throw Refused{ open, "a repeat count above SX_SELECT_REGEX_MAX_REPEAT (255)" };
-        if (*hi != kInf && *lo > *hi) throw Refused{ open, "a bound {m,n} with m > n" };
-    }
-
-    uint32_t alternation() {
-        Node alt; alt.kind = kAlt;
-        for (;;) {
-            Node cat; cat.kind = kCat;
-            while (at < len && p[at] != '|' && p[at] != ')') cat.kids.push_back(piece());
-            alt.kids.push_back(cat.kids.empty() ? leaf(kEmpty) : cat.kids.size() == 1 ? cat.kids[0] : node(std::move(cat)));
-            if (at < len && p[at] == '|') { at++; continue; }
-            break;
-        }
-        return alt.kids.size() == 1 ? alt.kids[0] : node(std::move(alt));
-    }
-
-    uint32_t piece() {
-        const uint32_t start = at;
-        const uint32_t x = p[at++];
-        uint32_t atom;
-        bool anchor = false;
-        switch (x) {
-        case '(': {
-            if (at < len && p[at] == '?') {
-                if (at + 1 < len && p[at + 1] == ':') at += 2;
-                else throw Refused{ start, "a group that begins with (? and is not (?:" };
-            }
-            atom = alternation();
-            if (at >= len || p[at] != ')') throw Refused{ start, "a '(' without its ')'" };
-            at++;
-            break;
-        }
-        case '[': atom = klass(); break;
-        case '.': { ByteSet s; s.add('\n'); atom = set_leaf(s, true); break; }
-        case '^': atom = leaf(kBol); anchor = true; break;
-        case '$': atom = leaf(kEol); anchor = true; break;
-        case '*': case '+': case '?': throw Refused{ start, "a quantifier with nothing in front of it" };
-        case '{': throw Refused{ start, "a '{' with nothing to repeat in front of it: escape it" };
-        case '\\': {
-            ByteSet s; bool is_set = false;
-            const uint32_t v = escape(&s, &is_set);
-            if (!is_set) s.add(v);
-            atom = set_leaf(s, false);
-            break;
-        }
-        default: { ByteSet s; s.add(x); atom = set_leaf(s, false); break; }
-        }
-        if (at >= len) return atom;
-        uint32_t lo, hi;
-        const uint32_t q = at;
-        switch (p[at]) {
-        case '*': lo = 0; hi = kInf; at++; break;
-        case '+': lo = 1; hi = kInf; at++; break;
-        case '?': lo = 0; hi = 1; at++; break;
-        case '{': at++; bounds(&lo, &hi); break;
-        default: return atom;
-        }
-        if (anchor) throw Refused{ q, "a quantifier on '^' or '$'" };
-        if (at < len && p[at] == '?') at++;      // lazy: only existence is asked
-        if (at < len && (p[at] == '*' || p[at] == '+' || p[at] == '?' || p[at] == '{')) throw Refused{ at, "a second quantifier" };
-        Node rep; rep.kind = kRep; rep.lo = lo; rep.hi = hi; rep.kids.push_back(atom);
-        return node(std::move(rep));
-    }
-
-    uint32_t pattern() {
-        const uint32_t root = alternation();
-        if (at < len) throw Refused{ at, "a ')' without its '('" };     // (alternation stops nowhere else)
-        return root;
-    }
-};
-
-// an upper bound on the NFA nodes that Nfa::build makes of `n`, its repeats unrolled (every leaf and every branch point is one),
-// saturating: x{m,n} is n copies of x and n - m branches, x{m,} max(m, 1) copies — the last one loops — and one branch
-uint64_t unrolled(const std::vector<Node>& nodes, uint32_t n) {
-    const Node& N = nodes[n];
-    constexpr uint64_t kMuch = (uint64_t)1 << 40;
-    uint64_t v = 0;
-    switch (N.kind) {
-    case kSet: case kBol: case kEol: case kEmpty: return 1;
-    case kCat: case kAlt:
-        for (uint32_t k : N.kids) v = std::min(v + unrolled(nodes, k), kMuch);
-        return N.kind == kAlt ? v + N.kids.size() - 1 : v;
-    case kRep: {
-        const uint64_t copies = N.hi == kInf ? std::max<uint32_t>(N.lo, 1) : N.hi, branches = N.hi == kInf ? 1 : N.hi - N.lo;
-        return std::min(std::max<uint64_t>(unrolled(nodes, N.kids[0]) * copies + branches, 1), kMuch);
-    }
-    }
-    return kMuch;
-}
-
-enum NfaKind : uint8_t { nChar, nSplit, nBol, nEol, nAccept };
-struct NfaNode { NfaKind kind; uint32_t set, a, b; };
-
-struct Nfa {
-    std::vector<NfaNode> n;
-    size_t most = 0;     // what the count on the trees allows: more is a fault of the count, not a reason to go on allocating
-    uint32_t add(NfaKind k, uint32_t set, uint32_t a, uint32_t b) {
-        if (n.size() >= most) throw Refused{ 0, "the NFA has more nodes than were counted" };
-        n.push_back(NfaNode{ k, set, a, b });
-        return (uint32_t)n.size() - 1;
-    }
-    // the entry of the nodes that match what tree node `t` matches and go on at `next`
-    uint32_t build(const std::vector<Node>& nodes, uint32_t t, uint32_t next) {
-        const Node& N = nodes[t];
-        switch (N.kind) {
-        case kSet: return add(nChar, N.set, next, 0);
-        case kBol: return add(nBol, 0, next, 0);
-        case kEol: return add(nEol, 0, next, 0);
-        case kEmpty: return next;
-        case kCat:
-            for (size_t k = N.kids.size(); k-- > 0;) next = build(nodes, N.kids[k], next);
-            return next;
-        case kAlt: {
-            uint32_t cur = build(nodes, N.kids.back(), next);
-            for (size_t k = N.kids.size() - 1; k-- > 0;) { const uint32_t one = build(nodes, N.kids[k], next); cur = add(nSplit, 0, one, cur); }
-            return cur;
-        }
-        case kRep: {
-            uint32_t cur = next;
-            if (N.hi == kInf) {      // x* = a branch: x and back, or on; x{m,}, m >= 1 = m times x, the last one entered at x: no copy for the loop
-                const uint32_t loop = add(nSplit, 0, 0, next);
-                const uint32_t body = build(nodes, N.kids[0], loop);
-                n[loop].a = body;
-                cur = N.lo ? body : loop;
-                for (uint32_t k = 1; k < N.lo; k++) cur = build(nodes, N.kids[0], cur);
-                return cur;
-            } else {                 // x{m,n} = m times x, then (x(x(...)?)?)?
-                for (uint32_t k = N.lo; k < N.hi; k++) { const uint32_t body = build(nodes, N.kids[0], cur); cur = add(nSplit, 0, body, next); }
-            }
-            for (uint32_t k = 0; k < N.lo; k++) cur = build(nodes, N.kids[0], cur);
-            return cur;
-        }
-        }
-        return next;
-    }
-};
-
-// what is reached from NFA nodes without a byte: the byte nodes, and whether the string is accepted here whatever follows
-// (`always`) or if it ends here (`at_end`: through a `$`)
-struct Closure { std::vector<uint32_t> chars; bool always = false, at_end = false; };
-
-struct Closer {
-    const Nfa& nfa;
-    std::vector<uint32_t> seen[2];     // by mode: 0 in front of any `$`, 1 behind one
-    uint32_t stamp = 0;
-    std::vector<std::pair<uint32_t, uint32_t>> stack;
-    explicit Closer(const Nfa& f) : nfa(f) { seen[0].assign(f.n.size(), 0); seen[1].assign(f.n.size(), 0); }
-    void run(uint32_t from, bool at_start, Closure* out) {
-        stamp++;
-        stack.clear();
-        stack.push_back({ from, 0 });
-        while (!stack.empty()) {
-            const uint32_t v = stack.back().first, mode = stack.back().second;
-            stack.pop_back();
-            if (seen[mode][v] == stamp) continue;
-            seen[mode][v] = stamp;
-            const NfaNode& N = nfa.n[v];
-            switch (N.kind) {
-            case nChar: if (!mode) out->chars.push_back(v); break;
-            case nSplit: stack.push_back({ N.b, mode }); stack.push_back({ N.a, mode }); break;
-            case nBol: if (at_start) stack.push_back({ N.a, mode }); break;
-            case nEol: stack.push_back({ N.a, 1 }); break;
-            case nAccept: if (mode) out->at_end = true; else out->always = true; break;
-            }
-        }
-        std::sort(out->chars.begin(), out->chars.end());
-    }
-};
-
-struct KeyHash {
-    size_t operator()(const std::vector<uint32_t>& k) const {
-        uint64_t h = 1469598103934665603ull;
-        for (uint32_t v : k) { h ^= v; h *= 1099511628211ull; }
-        return (size_t)h;
-    }
-};
-
-int fail(std::string* err, const std::string& what) { if (err) *err = what; return SX_E_INVALID; }
-
-constexpr uint32_t kEndMark = 0xFFFFFFFFu;               // in a subset's key: it accepts at the end
-constexpr uint64_t kSubsetEntries = (uint64_t)32 << 20;  // the subsets' entries all together: a bound on the construction's memory
-
-}  // namespace
-
 int selre_build(const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, SelreTable* out, std::string* err) {
+    using namespace refront;
     if (!patterns || !out) return fail(err, "a NULL pointer");
-    if (n_patterns < 1 || n_patterns > SX_SELECT_REGEX_MAX_PATTERNS) return fail(err, "n_patterns must be 1..64");
-    if (flags & ~(uint32_t)SX_SELECT_ASCII_NOCASE) return fail(err, "a regex set takes SX_SELECT_ASCII_NOCASE and no other flag");
-    for (uint32_t p = 0; p < n_patterns; p++)
-        if (!patterns[p].bytes || patterns[p].len < 1 || patterns[p].len > SX_SELECT_REGEX_MAX_PATTERN_BYTES)
-            return fail(err, "pattern " + std::to_string(p) + ": a pattern must have 1..1024 bytes and a pointer");
-    const bool nocase = (flags & SX_SELECT_ASCII_NOCASE) != 0;
     try {
-        // 1. the trees
-        std::vector<Node> nodes;
-        std::vector<ByteSet> sets;
-        std::vector<uint32_t> roots;
-        uint64_t positions = 0;
-        for (uint32_t p = 0; p < n_patterns; p++) {
-            Parser ps{ patterns[p].bytes, patterns[p].len, 0, nocase, nodes, sets };
-            try {
-                roots.push_back(ps.pattern());
-            } catch (const Refused& r) {
-                return fail(err, "pattern " + std::to_string(p) + ", offset " + std::to_string(r.off) + ": " + r.why);
-            }
-            // 2. the positions, before anything is unrolled
-            positions += unrolled(nodes, roots.back());
-            if (positions > SX_SELECT_REGEX_MAX_POSITIONS)
-                return fail(err, "pattern " + std::to_string(p) + ": more than SX_SELECT_REGEX_MAX_POSITIONS (65536) positions once the counted repeats are unrolled");
-        }
-        // 3. the NFA: one accept, every pattern an alternative
-        Nfa nfa;
-        nfa.most = (size_t)positions + n_patterns;      // the accept, the patterns' nodes, a branch per pattern but one
-        nfa.n.reserve(nfa.most);
-        uint32_t start = 0;
-        try {
-            const uint32_t accept = nfa.add(nAccept, 0, 0, 0);
-            start = nfa.build(nodes, roots.back(), accept);
-            for (size_t p = roots.size() - 1; p-- > 0;) { const uint32_t one = nfa.build(nodes, roots[p], accept); start = nfa.add(nSplit, 0, one, start); }
-        } catch (const Refused& r) {
-            return fail(err, std::string("internal: ") + r.why);
-        }
-        // the byte classes of the construction: the bytes that no set tells apart
-        uint8_t cls[256] = {};
-        uint32_t K = 1;
-        for (const ByteSet& s : sets) {
-            uint16_t split[256];
-            for (uint32_t c = 0; c < K; c++) split[c] = 0xFFFF;
-            bool in0[256] = {};   // the side of the set that keeps the class's number: its first byte's
-            for (uint32_t x = 0; x < 256; x++) {
-                const uint32_t c = cls[x];
-                if (split[c] == 0xFFFF) { split[c] = (uint16_t)c; in0[c] = s.has(x); continue; }
-                if (s.has(x) == in0[c]) continue;
-                if (split[c] == c) split[c] = (uint16_t)K++;
-                cls[x] = (uint8_t)split[c];
-            }
-        }
-        uint8_t rep[256];
-        for (uint32_t x = 256; x-- > 0;) rep[cls[x]] = (uint8_t)x;
+        // 1. to 3. the trees, the positions, the NFA; the byte classes of the construction
+        Front F;
+        { const int rc = front_build(patterns, n_patterns, flags, &F, err); if (rc != SX_OK) return rc; }
+        const Nfa& nfa = F.nfa;
+        const std::vector<ByteSet>& sets = F.sets;
+        const uint32_t start = F.start, K = F.K;
+        const uint8_t* rep = F.rep;
         // 4. the subsets.  D[s * K + c]; state 0 is the root; `matched` is made when first needed
         Closer closer(nfa);
         std::vector<Closure> after(nfa.n.size());      // behind a byte node: closure(its successor), made when first needed
@@ -466,92 +106,15 @@ int selre_build(const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags,
                                                                       : "the subset construction was stopped at the bound on its memory: its " + std::to_string(keys.size()) + " states so far hold more than 33554432 NFA positions in all");
         const uint32_t n = (uint32_t)keys.size();
         ids.clear(); keys.clear(); after.clear();
-        // 5. Hopcroft: blocks of states that no string tells apart
-        std::vector<uint32_t> elems(n), loc(n), blk(n), bbeg, bend, marked;
-        {
-            uint32_t rejecting = 0;
-            for (uint32_t s = 0; s < n; s++) rejecting += !accepts[s];
-            uint32_t a = 0, b = rejecting;
-            for (uint32_t s = 0; s < n; s++) { const uint32_t at = accepts[s] ? b++ : a++; elems[at] = s; loc[s] = at; }
-            if (rejecting) { bbeg.push_back(0); bend.push_back(rejecting); }
-            if (rejecting < n) { bbeg.push_back(rejecting); bend.push_back(n); }
-            for (uint32_t B = 0; B < bbeg.size(); B++) for (uint32_t i = bbeg[B]; i < bend[B]; i++) blk[elems[i]] = B;
-        }
-        if (bbeg.size() > 1) {
-            // the sources of every (class, target): inv[inv_at[c * n + q] .. inv_at[c * n + q + 1])
-            std::vector<uint32_t> inv_at((size_t)K * n + 1, 0), inv((size_t)K * n);
-            for (uint32_t s = 0; s < n; s++) for (uint32_t c = 0; c < K; c++) inv_at[(size_t)c * n + D[(size_t)s * K + c] + 1]++;
-            for (size_t i = 0; i < (size_t)K * n; i++) inv_at[i + 1] += inv_at[i];
-            {
-                std::vector<uint32_t> fill(inv_at.begin(), inv_at.end() - 1);
-                for (uint32_t s = 0; s < n; s++) for (uint32_t c = 0; c < K; c++) inv[fill[(size_t)c * n + D[(size_t)s * K + c]]++] = s;
-            }
-            std::vector<uint32_t> work{ 0, 1 }, members, touched;
-            marked.assign(2, 0);
-            while (!work.empty()) {
-                const uint32_t A = work.back();
-                work.pop_back();
-                members.assign(elems.begin() + bbeg[A], elems.begin() + bend[A]);
-                for (uint32_t c = 0; c < K; c++) {
-                    touched.clear();
-                    for (uint32_t q : members)
-                        for (uint32_t i = inv_at[(size_t)c * n + q]; i < inv_at[(size_t)c * n + q + 1]; i++) {
-                            const uint32_t p = inv[i], B = blk[p], to = bbeg[B] + marked[B];
-                            if (!marked[B]++) touched.push_back(B);
-                            const uint32_t other = elems[to];
-                            elems[to] = p; elems[loc[p]] = other; loc[other] = loc[p]; loc[p] = to;
-                        }
-                    for (uint32_t B : touched) {
-                        const uint32_t m = marked[B], size = bend[B] - bbeg[B];
-                        marked[B] = 0;
-                        if (m == size) continue;
-                        const uint32_t N = (uint32_t)bbeg.size();     // the smaller part becomes the new block
-                        if (m <= size - m) { bbeg.push_back(bbeg[B]); bend.push_back(bbeg[B] + m); bbeg[B] += m; }
-                        else { bbeg.push_back(bbeg[B] + m); bend.push_back(bend[B]); bend[B] = bbeg[B] + m; }
-                        marked.push_back(0);
-                        for (uint32_t i = bbeg[N]; i < bend[N]; i++) blk[elems[i]] = N;
-                        work.push_back(N);
-                    }
-                }
-            }
-        }
-        const uint32_t M = (uint32_t)bbeg.size();
-        // the quotient, then the byte classes whose columns are equal in every state
-        std::vector<uint32_t> Q((size_t)M * K);
-        std::vector<uint8_t> q_accepts(M);
-        for (uint32_t B = 0; B < M; B++) {
-            const uint32_t s = elems[bbeg[B]];
-            q_accepts[B] = accepts[s];
-            for (uint32_t c = 0; c < K; c++) Q[(size_t)B * K + c] = blk[D[(size_t)s * K + c]];
-        }
-        std::vector<uint32_t> final_of(K), first_of;     // construction class -> final class; final class -> a construction class
-        std::vector<uint64_t> column(K, 1469598103934665603ull);   // (a hash: most pairs of columns differ)
-        for (uint32_t B = 0; B < M; B++) for (uint32_t c = 0; c < K; c++) column[c] = (column[c] ^ Q[(size_t)B * K + c]) * 1099511628211ull;
-        for (uint32_t c = 0; c < K; c++) {
-            uint32_t f = 0;
-            for (; f < first_of.size(); f++) {
-                if (column[c] != column[first_of[f]]) continue;
-                uint32_t B = 0;
-                while (B < M && Q[(size_t)B * K + c] == Q[(size_t)B * K + first_of[f]]) B++;
-                if (B == M) break;
-            }
-            if (f == first_of.size()) first_of.push_back(c);
-            final_of[c] = f;
-        }
+        // 5. Hopcroft: blocks of states that no string tells apart, told apart to begin with by whether they accept
+        Quotient Qt;
+        minimise(n, K, D, accepts, 2, F.cls, &Qt);
+        const uint32_t M = Qt.M;
+        const std::vector<uint32_t>&Q = Qt.Q, &blk = Qt.blk, &first_of = Qt.first_of;
+        const std::vector<uint8_t>& q_accepts = Qt.kind;
         SelreTable T;
-        T.n_patterns = n_patterns; T.nocase = nocase ? 1u : 0u;
-        {   // final classes numbered by their lowest byte
-            std::vector<uint32_t> number(first_of.size(), kSelreNone);
-            uint32_t next_number = 0;
-            for (uint32_t x = 0; x < 256; x++) {
-                const uint32_t f = final_of[cls[x]];
-                if (number[f] == kSelreNone) number[f] = next_number++;
-                T.map[x] = (uint8_t)number[f];
-            }
-            std::vector<uint32_t> by_number(first_of.size());
-            for (uint32_t f = 0; f < first_of.size(); f++) by_number[number[f]] = first_of[f];
-            first_of = by_number;
-        }
+        T.n_patterns = n_patterns; T.nocase = (flags & SX_SELECT_ASCII_NOCASE) ? 1u : 0u;
+        memcpy(T.map, Qt.map, sizeof T.map);
         const uint32_t classes = (uint32_t)first_of.size();
         // breadth first from the root; then: root | ordinary | end-accepting | dead | matched
         std::vector<uint32_t> order, place(M, kSelreNone);

@@ -430,8 +430,8 @@ int               sx_result_segment_device(const sx_result* r, uint64_t i, const
                                            const uint8_t** d_arena, uint64_t* arena_len, int* packed, sx_segment_info* info);
 uint64_t          sx_result_count(const sx_result* r);
 /* The findings come in one or more segments, in print order: a buffer scanned piece by piece adds a segment per
- * piece; a single Mission with millions of runs is replayed in slabs, one segment each (a slab travels to the host while
- * the next is replayed); several Missions with a large output are interleaved on the device in parts of at most 2 GiB of
+ * piece; a Mission with millions of runs — alone, or the busy one among Missions with few — is replayed in slabs, one segment
+ * each (a slab travels to the host while the next is replayed); several Missions with a large output are interleaved on the device in parts of at most 2 GiB of
  * strings, one segment each (str_off has 32 bits).  The segments' memory is pinned host memory the device wrote
  * directly.  Each segment has its own arena: str_off counts from that arena's start.  A segment stored as sx_finding16 records is
  * expanded to sx_finding on its first sx_result_segment() call (a copy in host memory; sx_result_segment_packed() avoids it). */

@@ -441,6 +441,7 @@ void sx_destroy(sx_ctx* ctx) {
         if (ctx->d_select_scratch) (void)hipFree(ctx->d_select_scratch);
         if (ctx->d_select_scratch2) (void)hipFree(ctx->d_select_scratch2);
         for (hipEvent_t e : ctx->merge_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ctx->slab_ev) if (e) (void)hipEventDestroy(e);
         if (ctx->ev_interleaved) (void)hipEventDestroy(ctx->ev_interleaved);
         if (ctx->d_input) (void)hipFree(ctx->d_input);
         if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);

@@ -131,6 +131,9 @@ struct MissionDev {
     const uint32_t* grid_of_scan = nullptr; uint32_t grid_sub = 0; const uint8_t* grid_data = nullptr; uint64_t grid_len = 0;
     uint8_t* h_small = nullptr;        // pinned, kSmallReadBytes: the target of read_back_sync (sx_api.cpp)
     std::vector<hipEvent_t> wave_ev;
+    // the lane-per-region stage B of this Mission's last buffer: runs replayed and bytes written ([records][strings]) — the next
+    // buffer's output is estimated from them (device_replay_mission: slabs next to other Missions)
+    uint64_t last_out_runs = 0, last_out_bytes = 0;
 };
 
 
@@ -158,6 +161,14 @@ struct sx_ctx {
     uint64_t d_cache_cap = 0;
     hipStream_t merge_copy_stream = nullptr;   // device_merge: the copy of one part next to the sort of the following one
     hipEvent_t merge_ev[3] = { nullptr, nullptr, nullptr };
+    // a Mission replayed in slabs (device_replay_mission): its own events on that stream — "pass 2 written" and "copied" of the two
+    // output buffers in turn —, so that device_merge's (merge_async leaves them recorded across buffers) are never re-recorded by it
+    hipEvent_t slab_ev[3] = { nullptr, nullptr, nullptr };
+    // the last slab's copy was left running: slab_copy_drain() before its block is read or given back.  Set by the thread that replays
+    // the Mission in slabs; merge_drain clears it too, which a wave Mission's thread reaches (ensure_rp, ensure_scratch) — the two do not
+    // meet today (slabs next to other Missions exclude merge_async and a wave-predicted neighbour: slabs_next_to_others), and the flag
+    // is atomic so that nothing rests on that
+    std::atomic<bool> slab_copy_pending{ false };
     // device_merge's own memory (two output buffers of merge_out_room bytes each, then the sort's scratch): the copy of a part may
     // still read it while the next piece of the buffer is scanned and replayed (merge_async, scan_common's sequential pieces)
     uint8_t* d_merge = nullptr; uint64_t d_merge_cap = 0, merge_out_room = 0, merge_n_out = 0;
@@ -320,6 +331,7 @@ struct ReplayJob;
 int ensure_copy_stream(sx_ctx* ctx);   // sx_stage_b.cpp
 bool result_stays_on_device(const sx_ctx* ctx, const ReplayJob& job);   // sx_stage_b.cpp: SX_OPT_RESULT_ON_DEVICE, several Missions: this call qualifies
 int merge_drain(sx_ctx* ctx);          // sx_stage_b.cpp: waits for what device_merge left in flight (merge_async)
+int slab_copy_drain(sx_ctx* ctx);      // sx_stage_b.cpp: waits for the copy device_replay_mission left in flight (the last slab's)
 int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_bytes, uint64_t len,
                    const std::vector<uint32_t>& parity, const std::vector<uint64_t>& min_chars, int si,
                    std::vector<RunList>* out, bool cut_into_pieces = false, const ReplayJob* wave_job = nullptr);

@@ -235,7 +235,8 @@ struct MissionFindings {
     bool keep_on_device = false;
     std::shared_ptr<std::atomic<uint64_t>> dev_epoch_ref;
     uint64_t dev_epoch = 0;
-    // further segments of the same mission, in order (a mission replayed in slabs; only with a single mission)
+    // further blocks of the same mission, in order (a mission replayed in slabs: alone, or the busy one next to quiet ones — then
+    // merge_findings interleaves the others' findings across the blocks)
     std::vector<MissionFindings> more;
     // packed: the pinned block holds [ext_nf x sx_finding16][strings] — segments of a result that the device's dense writers
     // produced; `info` says what the records share.  data() expands them into `expanded` on first use (get(i): one record, no copy).

@@ -630,7 +630,11 @@ void merge_findings(std::vector<MissionFindings>& per, const std::shared_ptr<Pin
     out->pool = pool;
     size_t nonempty = 0, which = 0;
     for (size_t k = 0; k < per.size(); k++) if (per[k].count()) { nonempty++; which = k; }
-    auto release = [&](MissionFindings& mf) { if (mf.ext.p && pool) pool->give(mf.ext); mf.ext = {}; };
+    auto release = [&](MissionFindings& mf) {
+        if (mf.ext.p && pool) pool->give(mf.ext);
+        mf.ext = {};
+        for (auto& x : mf.more) { if (x.ext.p && pool) pool->give(x.ext); x.ext = {}; }
+    };
     if (nonempty <= 1) {  // nothing to interleave: hand the storage over as it is
         for (size_t k = 0; k < per.size(); k++) if (!(nonempty == 1 && k == which)) release(per[k]);
         if (nonempty == 1) {
@@ -641,13 +645,69 @@ void merge_findings(std::vector<MissionFindings>& per, const std::shared_ptr<Pin
         }
         return;
     }
+    const uint64_t seg_cap = seg_bytes ? seg_bytes : 0xFFFFFFF0ull;   // (tests: results of several segments without gigabytes of strings)
+    bool in_blocks = false;
+    for (auto& mf : per) in_blocks = in_blocks || !mf.more.empty();
+    if (in_blocks) {
+        // A Mission that was replayed in slabs brings its findings as several blocks, in order (MissionFindings::more): the merge
+        // walks them one behind the other and starts a new segment wherever that Mission enters its next block — what the other
+        // Missions found around a slab cut falls on the side of it where its position puts it.  The strings are copied a stretch at a
+        // time: consecutive findings of one block whose strings lie one behind the other in its arena (they do, as the replay
+        // writes them) go over in one append — millions of findings next to a few of another Mission are a few appends.
+        struct Cursor { std::vector<const MissionFindings*> blocks; size_t b = 0, i = 0; };
+        std::vector<Cursor> cur(per.size());
+        for (size_t k = 0; k < per.size(); k++) {
+            if (per[k].count()) cur[k].blocks.push_back(&per[k]);
+            for (auto& x : per[k].more) if (x.count()) cur[k].blocks.push_back(&x);
+        }
+        auto head = [](Cursor& c) -> const sx_finding* {
+            while (c.b < c.blocks.size() && c.i >= c.blocks[c.b]->count()) { c.b++; c.i = 0; }
+            return c.b < c.blocks.size() ? c.blocks[c.b]->data() + c.i : nullptr;
+        };
+        bool open = false;
+        const char* run_src = nullptr;    // the stretch not yet appended: run_len bytes from run_off of this arena
+        uint64_t run_off = 0, run_len = 0;
+        auto flush = [&]() {
+            if (run_len) out->segs.back().arena.append(run_src + run_off, run_len);
+            run_src = nullptr; run_len = 0;
+        };
+        for (;;) {
+            int best = -1;
+            const sx_finding* bf = nullptr;
+            for (size_t k = 0; k < per.size(); k++) {
+                const sx_finding* f = head(cur[k]);
+                if (!f) continue;
+                if (best < 0 || f->slice_index < bf->slice_index || (f->slice_index == bf->slice_index && f->position < bf->position)) { best = (int)k; bf = f; }
+            }
+            if (best < 0) break;
+            Cursor& c = cur[(size_t)best];
+            const MissionFindings& src = *c.blocks[c.b];
+            const bool next_block = c.i == 0 && c.b > 0;
+            if (!open || next_block || out->segs.back().arena.size() + run_len + bf->str_len > seg_cap) {
+                flush();
+                out->segs.emplace_back();
+                out->segs.back().v.reserve(src.count() - c.i + 64);
+                out->segs.back().arena.reserve(std::min<uint64_t>(seg_cap, src.strings_len() + 4096));
+                open = true;
+            }
+            MissionFindings& m = out->segs.back();
+            if (run_src != src.strings() || bf->str_off != run_off + run_len) { flush(); run_src = src.strings(); run_off = bf->str_off; }
+            sx_finding f = *bf;
+            f.str_off = (uint32_t)(m.arena.size() + run_len);
+            run_len += bf->str_len;
+            m.v.push_back(f);
+            c.i++;
+        }
+        flush();
+        for (auto& mf : per) { release(mf); mf.more.clear(); }
+        return;
+    }
     // One segment normally.  str_off is 32 bits: when the Missions' strings together exceed 4 GiB the findings go out as
     // several segments (in print order, each with its own arena), cut where the running string size would pass 4 GiB
     // (ADVICE, round 1: the offsets used to wrap silently).
     size_t total = 0, bytes = 0;
     for (auto& mf : per) { total += mf.count(); bytes += mf.strings_len(); }
     std::vector<size_t> idx(per.size(), 0);
-    const uint64_t seg_cap = seg_bytes ? seg_bytes : 0xFFFFFFF0ull;   // (tests: results of several segments without gigabytes of strings)
     if (bytes <= seg_cap) {   // the usual case: the arenas are copied whole, the offsets rebased
         out->segs.emplace_back();
         MissionFindings& m = out->segs.back();

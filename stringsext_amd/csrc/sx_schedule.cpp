@@ -175,6 +175,9 @@ struct BufferScan {
         HostBytes host_view(host_bytes ? host_bytes : (const uint8_t*)"");
         ByteView& early_view = host_bytes ? (ByteView&)host_view : (ByteView&)*base_view;
         PreReplayed pre(nm);
+        // (a Mission replayed in slabs leaves its last copy running under what follows here — replay_all waits for it; leaving early,
+        // this does, before the blocks in `pre` go anywhere)
+        struct SlabDrain { sx_ctx* ctx; ~SlabDrain() { (void)slab_copy_drain(ctx); } } slab_drain{ ctx };
         if (ctx->last_runs.size() != nm) ctx->last_runs.assign(nm, 0);
         ctx->wave_off.assign(nm, 0);
         if (ctx->wave_pred.size() != nm) ctx->wave_pred.assign(nm, 0);

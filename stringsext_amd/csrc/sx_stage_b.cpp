@@ -37,6 +37,10 @@ struct Slab {
     bool async_copy = false;          // leave the copy to the host running (the caller waits for `copied`)
     hipEvent_t reuse_after = nullptr; // the output buffer is read by a copy until this event
     hipEvent_t copied = nullptr;
+    hipEvent_t written = nullptr;     // async_copy: pass 2 is done (recorded on stream_b, the copy stream waits for it)
+    // one of several Missions: what this slab may write at most — from there on the Mission's output could reach the deferral
+    // threshold, which only the whole-list path knows (SX_RETRY_WHOLE); 0: no bound
+    uint64_t out_budget = 0;
     // the mission's own start in this buffer (the job's lo / entry_exact are the slab's): the exit state is replayed from the
     // last region's start, which may lie in an earlier slab
     uint64_t lo0 = 0;
@@ -189,6 +193,7 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
     if (n) HIP_TRY(ctx, hipStreamSynchronize(d.stream_b));
     SX_TL("  replay: pass 1 + stitch done");
     if (dev_stitch && h_tot[kTotTooLong] && slabbed) return SX_RETRY_WHOLE;
+    if (dev_stitch && slabbed && sl.out_budget && h_tot[kTotFindings] * sizeof(sx_finding) + h_tot[kTotBytes] >= sl.out_budget) return SX_RETRY_WHOLE;
     if (dev_stitch && h_tot[kTotTooLong]) {  // regions for the host: it also decides what stands
         dev_stitch = false;
         HIP_TRY(ctx, runs.wait());
@@ -301,8 +306,9 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
             blk = ctx->pool->take(out_bytes + 64);
             if (!blk.p) { ctx->err = "hipHostMalloc failed"; return SX_E_NOMEM; }
             if (sl.async_copy) {   // on the copy stream: the next slab's kernels run meanwhile
-                HIP_TRY(ctx, hipEventRecord(ctx->merge_ev[0], d.stream_b));
-                HIP_TRY(ctx, hipStreamWaitEvent(ctx->merge_copy_stream, ctx->merge_ev[0], 0));
+                ctx->slab_copy_pending = true;   // (from here on the block must not go back to the pool before slab_copy_drain)
+                HIP_TRY(ctx, hipEventRecord(sl.written, d.stream_b));
+                HIP_TRY(ctx, hipStreamWaitEvent(ctx->merge_copy_stream, sl.written, 0));
                 HIP_TRY(ctx, hipMemcpyAsync(blk.p, d_all, out_bytes, hipMemcpyDeviceToHost, ctx->merge_copy_stream));
                 HIP_TRY(ctx, hipEventRecord(sl.copied, ctx->merge_copy_stream));
             } else {
@@ -389,13 +395,40 @@ int ensure_copy_stream(sx_ctx* ctx) {
     if (ctx->merge_copy_stream) return SX_OK;
     HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->merge_copy_stream, hipStreamNonBlocking, 0));
     for (hipEvent_t& e : ctx->merge_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (hipEvent_t& e : ctx->slab_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return SX_OK;
 }
 
-// Stage B of one mission on the device.  A single mission with a long run list is replayed in slabs (a quarter of the
-// list each, cut where a region begins): a slab's findings travel to the host while the next slab is replayed, so that only
-// the last slab's copy is not hidden (string-dense and text-like input: the output is as large as the input).  Slab j begins
-// where slab j-1 stopped — its last region may run past the cut —, with the state derived there as at a shard start.
+// The last slab's copy is left running when device_replay_mission returns (the other Missions' stage A is collected, the host's
+// share of stage B replayed meanwhile): whoever reads a slab's block, or gives one back to the pool, calls this first.
+int slab_copy_drain(sx_ctx* ctx) {
+    if (!ctx->slab_copy_pending.exchange(false)) return SX_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->merge_copy_stream));
+    return SX_OK;
+}
+
+// Stage B of one mission on the device.  A mission with a long run list is replayed in slabs (a third of the list each, next to
+// other Missions half of it, cut where a region begins): a slab's findings travel to the host while the next slab is replayed, and the last slab's copy is left
+// running for the caller (slab_copy_drain) — the other Missions' stage A is collected and the host's share of stage B replayed
+// under it.  Slab j begins where slab j-1 stopped — its last region may run past the cut —, with the state derived there as at a
+// shard start.  The Mission's findings then are several blocks (MissionFindings::more), which merge_findings interleaves with
+// the other Missions' on the host.  So, with several Missions, slabs are for the busy one among quiet ones:
+//  * every other Mission has too few runs for the device by ctx->last_runs: that is this buffer's count for the Missions replayed
+//    before this one, and the last buffer's for those that follow (their findings are on the host, the merge is the host's whatever
+//    this Mission does) — two busy Missions are interleaved by device_merge, which wants each list in one piece.  A later Mission
+//    that was quiet then and is busy now still comes out right: it is replayed whole, in one block, and the host merges;
+//  * the output stays below the deferral threshold (defer_min_bytes: from there on it waits in HBM for device_merge).  It is
+//    estimated from the last buffer's bytes per run, with a factor of two; and it is checked: every slab knows after pass 1 what
+//    it will write, and the slab that would take the sum to the threshold hands the Mission to the whole-list path, which defers;
+//  * the result goes to the host, and the buffer is not one of a sequence whose merged parts are still being copied (merge_async).
+static bool slabs_next_to_others(const sx_ctx* ctx, size_t k, const ReplayJob& job) {
+    if (ctx->missions.size() < 2 || (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) || ctx->merge_async || ctx->sharded_call) return false;
+    if (ctx->last_runs.size() != ctx->missions.size()) return false;
+    for (size_t o = 0; o < ctx->missions.size(); o++)
+        if (o != k && (ctx->missions[o].host_sequential() || device_replay_wanted(ctx, job, o, ctx->last_runs[o]))) return false;
+    return true;
+}
+
 int device_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& job, const RunList& runs,
                           MissionFindings* out, uint64_t* end_pos, uint64_t defer_min_bytes) {
     const size_t n = runs.size();
@@ -407,10 +440,24 @@ int device_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob
         if (k < ctx->wave_pred.size()) ctx->wave_pred[k] = 0;
     }
     if (runs.skipped) return SX_NEED_RUNS;
+    auto note_output = [&]() {   // for the next buffer's estimate
+        uint64_t bytes = out->count() * sizeof(sx_finding) + out->strings_len();
+        for (const MissionFindings& m : out->more) bytes += m.count() * sizeof(sx_finding) + m.strings_len();
+        d.last_out_runs = n; d.last_out_bytes = bytes;
+    };
     size_t K = 1;
-    const bool can = ctx->missions.size() == 1 && runs.on_device && !ctx->sw.host_stitch && defer_min_bytes == 0;
+    const bool alone = ctx->missions.size() == 1 && defer_min_bytes == 0;
+    const bool beside = !alone && slabs_next_to_others(ctx, k, job);
+    const bool can = (alone || beside) && runs.on_device && !ctx->sw.host_stitch;
     const bool keep_dev_wanted = (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) && ctx->missions.size() == 1 && defer_min_bytes == 0 && job.commit_state && !ctx->sharded_call && ctx->single_piece;   // (one slab then: one block of the context's)
-    if (can && n >= (1u << 20) && !keep_dev_wanted) K = 3;   // (measured on string-dense and text-like input: 3 beats 2, 4 and 6)
+    // (measured on string-dense and text-like input, one Mission: 3 beats 2, 4 and 6.  Next to other Missions, on the headline — 1.4 M runs
+    // and 60 MB of findings per half —: 2 beats 1, and 3 and 4 lose to 1: a slab costs two host waits, and the half that is replayed first
+    // does so next to the following half's scan, where every kernel and wait takes longer)
+    if (can && n >= (1u << 20) && !keep_dev_wanted) {
+        K = beside ? 2 : 3;
+        // (next to other Missions: only with a buffer behind this one — what the others yield, what this one writes per run)
+        if (beside && (!d.last_out_runs || (defer_min_bytes && 2.0 * (double)n * (double)d.last_out_bytes / (double)d.last_out_runs >= (double)defer_min_bytes))) K = 1;
+    }
     if (ctx->sw.slabs) { K = (size_t)ctx->sw.slabs; if (!can || n < 8 * K) K = 1; }
     std::vector<uint64_t> idx{ 0 }, his{ 0 };
     if (K > 1) {   // where to cut
@@ -432,8 +479,10 @@ int device_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob
     if (ns > 1) {
         std::vector<MissionFindings> got;
         SlabCarry carry;
-        hipEvent_t copied[2] = { ctx->merge_ev[1], ctx->merge_ev[2] };
-        uint64_t e_prev = 0;
+        hipEvent_t copied[2] = { ctx->slab_ev[1], ctx->slab_ev[2] };
+        uint64_t e_prev = 0, written = 0;
+        uint64_t fast0 = 0, general0 = 0;   // (a Mission handed to the whole-list path is counted once)
+        { std::lock_guard<std::mutex> g(ctx->mu); fast0 = ctx->stats.fast_regions; general0 = ctx->stats.general_regions; }
         int rc = SX_OK;
         for (size_t j = 0; j < ns && rc == SX_OK; j++) {
             ReplayJob sj = job;
@@ -443,19 +492,26 @@ int device_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob
             Slab sl;
             sl.i0 = idx[j]; sl.i1 = idx[j + 1]; sl.first = j == 0; sl.last = j + 1 == ns;
             sl.out_slot = (j & 1) ? 8 : 5; sl.async_copy = true;
-            sl.reuse_after = j >= 2 ? copied[j & 1] : nullptr; sl.copied = copied[j & 1];
+            sl.reuse_after = j >= 2 ? copied[j & 1] : nullptr; sl.copied = copied[j & 1]; sl.written = ctx->slab_ev[0];
             sl.lo0 = job.lo[k]; sl.entry_exact0 = job.entry_exact[k] != 0;
+            if (defer_min_bytes) {
+                if (written >= defer_min_bytes) { rc = SX_RETRY_WHOLE; break; }
+                sl.out_budget = defer_min_bytes - written;
+            }
             MissionFindings mf;
             uint64_t e_now = 0;
             rc = device_replay_slab(ctx, k, view, sj, runs, sl, carry, &mf, &e_now, 0);
             e_prev = std::max(e_prev, e_now);
             if (rc == SX_OK) {
                 out->replay_bytes += mf.replay_bytes; mf.replay_bytes = 0;
+                written += mf.count() * sizeof(sx_finding) + mf.strings_len();
                 if (mf.count()) got.push_back(std::move(mf));
             } else if (mf.ext.p) got.push_back(std::move(mf));
         }
-        (void)hipStreamSynchronize(ctx->merge_copy_stream);
-        (void)hipStreamSynchronize(d.stream_b);
+        // On success neither stream is waited for here.  The last slab's copy runs on (slab_copy_drain).  So may the tail of its pass 2
+        // on stream_b, while the caller queues the next Mission's stage A or device replay: that is in order only because every
+        // Mission's stream_b is the one ctx->post_stream (sx_api.cpp) — what is queued next runs behind it —, and because d_cache and
+        // d_scratch grow through hipFree, which waits for the device.  A Mission with a stream of its own would need the wait back.
         if (rc == SX_OK) {
             const uint64_t rb = out->replay_bytes;
             if (!got.empty()) {
@@ -464,16 +520,23 @@ int device_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob
             }
             out->replay_bytes = rb;
             if (end_pos) *end_pos = e_prev;
+            note_output();
             return SX_OK;
         }
+        (void)hipStreamSynchronize(ctx->merge_copy_stream);
+        (void)hipStreamSynchronize(d.stream_b);
+        ctx->slab_copy_pending = false;
         for (auto& g : got) if (g.ext.p) ctx->pool->give(g.ext);
         out->replay_bytes = 0;
         if (rc != SX_RETRY_WHOLE) return rc;
+        { std::lock_guard<std::mutex> g(ctx->mu); ctx->stats.fast_regions = fast0; ctx->stats.general_regions = general0; }
     }
     Slab sl;
     sl.i1 = n;
     SlabCarry carry;
-    return device_replay_slab(ctx, k, view, job, runs, sl, carry, out, end_pos, defer_min_bytes);
+    const int rc = device_replay_slab(ctx, k, view, job, runs, sl, carry, out, end_pos, defer_min_bytes);
+    if (rc == SX_OK) note_output();
+    return rc;
 }
 
 // A mission's findings that were left on the device (dev_only) come to the host after all.
@@ -539,6 +602,7 @@ int merge_drain(sx_ctx* ctx) {
     if (ctx->post_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->post_stream));
     if (ctx->merge_copy_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->merge_copy_stream));
     ctx->merge_copy_pending[0] = ctx->merge_copy_pending[1] = false;
+    ctx->slab_copy_pending = false;
     ctx->interleave_pending = false;
     return SX_OK;
 }
@@ -812,6 +876,8 @@ int replay_all(sx_ctx* ctx, ByteView& bytes, const ReplayJob& job, const std::ve
     const double t0 = now_ms();
     const size_t nm = ctx->missions.size();
     const unsigned nthreads = replay_threads(ctx);
+    // (leaving early: no slab's copy may still be writing into a block that goes back to the pool)
+    struct SlabDrain { sx_ctx* ctx; ~SlabDrain() { (void)slab_copy_drain(ctx); } } slab_drain{ ctx };
     std::vector<std::vector<uint64_t>> bounds(nm);
     std::vector<std::vector<ReplayPart>> parts(nm);
     std::vector<std::pair<size_t, size_t>> tasks;
@@ -883,6 +949,11 @@ int replay_all(sx_ctx* ctx, ByteView& bytes, const ReplayJob& job, const std::ve
     const double t_stitch = now_ms();
     SX_TL("replay_all: host parts + stitch done");
     const size_t count_before = into->count();
+    {   // from here on the findings are read: a Mission's last slab may still be on its way (device_replay_mission)
+        int rc = slab_copy_drain(ctx);
+        if (rc != SX_OK) return rc;
+    }
+    SX_TL("replay_all: slab copies done");
     {   // several missions with findings that are all still on the device: interleave them there
         // (a stable radix sort by position) instead of finding by finding on the host
         int rc = device_merge(ctx, job, per, into);

@@ -50,7 +50,7 @@ struct Switches {
     bool fast_replay = true;           // SX_FAST_REPLAY on / off: the fast pre-pass of pass 1 (tests)
     int count_waves = 4;               // SX_COUNT_WAVES=4 / 6 / 8: wavefronts per SIMD the cached count kernel is built for (experiments)
     int stitch_block = 0;              // SX_STITCH_BLOCK=n (> 0): runs per block of the stitch; 0 unset: 128, 512 from 2^20 runs on (tests)
-    int slabs = 0;                     // SX_SLABS=n (1 .. 64): slabs of a single Mission's device replay; 0 unset: 3 from 2^20 runs on (tests)
+    int slabs = 0;                     // SX_SLABS=n (1 .. 64): slabs of the device replay of a Mission that may have them (alone, or busy among quiet ones: sx_stage_b.cpp); 0 unset: from 2^20 runs on 3 for a single Mission, 2 next to other Missions (tests)
     int replay_copy_wgs = 0;           // SX_REPLAY_COPY_WGS=n (> 0): the result copy as a kernel of n workgroups, not the runtime's blit (experiments)
     // ---- the Missions' findings interleaved (sx_stage_b.cpp device_merge, sx_sort.hip, sx_replay.cpp)
     bool host_merge = false;           // SX_HOST_MERGE presence: interleave on the host (tests)

@@ -566,8 +566,8 @@ int  sx_result_select_set_device(sx_ctx* ctx, const sx_result* r, const sx_selec
  *   ^ or $ in mid-pattern                 legal: (^a|b)c, a$|b; a^b is legal and matches nothing
  *   every other backslash + alphanumeric (\b \B \A \Z \1 \e ...)  refused
  * Refused means SX_E_INVALID, and sx_last_error names the pattern's index, the byte offset and the reason.  Not in the language:
- * Unicode-aware classes and folding ([а-я] is a byte class), \b, lookaround, back-references, captures, which pattern matched.
- * (Where the matches lie: sx_result_extract_regex_device, below.)
+ * Unicode-aware classes and folding ([а-я] is a byte class), \b, lookaround, back-references, captures.
+ * (Where the matches lie: sx_result_extract_regex_device, below; which patterns match in a finding: sx_result_label_device, below.)
  * flags: 0 or SX_SELECT_ASCII_NOCASE — the fold is compiled into the set, and it is re.IGNORECASE on a bytes pattern: a literal
  * letter matches both cases, a class holds a letter's other case too and negation applies after that ([Z-a] matches z and A,
  * [^Z-a] matches neither); no byte >= 0x80 is folded.
@@ -641,7 +641,8 @@ int  sx_result_select_regex_device(sx_ctx* ctx, const sx_result* r, const sx_sel
  * set on another device, or — with sx_last_error text — a segment whose match count does not fit the 32-bit per-segment counters.
  * COST.  A byte that cannot begin a match costs one table look-up.  A walk that runs far and then fails is repeated from the next
  * start: the worst case is QUADRATIC in a string's length (a*b over a long run of a).  There is no linear-time guarantee.
- * Not built: which pattern matched, captures, the input-byte positions of the matches. */
+ * Not built: which pattern a MATCH is of (sx_result_label_device says which patterns match in a finding, and so in an extraction's
+ * match taken as a finding of its own), captures, the input-byte positions of the matches. */
 typedef struct sx_extract_regex sx_extract_regex;
 typedef struct sx_extract_regex_info {
     uint32_t n_patterns, states, classes, nocase;
@@ -689,7 +690,8 @@ int  sx_result_extract_regex_device(sx_ctx* ctx, const sx_result* r, const sx_ex
  * states <= 32768, else 4), table_bytes in HBM (everything but the counters), the rows of the first lds_states states are what the
  * kernel keeps in LDS, the other rows it reads through L2.
  * Not thread-safe: one sx_result_tally_device call per set at a time, and no reset or read during it.
- * Not built: the number of FINDINGS per keyword (grep -c) and where in a string a hit lies. */
+ * Not built: the number of FINDINGS per keyword (grep -c; for up to 64 regular expressions sx_result_label_device counts exactly that)
+ * and where in a string a hit lies. */
 typedef struct sx_tally_set sx_tally_set;
 typedef struct sx_tally_set_info {
     uint32_t n_patterns, unique;   /* unique: distinct keywords after the fold */
@@ -706,6 +708,77 @@ int  sx_result_tally_device(sx_ctx* ctx, const sx_result* r, sx_tally_set* set, 
 int  sx_tally_set_read(const sx_tally_set* set, uint64_t* hits, uint64_t* first, uint32_t n_patterns);
 int  sx_tally_set_counters_device(const sx_tally_set* set, const uint64_t** d_hits, const uint64_t** d_first,
                                   const uint32_t** d_unique_of_pattern, uint32_t* unique);
+
+/* The LABELS of a result whose segments ALL lie in HBM: for every finding, WHICH patterns of a regex list are found in its string,
+ * as one 64-bit word — what the regex selection's one bit per finding ("some pattern matched") throws away —, made where the findings
+ * lie (csrc/sx_label_dev.hip) in one walk over the strings, with the number of findings per pattern (`grep -c`, exactly) and the first
+ * of them counted on the way; and the selection by label, which splits a result into its kinds without reading a string byte.
+ * PATTERNS AND FLAGS.  A label set holds 1..SX_SELECT_REGEX_MAX_PATTERNS patterns; pattern p owns bit p.  The language is exactly the
+ * regex set's, above: the same refusals, the same limits (SX_SELECT_REGEX_MAX_*, the bound on the construction's memory), the same
+ * error texts; flags: 0 or SX_SELECT_ASCII_NOCASE, compiled into the set.  sx_label_set_create builds, on the host, ONE minimal DFA
+ * (csrc/sx_label_build.hpp: the regex set's parser and NFA with an accept per pattern, unanchored subset construction, per state the
+ * patterns that have matched with the byte that led there and those that match if the string ends there) and puts its tables into HBM
+ * on the context's device, with two counters per pattern.  There is no "matched" state that absorbs the walk once ANY pattern has
+ * matched, because the others are still asked for: a label set reaches SX_SELECT_REGEX_MAX_STATES sooner than a regex set of the same
+ * patterns (SX_E_INVALID, the regex set's text), and a lane stops early only where every pattern has matched or none can any more.
+ * It is an object of its own: a regex set compiles nothing more than before.  It owns its device memory, tables and counters, and
+ * does not depend on the context's lifetime: it may be freed before or after sx_destroy, and used with any context on the same HIP
+ * device (another device: SX_E_INVALID).  Errors as sx_select_regex_create's; *out = NULL on every error.
+ * sx_label_set_info_get: what was built — table_bytes in HBM (everything but the counters), the rows of the first lds_states states are
+ * what the kernel keeps in LDS, the other rows it reads through L2; here_states: the states that end a match of some pattern.
+ * THE RULE.  Bit p of finding i's label is set iff pattern p is found somewhere in its string: Python's re.search on the bytes
+ * pattern with `$` read as `\Z`, and re.IGNORECASE for a nocase set.  A match never spans two findings.  The bits of patterns the set
+ * does not have are 0.
+ * THE COUNTERS, per pattern, read after one or more sx_result_label_device calls: findings[p] = the number of findings with bit p;
+ * first[p] = the smallest (ordinal_base + index of the finding in the result's print order) among them — the print order is segment
+ * 0's records, then segment 1's, and so on —, or SX_LABEL_NEVER if there is none.  A new set is reset.
+ * sx_result_label_device makes *out, the labels of r's findings (sx_labels_free), and ADDS to the set's counters as the tally does: a
+ * stream scanned buffer by buffer gives one count of the whole stream if the caller passes the number of findings of the buffers
+ * before as ordinal_base.  The labels object owns its device memory: one array of 64-bit words per source segment, in record order
+ * (sx_labels_segments, sx_labels_segment_device: *d_labels = *n_findings words in HBM, valid until sx_labels_free, before or after
+ * sx_destroy).  The sources are exactly what sx_print_findings_device accepts — both record types, any layout of the strings, the
+ * result of any selection or extraction —, and SX_E_STATE comes back wherever that function would refuse the source; that is decided
+ * for ALL segments before anything is launched.  The source is read, never moved.  The call writes neither the result block nor the
+ * selection blocks: it does NOT count towards "valid until the SECOND selection after the one that made it" and invalidates nothing.
+ * It returns when the kernels are done.  SX_E_INVALID: a NULL pointer, a set on another device.  SX_E_NOMEM: the labels cannot be
+ * allocated; nothing is counted then (the allocation comes before the launch).
+ * sx_label_set_reset: every findings = 0, every first = SX_LABEL_NEVER.  sx_label_set_read: findings and first per pattern (either
+ * array may be NULL); n_patterns must be the set's (else SX_E_INVALID).  sx_label_set_counters_device: the counters where they lie,
+ * in HBM, 64 words each of which the first n_patterns are used, for hosts that stay on the GPU; either may be NULL; valid until
+ * sx_label_set_free.
+ * sx_result_select_labels_device: finding i of r is selected iff
+ *   (any == 0 || (label_i & any) != 0) && (label_i & all) == all && (label_i & none) == 0
+ * — any == all == none == 0 selects everything.  Mask bits at or above n_patterns are legal: such a bit is never set in a label, so
+ * in `all` it selects nothing and in `none` it is harmless.  In everything else the contract of sx_result_select_regex_device, word
+ * for word — the output layout, the empty result, the source that is read and never moved, the two selection blocks and their
+ * epochs —: the call counts as a selection.  It reads 8 bytes per record and the records, no string byte.  `labels` must have been
+ * made from r: the labels remember, per segment, where the source's records lie, how many they are and the epoch of their block;
+ * another result is SX_E_INVALID (sx_last_error says so), a source whose memory has been reused since is SX_E_STATE, as that source
+ * itself would be.  The labels of a selection are not carried to its output: label the output again, or select by label first.
+ * Not thread-safe: one sx_result_label_device call per set at a time, and no reset or read during it.
+ * Not built: which pattern matched WHERE (labels on an extraction's matches by their own pattern), labels for keyword sets of 65536
+ * entries, labels carried through a selection, Unicode folding. */
+typedef struct sx_label_set sx_label_set;   /* compiled patterns + their counters, in HBM */
+typedef struct sx_labels    sx_labels;      /* one result's labels, in HBM */
+typedef struct sx_label_set_info {
+    uint32_t n_patterns, states, classes, nocase;
+    uint64_t table_bytes;     /* everything the set holds in HBM except the counters */
+    uint32_t lds_states;      /* states whose rows the kernel keeps in LDS */
+    uint32_t here_states;     /* states that end a match of some pattern: a step into one ORs its mask into the label */
+} sx_label_set_info;
+#define SX_LABEL_NEVER UINT64_MAX
+int  sx_label_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_label_set** out);
+int  sx_label_set_info_get(const sx_label_set* set, sx_label_set_info* out);
+void sx_label_set_free(sx_label_set* set);
+int  sx_label_set_reset(sx_label_set* set);
+int  sx_label_set_read(const sx_label_set* set, uint64_t* findings, uint64_t* first, uint32_t n_patterns);
+int  sx_label_set_counters_device(const sx_label_set* set, const uint64_t** d_findings, const uint64_t** d_first);
+int  sx_result_label_device(sx_ctx* ctx, const sx_result* r, sx_label_set* set, uint64_t ordinal_base, sx_labels** out);
+int  sx_labels_segment_device(const sx_labels* labels, uint64_t segment, const uint64_t** d_labels, uint64_t* n_findings);
+uint64_t sx_labels_segments(const sx_labels* labels);
+void sx_labels_free(sx_labels* labels);
+int  sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels,
+                                    uint64_t any, uint64_t all, uint64_t none, sx_result** out);
 
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);

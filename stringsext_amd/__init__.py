@@ -24,6 +24,7 @@ SX_SELECT_SET_MAX_PATTERNS, SX_SELECT_SET_MAX_PATTERN_BYTES, SX_SELECT_SET_MAX_T
 SX_SELECT_REGEX_MAX_PATTERNS, SX_SELECT_REGEX_MAX_PATTERN_BYTES, SX_SELECT_REGEX_MAX_REPEAT = 64, 1024, 255
 SX_SELECT_REGEX_MAX_POSITIONS, SX_SELECT_REGEX_MAX_STATES = 65536, 65536
 SX_TALLY_NEVER = (1 << 64) - 1   # sx_tally_set_read: first[k] of a keyword without a hit
+SX_LABEL_NEVER = (1 << 64) - 1   # sx_label_set_read: first[p] of a pattern without a finding
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -45,7 +46,9 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_select_set_create", "sx_select_set_info_get", "sx_select_set_free", "sx_result_select_set_device", "sx_select_regex_create", "sx_select_regex_info_get", "sx_select_regex_free",
            "sx_result_select_regex_device", "sx_extract_regex_create", "sx_extract_regex_info_get", "sx_extract_regex_free",
            "sx_result_extract_regex_device", "sx_tally_set_create", "sx_tally_set_info_get", "sx_tally_set_free", "sx_tally_set_reset",
-           "sx_result_tally_device", "sx_tally_set_read", "sx_tally_set_counters_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
+           "sx_result_tally_device", "sx_tally_set_read", "sx_tally_set_counters_device",
+           "sx_label_set_create", "sx_label_set_info_get", "sx_label_set_free", "sx_label_set_reset", "sx_label_set_read", "sx_label_set_counters_device",
+           "sx_result_label_device", "sx_labels_segment_device", "sx_labels_segments", "sx_labels_free", "sx_result_select_labels_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
 
@@ -195,6 +198,11 @@ class TallySetInfo(C.Structure):   # sx_tally_set_info
                 ("reserved", C.c_uint32)]
 
 
+class LabelSetInfo(C.Structure):   # sx_label_set_info
+    _fields_ = [("n_patterns", C.c_uint32), ("states", C.c_uint32), ("classes", C.c_uint32), ("nocase", C.c_uint32),
+                ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32), ("here_states", C.c_uint32)]
+
+
 class Run(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("chars", C.c_uint64)]
 
@@ -287,6 +295,17 @@ def lib():
     L.sx_result_tally_device.argtypes = [vp, vp, vp, u64, pu64]
     L.sx_tally_set_read.argtypes = [vp, pu64, pu64, C.c_uint32]
     L.sx_tally_set_counters_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint32)]
+    L.sx_label_set_create.argtypes = [vp, C.POINTER(Pattern), C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.sx_label_set_info_get.argtypes = [vp, C.POINTER(LabelSetInfo)]
+    L.sx_label_set_free.argtypes, L.sx_label_set_free.restype = [vp], None
+    L.sx_label_set_reset.argtypes = [vp]
+    L.sx_label_set_read.argtypes = [vp, pu64, pu64, C.c_uint32]
+    L.sx_label_set_counters_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.sx_result_label_device.argtypes = [vp, vp, vp, u64, C.POINTER(vp)]
+    L.sx_labels_segment_device.argtypes = [vp, u64, C.POINTER(vp), pu64]
+    L.sx_labels_segments.argtypes, L.sx_labels_segments.restype = [vp], u64
+    L.sx_labels_free.argtypes, L.sx_labels_free.restype = [vp], None
+    L.sx_result_select_labels_device.argtypes = [vp, vp, vp, u64, u64, u64, C.POINTER(vp)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -410,7 +429,7 @@ class Result:
                                                     C.byref(p), C.byref(n)))
         return p.value, n.value
 
-    def select_device(self, patterns, ignore_case=False, invert=False):
+    def select_device(self, patterns, ignore_case=False, invert=False, any=0, all=0, none=0):
         """The findings whose string holds one of `patterns` (bytes, or a list of 1..16 bytes objects of 1..64 bytes each) as a
         substring — `grep -F` over the strings —, selected on the device (sx_result_select_device) out of a result whose segments
         all lie in HBM (result_on_device=True): a new Result on the device, record order kept, strings back to back, which
@@ -421,9 +440,25 @@ class Result:
         `patterns` may also be a PatternSet (Scanner.pattern_set: a compiled keyword list of up to 65536 patterns, grep -F -f): the
         same selection by sx_result_select_set_device; the fold belongs to the set then, and ignore_case=True raises ValueError.
         Or a RegexSet (Scanner.regex_set: up to 64 byte regular expressions, grep -E -f): sx_result_select_regex_device, with the
-        same rule for the fold.  An ExtractSet is no selection (extract_device takes it): TypeError."""
+        same rule for the fold.  An ExtractSet is no selection (extract_device takes it): TypeError.
+        Or the Labels that label_device() made of THIS Result, with the masks any, all, none (sx_result_select_labels_device): the
+        findings whose label has a bit of `any` (any == 0: no such condition), every bit of `all` and no bit of `none`; no string
+        byte is read.  ignore_case and invert do not apply then (ValueError), and the masks apply to nothing else (ValueError).
+        Labels of another Result: SxError SX_E_INVALID."""
         if isinstance(patterns, ExtractSet):
-            raise TypeError("select_device takes patterns, a PatternSet or a RegexSet; an ExtractSet goes to extract_device")
+            raise TypeError("select_device takes patterns, a PatternSet, a RegexSet or Labels; an ExtractSet goes to extract_device")
+        if isinstance(patterns, Labels):
+            if ignore_case or invert:
+                raise ValueError("a selection by Labels takes the masks any, all and none: the fold belongs to the LabelSet, and `none` inverts")
+            if not self._s.h:
+                raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+            if not patterns.h:
+                raise SxError(SX_E_INVALID, "the Labels have been freed")
+            out = C.c_void_p()
+            self._s._chk(lib().sx_result_select_labels_device(self._s.h, self.h, patterns.h, any, all, none, C.byref(out)))
+            return Result(self._s, out)
+        if any or all or none:
+            raise ValueError("the masks any, all and none select by Labels (Result.label_device)")
         if isinstance(patterns, RegexSet):
             if ignore_case:
                 raise ValueError("ignore_case belongs to the RegexSet: Scanner.regex_set(patterns, ignore_case=True)")
@@ -485,6 +520,20 @@ class Result:
         n = C.c_uint64()
         self._s._chk(lib().sx_result_tally_device(self._s.h, self.h, tally.h, ordinal_base, C.byref(n)))
         return n.value
+
+    def label_device(self, label_set, ordinal_base=0):
+        """sx_result_label_device: for every finding of this Result WHICH patterns of `label_set` (a LabelSet: Scanner.label_set) are
+        found in its string — Labels, one 64-bit word per finding in HBM, bit p for pattern p —, and per pattern the number of such
+        findings and the first of them ADDED to the set's counters; a finding's ordinal is ordinal_base + its index in this Result's
+        print order.  This Result is read, not moved, and no selection ages.  Raises SxError: SX_E_STATE wherever printed_device()
+        would refuse this Result (nothing is counted then), SX_E_INVALID for a freed set."""
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        if not isinstance(label_set, LabelSet) or not label_set.h:
+            raise SxError(SX_E_INVALID, "the LabelSet has been freed" if isinstance(label_set, LabelSet) else "label_device takes a LabelSet")
+        out = C.c_void_p()
+        self._s._chk(lib().sx_result_label_device(self._s.h, self.h, label_set.h, ordinal_base, C.byref(out)))
+        return Labels(self._s, out)
 
     def free(self):
         if self.h:
@@ -637,6 +686,104 @@ class TallySet:
             pass
 
 
+class LabelSet:
+    """Byte regular expressions compiled for labelling on the device (sx_label_set_create; Scanner.label_set makes it), with their
+    counters: Result.label_device() says which of them every finding holds and adds to the counters, on result after result.  It owns
+    its device memory: free() it before or after the Scanner's close()."""
+
+    def __init__(self, handle, n_patterns):
+        self.h, self.n_patterns = handle, n_patterns
+
+    def _handle(self):
+        if not self.h:
+            raise SxError(SX_E_INVALID, "the LabelSet has been freed")
+        return self.h
+
+    @property
+    def info(self):
+        """a LabelSetInfo (sx_label_set_info): n_patterns, states, classes, nocase, table_bytes (in HBM), lds_states, here_states"""
+        i = LabelSetInfo()
+        rc = lib().sx_label_set_info_get(self._handle(), C.byref(i))
+        if rc != SX_OK:
+            raise SxError(rc, "sx_label_set_info_get")
+        return i
+
+    def read(self):
+        """(findings, first): two lists with an entry per pattern; first[p] is SX_LABEL_NEVER where findings[p] is 0"""
+        findings, first = (C.c_uint64 * self.n_patterns)(), (C.c_uint64 * self.n_patterns)()
+        rc = lib().sx_label_set_read(self._handle(), findings, first, self.n_patterns)
+        if rc != SX_OK:
+            raise SxError(rc, "sx_label_set_read")
+        return list(findings), list(first)
+
+    def reset(self):
+        """every findings = 0, every first = SX_LABEL_NEVER"""
+        rc = lib().sx_label_set_reset(self._handle())
+        if rc != SX_OK:
+            raise SxError(rc, "sx_label_set_reset")
+
+    def counters_device(self):
+        """(d_findings, d_first): device addresses of two arrays of 64 uint64, of which the first n_patterns are used"""
+        f, m = C.c_void_p(), C.c_void_p()
+        rc = lib().sx_label_set_counters_device(self._handle(), C.byref(f), C.byref(m))
+        if rc != SX_OK:
+            raise SxError(rc, "sx_label_set_counters_device")
+        return f.value, m.value
+
+    def free(self):
+        if self.h:
+            lib().sx_label_set_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Labels:
+    """One Result's labels in HBM (sx_result_label_device; Result.label_device makes them): a 64-bit word per finding, an array per
+    segment of the Result.  Result.select_device() of the SAME Result takes them with the masks any, all, none.  They own their
+    device memory: free() them before or after the Scanner's close()."""
+
+    def __init__(self, scanner, handle):
+        self._s, self.h = scanner, handle
+
+    def device_segments(self):
+        """[(device pointer to the segment's labels, n findings)] per segment of the source"""
+        if not self.h:
+            raise SxError(SX_E_INVALID, "the Labels have been freed")
+        L = lib()
+        out = []
+        for i in range(L.sx_labels_segments(self.h)):
+            p, n = C.c_void_p(), C.c_uint64()
+            rc = L.sx_labels_segment_device(self.h, i, C.byref(p), C.byref(n))
+            if rc != SX_OK:
+                raise SxError(rc, "sx_labels_segment_device")
+            out.append((p.value, n.value))
+        return out
+
+    def download(self):
+        """one list of ints per segment: the labels in record order (sx_device_download)"""
+        out = []
+        for p, n in self.device_segments():
+            raw = self._s.download(p, n * 8) if n else b""
+            out.append(list((C.c_uint64 * n).from_buffer_copy(raw)) if n else [])
+        return out
+
+    def free(self):
+        if self.h:
+            lib().sx_labels_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Scanner:
     """One sx_ctx: N missions bound to one HIP device (device=SX_HOST_ONLY: replay stage only).
     result_on_device=True (SX_OPT_RESULT_ON_DEVICE): the result of scan() / scan_device() stays in HBM — Result.device_segments(),
@@ -707,6 +854,17 @@ class Scanner:
         out = C.c_void_p()
         self._chk(lib().sx_extract_regex_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
         return ExtractSet(out)
+
+    def label_set(self, patterns, ignore_case=False):
+        """sx_label_set_create: `patterns` (the language and the limits of regex_set; pattern p owns bit p of a label) compiled into
+        one DFA with a mask per state in HBM on this Scanner's device, with two counters per pattern, for Result.label_device().
+        ignore_case: re.IGNORECASE on a bytes pattern, compiled in.  A refused pattern raises SxError (SX_E_INVALID) whose text names
+        the pattern's index, the offset and the reason."""
+        pats = [bytes(p) for p in patterns]
+        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        out = C.c_void_p()
+        self._chk(lib().sx_label_set_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        return LabelSet(out, len(pats))
 
     def scan(self, data, file_id=-1, is_last=False):
         """sx_scan: replaces the loop src/main.rs:153-168 for one chunk held in host memory."""

@@ -11,6 +11,8 @@
 #include "sx_extract_core.hpp"
 #include "sx_seltally_build.hpp"
 #include "sx_seltally_core.hpp"
+#include "sx_label_build.hpp"
+#include "sx_label_core.hpp"
 
 using namespace sx;
 
@@ -47,6 +49,30 @@ struct sx_tally_set {
     const uint32_t* d_unique_of_pattern = nullptr;
     std::vector<uint32_t> unique_of_pattern;
     sx_tally_set_info info{};
+};
+
+// sx_label_set_create: regular expressions compiled for the labels; `mem` = [the class map][the table][here][end][findings][first],
+// device memory of its own
+struct sx_label_set {
+    int device = 0;
+    uint8_t* mem = nullptr;
+    LabelDevice dev{};
+    sx_label_set_info info{};
+};
+
+// sx_result_label_device: one result's labels; `mem` = an array per source segment, each 256-byte aligned, device memory of its own.
+// Per segment what tells the source apart: where its records lie, how many they are, and the epoch of its block when it was labelled.
+struct sx_labels {
+    struct Seg {
+        const uint64_t* d = nullptr;
+        const void* recs = nullptr;
+        uint64_t n = 0;
+        std::shared_ptr<std::atomic<uint64_t>> epoch_ref;
+        uint64_t epoch = 0;
+    };
+    int device = 0;
+    uint8_t* mem = nullptr;
+    std::vector<Seg> segs;
 };
 
 namespace sx {
@@ -778,9 +804,21 @@ static int grow_device(sx_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t bytes, 
 // selection block, pass 2 of every segment that has selected findings, one more wait.  The source is read, never moved.
 // grep -o (sx_extract_dev.hip), for the fourth: with the compiled `ex` the two passes are extract_measure and extract_place, an output
 // record is a match, not a finding, and a segment may get more records than it had; the blocks, their turns and the epochs are the same.
-static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, const SelsetDevice* set, const SelreDevice* re, const ExtractDevice* ex, uint32_t flags, sx_result** out) {
+// By label (sx_label_dev.hip), for the fifth: with `labels` (made from r: checked here) and masks = { any, all, none } pass 1 is
+// label_pick_kernel, which reads no string byte; everything behind it is the selection's.
+static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, const SelsetDevice* set, const SelreDevice* re, const ExtractDevice* ex, uint32_t flags, sx_result** out,
+                            const sx_labels* labels = nullptr, const uint64_t* masks = nullptr) {
     if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
     { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
+    if (labels) {
+        bool same = labels->segs.size() == r->r.segs.size();
+        for (size_t i = 0; same && i < labels->segs.size(); i++) {
+            const sx_labels::Seg& l = labels->segs[i];
+            const MissionFindings& s = r->r.segs[i];
+            same = l.recs == s.dev_copy && l.n == s.ext_nf && l.epoch_ref == s.dev_epoch_ref && l.epoch == s.dev_epoch;
+        }
+        if (!same) { ctx->set_err("the labels were not made from this result"); return SX_E_INVALID; }
+    }
     // the block this call writes: a source that lies there was made two selections ago
     const int slot = (int)(ctx->select_calls & 1u);
     for (const MissionFindings& s : r->r.segs)
@@ -814,7 +852,9 @@ static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* p
         if (set || re) p.pat.invert = (flags & SX_SELECT_INVERT) ? 1u : 0u;
         else select_fill_patterns(&p.pat, patterns, n_patterns, flags);
         const size_t bytes = select_scratch_bytes(s.ext_nf);
-        HIP_TRY(ctx, select_measure(&p, set, re, ctx->d_select_scratch + at, bytes, st, &d_count[i], &d_bytes[i]));
+        LabelPick pick{ nullptr, 0, 0, 0 };
+        if (labels) pick = LabelPick{ labels->segs[i].d, masks[0], masks[1], masks[2] };
+        HIP_TRY(ctx, select_measure(&p, set, re, ctx->d_select_scratch + at, bytes, st, &d_count[i], &d_bytes[i], labels ? &pick : nullptr));
         at += bytes;
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1123,6 +1163,156 @@ int sx_tally_set_counters_device(const sx_tally_set* set, const uint64_t** d_hit
     if (d_unique_of_pattern) *d_unique_of_pattern = set->d_unique_of_pattern;
     if (unique) *unique = set->dev.unique;
     return SX_OK;
+}
+
+int sx_label_set_reset(sx_label_set* set) {
+    if (!set) return SX_E_INVALID;
+    if (hipSetDevice(set->device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    hipError_t e = hipMemset(set->dev.findings, 0, kLabelBits * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMemset(set->dev.first, 0xFF, kLabelBits * sizeof(uint64_t));   // SX_LABEL_NEVER
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (as sx_tally_set_reset: the labelling runs on a stream that does not wait for this one)
+    if (e != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    return SX_OK;
+}
+
+int sx_label_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_label_set** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !out) return SX_E_INVALID;
+    LabelTable T;
+    std::string err;
+    { const int rc = label_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("label set: " + err); return rc; } }
+    if (ctx->host_only) { ctx->set_err("host-only context: no device for the label set"); return SX_E_STATE; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t next_bytes = T.next.size() * sizeof(uint16_t), table = (next_bytes + 15) / 16 * 16;   // (label_match_kernel copies the LDS rows in 16-byte chunks)
+    const size_t here_bytes = T.here.size() * sizeof(uint64_t), end_bytes = T.end.size() * sizeof(uint64_t), counters = kLabelBits * sizeof(uint64_t);
+    const size_t at_here = sizeof T.map + table, at_end = at_here + here_bytes, at_findings = at_end + end_bytes, bytes = at_findings + 2 * counters;
+    uint8_t* mem = nullptr;
+    if (hipMalloc((void**)&mem, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->set_err("label set: no device memory for " + std::to_string(bytes) + " bytes of tables and counters");
+        return SX_E_NOMEM;
+    }
+    hipError_t e = hipMemcpy(mem, T.map, sizeof T.map, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mem + sizeof T.map, T.next.data(), next_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && here_bytes) e = hipMemcpy(mem + at_here, T.here.data(), here_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mem + at_end, T.end.data(), end_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(mem); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
+    sx_label_set* set = new (std::nothrow) sx_label_set;
+    if (!set) { (void)hipFree(mem); return SX_E_NOMEM; }
+    set->device = ctx->device; set->mem = mem;
+    set->dev = LabelDevice{ mem, (const uint16_t*)(mem + sizeof T.map), (const uint64_t*)(mem + at_here), (const uint64_t*)(mem + at_end),
+                            (uint64_t*)(mem + at_findings), (uint64_t*)(mem + at_findings + counters), T.root_here, T.all,
+                            T.states, T.classes, T.lds_states, T.here_first, T.dead, T.n_patterns };
+    set->info = sx_label_set_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)(sizeof T.map + next_bytes + here_bytes + end_bytes), T.lds_states, (uint32_t)T.here.size() };
+    if (sx_label_set_reset(set) != SX_OK) { ctx->set_err("label set: the counters could not be reset"); sx_label_set_free(set); return SX_E_HIP; }
+    *out = set;
+    return SX_OK;
+}
+
+int sx_label_set_info_get(const sx_label_set* set, sx_label_set_info* out) {
+    if (!set || !out) return SX_E_INVALID;
+    *out = set->info;
+    return SX_OK;
+}
+
+void sx_label_set_free(sx_label_set* set) {
+    if (!set) return;
+    (void)hipFree(set->mem);
+    delete set;
+}
+
+int sx_label_set_read(const sx_label_set* set, uint64_t* findings, uint64_t* first, uint32_t n_patterns) {
+    if (!set || n_patterns != set->info.n_patterns) return SX_E_INVALID;
+    if (hipSetDevice(set->device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    for (int k = 0; k < 2; k++) {
+        uint64_t* out = k ? first : findings;
+        if (!out) continue;
+        if (hipMemcpy(out, k ? set->dev.first : set->dev.findings, (size_t)n_patterns * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    }
+    return SX_OK;
+}
+
+int sx_label_set_counters_device(const sx_label_set* set, const uint64_t** d_findings, const uint64_t** d_first) {
+    if (!set) return SX_E_INVALID;
+    if (d_findings) *d_findings = set->dev.findings;
+    if (d_first) *d_first = set->dev.first;
+    return SX_OK;
+}
+
+// The labels where the findings lie (sx_label_dev.hip): the source is checked as a whole, the labels' memory is had, then one kernel per
+// segment, each with the ordinal of its first record, on the selections' stream, and one wait.  Only the labels and the set's counters
+// are written.
+int sx_result_label_device(sx_ctx* ctx, const sx_result* r, sx_label_set* set, uint64_t ordinal_base, sx_labels** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !set || !out) return SX_E_INVALID;
+    if (ctx->host_only) { ctx->set_err("host-only context: no device labels"); return SX_E_STATE; }
+    if (set->device != ctx->device) { ctx->set_err("the label set lies on another device"); return SX_E_INVALID; }
+    { const int rc = result_on_device(ctx, r, "label on the host"); if (rc != SX_OK) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    sx_labels* lab = new (std::nothrow) sx_labels;
+    if (!lab) return SX_E_NOMEM;
+    lab->device = ctx->device;
+    uint64_t bytes = 0;
+    for (const MissionFindings& s : r->r.segs) bytes += ((uint64_t)s.ext_nf * sizeof(uint64_t) + 255) / 256 * 256;
+    if (hipMalloc((void**)&lab->mem, bytes ? bytes : 256) != hipSuccess) {
+        (void)hipGetLastError();
+        delete lab;
+        ctx->set_err("device labels: no memory for " + std::to_string(bytes) + " bytes of labels");
+        return SX_E_NOMEM;
+    }
+    uint64_t walked = 0, at = 0;
+    hipError_t e = hipSuccess;
+    for (const MissionFindings& s : r->r.segs) {
+        sx_labels::Seg seg;
+        seg.d = (const uint64_t*)(lab->mem + at); seg.recs = s.dev_copy; seg.n = s.ext_nf; seg.epoch_ref = s.dev_epoch_ref; seg.epoch = s.dev_epoch;
+        lab->segs.push_back(seg);
+        LabelParams p;
+        memset(&p, 0, sizeof p);
+        p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
+        p.ordinal = ordinal_base + walked;
+        p.labels = (uint64_t*)(lab->mem + at);
+        p.set = set->dev;
+        e = label_launch(p, st);
+        if (e != hipSuccess) break;
+        walked += s.ext_nf;
+        at += ((uint64_t)s.ext_nf * sizeof(uint64_t) + 255) / 256 * 256;
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) {
+        sx_labels_free(lab);
+        ctx->set_err(std::string("device labels: ") + hipGetErrorString(e));
+        return SX_E_HIP;
+    }
+    *out = lab;
+    return SX_OK;
+}
+
+uint64_t sx_labels_segments(const sx_labels* labels) { return labels ? labels->segs.size() : 0; }
+
+int sx_labels_segment_device(const sx_labels* labels, uint64_t segment, const uint64_t** d_labels, uint64_t* n_findings) {
+    if (d_labels) *d_labels = nullptr;
+    if (n_findings) *n_findings = 0;
+    if (!labels || segment >= labels->segs.size()) return SX_E_INVALID;
+    if (d_labels) *d_labels = labels->segs[segment].d;
+    if (n_findings) *n_findings = labels->segs[segment].n;
+    return SX_OK;
+}
+
+void sx_labels_free(sx_labels* labels) {
+    if (!labels) return;
+    (void)hipFree(labels->mem);
+    delete labels;
+}
+
+int sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels, uint64_t any, uint64_t all, uint64_t none, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !labels || !out) return SX_E_INVALID;
+    if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
+    if (labels->device != ctx->device) { ctx->set_err("the labels lie on another device"); return SX_E_INVALID; }
+    const uint64_t masks[3] = { any, all, none };
+    return select_on_device(ctx, r, nullptr, 0, nullptr, nullptr, nullptr, 0, out, labels, masks);
 }
 
 int sx_get_stats(const sx_ctx* ctx, sx_stats* out) {

@@ -277,14 +277,18 @@ hipError_t print_write(const PrintParams& P, hipStream_t stream);
 // the selected records' number and string bytes, valid once `stream` has got there; select_place: the selected records to out_recs, their
 // strings back to back to out_arena (scratch: select_place_scratch_bytes(n_sel), 256-aligned; order_part_strings inside)
 // (set: NULL, or a compiled keyword set — sx_selset_core.hpp —, whose selset_match_kernel then is pass 1: sx_selset_dev.hip; re: NULL, or
-// a compiled regex set — sx_selre_core.hpp —, whose selre_match_kernel then is pass 1: sx_selre_dev.hip; not both)
+// a compiled regex set — sx_selre_core.hpp —, whose selre_match_kernel then is pass 1: sx_selre_dev.hip; pick: NULL, or the segment's
+// labels and three masks — sx_label_core.hpp —, whose label_pick_kernel then is pass 1: sx_label_dev.hip; at most one of the three)
 struct SelectParams;
 struct SelsetDevice;
 struct SelreDevice;
+struct LabelPick;
 size_t select_scratch_bytes(uint64_t n);
 hipError_t selset_launch_match(const SelectParams& P, const SelsetDevice& set, uint64_t waves, hipStream_t stream);
 hipError_t selre_launch_match(const SelectParams& P, const SelreDevice& re, uint64_t waves, hipStream_t stream);
-hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreDevice* re, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes);
+hipError_t label_launch_pick(const SelectParams& P, const LabelPick& pick, uint64_t waves, hipStream_t stream);
+hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreDevice* re, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes,
+                          const LabelPick* pick = nullptr);
 size_t select_place_scratch_bytes(uint64_t n_sel);
 hipError_t select_place(const SelectParams& P, void* out_recs, uint64_t n_sel, uint8_t* out_arena, void* scratch, size_t scratch_bytes, hipStream_t stream);
 // The regex extraction on the device (sx_extract_dev.hip, ExtractParams: sx_extract_core.hpp), a segment at a time, in the shape of the
@@ -301,6 +305,10 @@ hipError_t extract_place(const ExtractParams& P, void* out_recs, uint64_t n_out,
 // the segment's hits to the set's counters; nothing else is written, and the counters are valid once `stream` has got there
 struct SeltallyParams;
 hipError_t seltally_launch(const SeltallyParams& P, hipStream_t stream);
+// The labels on the device (sx_label_dev.hip, LabelParams: sx_label_core.hpp), a segment at a time: label_match_kernel writes the segment's
+// labels and adds to the set's counters; nothing else is written, and both are valid once `stream` has got there
+struct LabelParams;
+hipError_t label_launch(const LabelParams& P, hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
 hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit

@@ -62,8 +62,9 @@ size_t select_scratch_bytes(uint64_t n) {
 // `scratch`; *count and *bytes: the device words that will hold the number of selected records and their string bytes, valid when
 // `stream` has run this far.  set: NULL = P.pat's patterns (select_match_kernel); else a compiled set, whose kernel
 // (sx_selset_dev.hip) fills the same per-wavefront words, and of P.pat only `invert` counts; re: the same for a compiled regex set
-// (sx_selre_dev.hip).  At most one of the two.
-hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreDevice* re, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes) {
+// (sx_selre_dev.hip); pick: the same for the segment's labels and three masks (sx_label_dev.hip).  At most one of the three.
+hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreDevice* re, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes,
+                          const LabelPick* pick) {
     if (P->n == 0 || P->n >= 0xFFFFFFFFull || scratch_bytes < select_scratch_bytes(P->n) || ((uintptr_t)scratch & 255)) return hipErrorInvalidValue;
     const uint64_t waves = (P->n + kSelectRecs - 1) / kSelectRecs;
     const size_t w8 = up256((size_t)(waves + 1) * 8), w4 = up256((size_t)(waves + 1) * 4);
@@ -75,8 +76,9 @@ hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreD
     uint32_t* wbase = (uint32_t*)at; at += w4;
     size_t tmp_bytes = scratch_bytes - (size_t)(at - (uint8_t*)scratch);
     hipError_t e;
-    if (set && re) return hipErrorInvalidValue;
-    if (set) e = selset_launch_match(*P, *set, waves, stream);
+    if ((set ? 1 : 0) + (re ? 1 : 0) + (pick ? 1 : 0) > 1) return hipErrorInvalidValue;
+    if (pick) e = label_launch_pick(*P, *pick, waves, stream);
+    else if (set) e = selset_launch_match(*P, *set, waves, stream);
     else if (re) e = selre_launch_match(*P, *re, waves, stream);
     else {
         hipLaunchKernelGGL(select_match_kernel, dim3((unsigned)((waves + 1 + kSelectWaves - 1) / kSelectWaves)), dim3(64 * kSelectWaves), 0, stream, *P, waves);

@@ -1,9 +1,9 @@
-// sx_selre_front.hpp — what the two regex builders share (sx_selre_build.cpp: "does a pattern match somewhere in the string";
-// sx_extract_build.cpp: "where do the matches lie"), host only and internal to them: the parser (a syntax tree per pattern; whatever
+// sx_selre_front.hpp — what the three regex builders share (sx_selre_build.cpp: "does a pattern match somewhere in the string";
+// sx_extract_build.cpp: "where do the matches lie"; sx_label_build.cpp: "which patterns match"), host only and internal to them: the parser (a syntax tree per pattern; whatever
 // Python's `re` would read differently is refused with the offset), the count of the positions with the repeats unrolled (on the
 // tree: nothing is allocated for a pattern that is refused for it), the Thompson NFA, the closure over its edges without a byte, the
 // byte classes of the construction, and, behind either builder's subset construction, Hopcroft's minimisation with the merge of the
-// byte classes whose columns have become equal.  Both builders accept the same language, refuse the same forms and meet the same
+// byte classes whose columns have become equal.  All builders accept the same language, refuse the same forms and meet the same
 // limits with the same texts because they are these functions.  No HIP header: the test-only harnesses compile it with g++.
 #pragma once
 #include <stdint.h>
@@ -241,7 +241,7 @@ inline uint64_t unrolled(const std::vector<Node>& nodes, uint32_t n) {
 }
 
 enum NfaKind : uint8_t { nChar, nSplit, nBol, nEol, nAccept };
-struct NfaNode { NfaKind kind; uint32_t set, a, b; };
+struct NfaNode { NfaKind kind; uint32_t set, a, b; };     // nAccept: `set` is the pattern's index where every pattern has its own (Front)
 
 struct Nfa {
     std::vector<NfaNode> n;
@@ -288,8 +288,9 @@ struct Nfa {
 };
 
 // what is reached from NFA nodes without a byte: the byte nodes, and whether the string is accepted here whatever follows
-// (`always`) or if it ends here (`at_end`: through a `$`)
-struct Closure { std::vector<uint32_t> chars; bool always = false, at_end = false; };
+// (`always`) or if it ends here (`at_end`: through a `$`); `here` and `end` say the same per accept node: bit p for pattern p's
+// (bit 0 alone where the NFA has one accept for all)
+struct Closure { std::vector<uint32_t> chars; bool always = false, at_end = false; uint64_t here = 0, end = 0; };
 
 struct Closer {
     const Nfa& nfa;
@@ -312,7 +313,10 @@ struct Closer {
             case nSplit: stack.push_back({ N.b, mode }); stack.push_back({ N.a, mode }); break;
             case nBol: if (at_start) stack.push_back({ N.a, mode }); break;
             case nEol: stack.push_back({ N.a, 1 }); break;
-            case nAccept: if (mode) out->at_end = true; else out->always = true; break;
+            case nAccept:
+                if (mode) { out->at_end = true; out->end |= (uint64_t)1 << N.set; }
+                else { out->always = true; out->here |= (uint64_t)1 << N.set; }
+                break;
             }
         }
         std::sort(out->chars.begin(), out->chars.end());
@@ -333,7 +337,8 @@ constexpr uint32_t kEndMark = 0xFFFFFFFFu;               // in a subset's key: i
 constexpr uint64_t kSubsetEntries = (uint64_t)32 << 20;  // the subsets' entries all together: a bound on the construction's memory
 
 // Steps 1 to 3 — the trees, the positions, the NFA with one accept and every pattern an alternative — and the byte classes of the
-// construction: the bytes that no set tells apart.
+// construction: the bytes that no set tells apart.  accept_per_pattern (set before front_build; the regex set and the extraction
+// leave it alone): every pattern ends in an accept node of its own that carries the pattern's index.
 struct Front {
     std::vector<ByteSet> sets;
     Nfa nfa;
@@ -341,6 +346,7 @@ struct Front {
     uint32_t K = 1;          // construction classes
     uint8_t cls[256] = {};   // byte -> construction class
     uint8_t rep[256] = {};   // construction class -> its lowest byte
+    bool accept_per_pattern = false;
 };
 
 // SX_OK, or SX_E_INVALID with *err said: a bad count, flag, length or pointer, a refused pattern, a limit on repeats or positions.
@@ -371,12 +377,18 @@ inline int front_build(const sx_pattern* patterns, uint32_t n_patterns, uint32_t
     }
     // 3. the NFA: one accept, every pattern an alternative
     Nfa& nfa = F->nfa;
-    nfa.most = (size_t)positions + n_patterns;      // the accept, the patterns' nodes, a branch per pattern but one
+    // the accept (or one per pattern), the patterns' nodes, a branch per pattern but one
+    nfa.most = (size_t)positions + n_patterns + (F->accept_per_pattern ? n_patterns - 1 : 0);
     nfa.n.reserve(nfa.most);
     try {
-        const uint32_t accept = nfa.add(nAccept, 0, 0, 0);
+        const bool per = F->accept_per_pattern;
+        uint32_t accept = nfa.add(nAccept, per ? n_patterns - 1 : 0, 0, 0);
         uint32_t start = nfa.build(nodes, roots.back(), accept);
-        for (size_t p = roots.size() - 1; p-- > 0;) { const uint32_t one = nfa.build(nodes, roots[p], accept); start = nfa.add(nSplit, 0, one, start); }
+        for (size_t p = roots.size() - 1; p-- > 0;) {
+            if (per) accept = nfa.add(nAccept, (uint32_t)p, 0, 0);
+            const uint32_t one = nfa.build(nodes, roots[p], accept);
+            start = nfa.add(nSplit, 0, one, start);
+        }
         F->start = start;
     } catch (const Refused& r) {
         return fail(err, std::string("internal: ") + r.why);
@@ -402,18 +414,21 @@ inline int front_build(const sx_pattern* patterns, uint32_t n_patterns, uint32_t
 }
 
 // Step 5.  The minimal automaton of a complete DFA D[s * K + c] over n states whose states are told apart by `kinds` (values below
-// n_kinds) to begin with: Hopcroft's blocks of states that no string tells apart, the quotient, then the byte classes whose columns
+// n_kinds; Kind: uint8_t for the regex set and the extraction, uint32_t where there may be more than 256 of them) to begin with: Hopcroft's blocks of states that no string tells apart, the quotient, then the byte classes whose columns
 // are equal in every block, numbered by their lowest byte.
-struct Quotient {
+template <class Kind>
+struct QuotientOf {
     uint32_t M = 0;                   // blocks
     std::vector<uint32_t> blk;        // state -> block
-    std::vector<uint8_t> kind;        // block -> its states' kind
+    std::vector<Kind> kind;           // block -> its states' kind
     std::vector<uint32_t> Q;          // Q[B * K + c]: block, construction class -> block
     std::vector<uint32_t> first_of;   // final class -> a construction class of it
     uint8_t map[256] = {};            // byte -> final class
 };
+using Quotient = QuotientOf<uint8_t>;
 
-inline void minimise(uint32_t n, uint32_t K, const std::vector<uint32_t>& D, const std::vector<uint8_t>& kinds, uint32_t n_kinds, const uint8_t* cls, Quotient* out) {
+template <class Kind>
+inline void minimise(uint32_t n, uint32_t K, const std::vector<uint32_t>& D, const std::vector<Kind>& kinds, uint32_t n_kinds, const uint8_t* cls, QuotientOf<Kind>* out) {
     std::vector<uint32_t> elems(n), loc(n), blk(n), bbeg, bend, marked;
     {
         std::vector<uint32_t> at(n_kinds + 1, 0);

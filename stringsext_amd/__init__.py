@@ -447,46 +447,30 @@ class Result:
         Labels of another Result: SxError SX_E_INVALID."""
         if isinstance(patterns, ExtractSet):
             raise TypeError("select_device takes patterns, a PatternSet, a RegexSet or Labels; an ExtractSet goes to extract_device")
-        if isinstance(patterns, Labels):
-            if ignore_case or invert:
-                raise ValueError("a selection by Labels takes the masks any, all and none: the fold belongs to the LabelSet, and `none` inverts")
+        if isinstance(patterns, (Labels, RegexSet, PatternSet)):
+            if isinstance(patterns, Labels):
+                if ignore_case or invert:
+                    raise ValueError("a selection by Labels takes the masks any, all and none: the fold belongs to the LabelSet, and `none` inverts")
+                entry, args = "sx_result_select_labels_device", (any, all, none)
+            else:
+                if any or all or none:
+                    raise ValueError("the masks any, all and none select by Labels (Result.label_device)")
+                if ignore_case:
+                    raise ValueError("ignore_case belongs to the %s: Scanner.%s(patterns, ignore_case=True)" % (type(patterns).__name__, patterns._maker))
+                entry, args = patterns._select, (SX_SELECT_INVERT if invert else 0,)
             if not self._s.h:
                 raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
-            if not patterns.h:
-                raise SxError(SX_E_INVALID, "the Labels have been freed")
             out = C.c_void_p()
-            self._s._chk(lib().sx_result_select_labels_device(self._s.h, self.h, patterns.h, any, all, none, C.byref(out)))
+            self._s._chk(getattr(lib(), entry)(self._s.h, self.h, patterns._handle(), *args, C.byref(out)))
             return Result(self._s, out)
         if any or all or none:
             raise ValueError("the masks any, all and none select by Labels (Result.label_device)")
-        if isinstance(patterns, RegexSet):
-            if ignore_case:
-                raise ValueError("ignore_case belongs to the RegexSet: Scanner.regex_set(patterns, ignore_case=True)")
-            if not self._s.h:
-                raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
-            if not patterns.h:
-                raise SxError(SX_E_INVALID, "the RegexSet has been freed")
-            out = C.c_void_p()
-            self._s._chk(lib().sx_result_select_regex_device(self._s.h, self.h, patterns.h, SX_SELECT_INVERT if invert else 0, C.byref(out)))
-            return Result(self._s, out)
-        if isinstance(patterns, PatternSet):
-            if ignore_case:
-                raise ValueError("ignore_case belongs to the PatternSet: Scanner.pattern_set(patterns, ignore_case=True)")
-            if not self._s.h:
-                raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
-            if not patterns.h:
-                raise SxError(SX_E_INVALID, "the PatternSet has been freed")
-            out = C.c_void_p()
-            self._s._chk(lib().sx_result_select_set_device(self._s.h, self.h, patterns.h, SX_SELECT_INVERT if invert else 0, C.byref(out)))
-            return Result(self._s, out)
         if not self._s.h:
             raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
-        pats = [patterns] if isinstance(patterns, (bytes, bytearray, memoryview)) else list(patterns)
-        pats = [bytes(p) for p in pats]
-        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        arr, n = _pattern_array([patterns] if isinstance(patterns, (bytes, bytearray, memoryview)) else patterns)
         flags = (SX_SELECT_ASCII_NOCASE if ignore_case else 0) | (SX_SELECT_INVERT if invert else 0)
         out = C.c_void_p()
-        self._s._chk(lib().sx_result_select_device(self._s.h, self.h, arr, len(pats), flags, C.byref(out)))
+        self._s._chk(lib().sx_result_select_device(self._s.h, self.h, arr, n, flags, C.byref(out)))
         return Result(self._s, out)
 
     def extract_device(self, extract_set):
@@ -547,24 +531,33 @@ class Result:
             pass
 
 
-class PatternSet:
-    """A keyword list compiled for the device (sx_select_set_create; Scanner.pattern_set makes it): Result.select_device() takes it
-    in place of a list, on result after result.  It owns its device memory: free() it before or after the Scanner's close()."""
+class _DeviceHandle:
+    """What the compiled sets and the Labels share: `h`, a handle of the library that owns device memory until free().  A class
+    names its free function (_free) and, if it has one, its info function and struct (_info_get, _info_type)."""
+    _free = _info_get = _info_type = _freed = None
 
     def __init__(self, handle):
         self.h = handle
 
-    def info(self):
-        """sx_select_set_info as a dict: n_patterns, states, classes, nocase, table_bytes (in HBM), lds_states"""
-        i = SelectSetInfo()
-        rc = lib().sx_select_set_info_get(self.h, C.byref(i))
+    def _handle(self):
+        if not self.h:
+            raise SxError(SX_E_INVALID, self._freed or "the %s has been freed" % type(self).__name__)
+        return self.h
+
+    def _info(self):
+        i = self._info_type()
+        rc = getattr(lib(), self._info_get)(self._handle(), C.byref(i))
         if rc != SX_OK:
-            raise SxError(rc, "the PatternSet has been freed")
-        return {k: getattr(i, k) for k, _ in SelectSetInfo._fields_ if k != "reserved"}
+            raise SxError(rc, self._info_get)
+        return i
+
+    def _info_dict(self):
+        i = self._info()
+        return {k: getattr(i, k) for k, _ in self._info_type._fields_ if k != "reserved"}
 
     def free(self):
         if self.h:
-            lib().sx_select_set_free(self.h)
+            getattr(lib(), self._free)(self.h)
             self.h = None
 
     def __del__(self):
@@ -574,82 +567,62 @@ class PatternSet:
             pass
 
 
-class RegexSet:
+def _pattern_array(patterns):
+    """(an array of sx_pattern, its length) for a list of bytes-like patterns; the array keeps the bytes alive"""
+    pats = [bytes(p) for p in patterns]
+    return (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats]), len(pats)
+
+
+class PatternSet(_DeviceHandle):
+    """A keyword list compiled for the device (sx_select_set_create; Scanner.pattern_set makes it): Result.select_device() takes it
+    in place of a list, on result after result.  It owns its device memory: free() it before or after the Scanner's close()."""
+
+    _free, _info_get, _info_type = "sx_select_set_free", "sx_select_set_info_get", SelectSetInfo
+    _select, _maker = "sx_result_select_set_device", "pattern_set"
+
+    def info(self):
+        """sx_select_set_info as a dict: n_patterns, states, classes, nocase, table_bytes (in HBM), lds_states"""
+        return self._info_dict()
+
+
+class RegexSet(_DeviceHandle):
     """Byte regular expressions compiled for the device (sx_select_regex_create; Scanner.regex_set makes it): Result.select_device()
     takes it in place of a list, on result after result.  It owns its device memory: free() it before or after the Scanner's
     close()."""
 
-    def __init__(self, handle):
-        self.h = handle
+    _free, _info_get, _info_type = "sx_select_regex_free", "sx_select_regex_info_get", SelectRegexInfo
+    _select, _maker = "sx_result_select_regex_device", "regex_set"
 
     def info(self):
         """sx_select_regex_info as a dict: n_patterns, states, classes, nocase, table_bytes (in HBM), lds_states, end_states"""
-        i = SelectRegexInfo()
-        rc = lib().sx_select_regex_info_get(self.h, C.byref(i))
-        if rc != SX_OK:
-            raise SxError(rc, "the RegexSet has been freed")
-        return {k: getattr(i, k) for k, _ in SelectRegexInfo._fields_}
-
-    def free(self):
-        if self.h:
-            lib().sx_select_regex_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        return self._info_dict()
 
 
-class ExtractSet:
+class ExtractSet(_DeviceHandle):
     """Byte regular expressions compiled for the extraction on the device (sx_extract_regex_create; Scanner.extract_set makes it):
     Result.extract_device() takes it, on result after result.  It owns its device memory: free() it before or after the Scanner's
     close()."""
 
-    def __init__(self, handle):
-        self.h = handle
+    _free, _info_get, _info_type = "sx_extract_regex_free", "sx_extract_regex_info_get", ExtractRegexInfo
 
     def info(self):
         """sx_extract_regex_info as a dict: n_patterns, states, classes, nocase, table_bytes (in HBM), lds_states"""
-        i = ExtractRegexInfo()
-        rc = lib().sx_extract_regex_info_get(self.h, C.byref(i))
-        if rc != SX_OK:
-            raise SxError(rc, "the ExtractSet has been freed")
-        return {k: getattr(i, k) for k, _ in ExtractRegexInfo._fields_ if k != "reserved"}
-
-    def free(self):
-        if self.h:
-            lib().sx_extract_regex_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        return self._info_dict()
 
 
-class TallySet:
+class TallySet(_DeviceHandle):
     """A keyword list compiled for counting on the device (sx_tally_set_create; Scanner.tally_set makes it), with its counters:
     Result.tally_device() adds a result's hits to them, on result after result.  It owns its device memory: free() it before or
     after the Scanner's close()."""
 
+    _free, _info_get, _info_type = "sx_tally_set_free", "sx_tally_set_info_get", TallySetInfo
+
     def __init__(self, handle, n_patterns):
         self.h, self.n_patterns = handle, n_patterns
 
-    def _handle(self):
-        if not self.h:
-            raise SxError(SX_E_INVALID, "the TallySet has been freed")
-        return self.h
-
     def info(self):
         """sx_tally_set_info as a dict: n_patterns, unique, states, classes, nocase, entry_bytes, table_bytes (in HBM), lds_states"""
-        i = TallySetInfo()
-        rc = lib().sx_tally_set_info_get(self._handle(), C.byref(i))
-        if rc != SX_OK:
-            raise SxError(rc, "sx_tally_set_info_get")
-        return {k: getattr(i, k) for k, _ in TallySetInfo._fields_ if k != "reserved"}
+        return self._info_dict()
 
     def read(self):
         """(hits, first): two lists with an entry per input pattern; first[k] is SX_TALLY_NEVER where hits[k] is 0"""
@@ -674,39 +647,21 @@ class TallySet:
             raise SxError(rc, "sx_tally_set_counters_device")
         return h.value, f.value, m.value, u.value
 
-    def free(self):
-        if self.h:
-            lib().sx_tally_set_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class LabelSet:
+class LabelSet(_DeviceHandle):
     """Byte regular expressions compiled for labelling on the device (sx_label_set_create; Scanner.label_set makes it), with their
     counters: Result.label_device() says which of them every finding holds and adds to the counters, on result after result.  It owns
     its device memory: free() it before or after the Scanner's close()."""
 
+    _free, _info_get, _info_type = "sx_label_set_free", "sx_label_set_info_get", LabelSetInfo
+
     def __init__(self, handle, n_patterns):
         self.h, self.n_patterns = handle, n_patterns
-
-    def _handle(self):
-        if not self.h:
-            raise SxError(SX_E_INVALID, "the LabelSet has been freed")
-        return self.h
 
     @property
     def info(self):
         """a LabelSetInfo (sx_label_set_info): n_patterns, states, classes, nocase, table_bytes (in HBM), lds_states, here_states"""
-        i = LabelSetInfo()
-        rc = lib().sx_label_set_info_get(self._handle(), C.byref(i))
-        if rc != SX_OK:
-            raise SxError(rc, "sx_label_set_info_get")
-        return i
+        return self._info()
 
     def read(self):
         """(findings, first): two lists with an entry per pattern; first[p] is SX_LABEL_NEVER where findings[p] is 0"""
@@ -730,35 +685,24 @@ class LabelSet:
             raise SxError(rc, "sx_label_set_counters_device")
         return f.value, m.value
 
-    def free(self):
-        if self.h:
-            lib().sx_label_set_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class Labels:
+class Labels(_DeviceHandle):
     """One Result's labels in HBM (sx_result_label_device; Result.label_device makes them): a 64-bit word per finding, an array per
     segment of the Result.  Result.select_device() of the SAME Result takes them with the masks any, all, none.  They own their
     device memory: free() them before or after the Scanner's close()."""
+
+    _free, _freed = "sx_labels_free", "the Labels have been freed"
 
     def __init__(self, scanner, handle):
         self._s, self.h = scanner, handle
 
     def device_segments(self):
         """[(device pointer to the segment's labels, n findings)] per segment of the source"""
-        if not self.h:
-            raise SxError(SX_E_INVALID, "the Labels have been freed")
-        L = lib()
+        L, h = lib(), self._handle()
         out = []
-        for i in range(L.sx_labels_segments(self.h)):
+        for i in range(L.sx_labels_segments(h)):
             p, n = C.c_void_p(), C.c_uint64()
-            rc = L.sx_labels_segment_device(self.h, i, C.byref(p), C.byref(n))
+            rc = L.sx_labels_segment_device(h, i, C.byref(p), C.byref(n))
             if rc != SX_OK:
                 raise SxError(rc, "sx_labels_segment_device")
             out.append((p.value, n.value))
@@ -771,17 +715,6 @@ class Labels:
             raw = self._s.download(p, n * 8) if n else b""
             out.append(list((C.c_uint64 * n).from_buffer_copy(raw)) if n else [])
         return out
-
-    def free(self):
-        if self.h:
-            lib().sx_labels_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 class Scanner:
@@ -819,40 +752,36 @@ class Scanner:
     def pattern_set(self, patterns, ignore_case=False):
         """sx_select_set_create: `patterns` (1..65536 bytes objects of 1..255 bytes, 1 MiB in all; duplicates allowed) compiled into
         an automaton in HBM on this Scanner's device, for Result.select_device().  ignore_case: 'A'..'Z' as 'a'..'z', compiled in."""
-        pats = [bytes(p) for p in patterns]
-        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        arr, n = _pattern_array(patterns)
         out = C.c_void_p()
-        self._chk(lib().sx_select_set_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        self._chk(lib().sx_select_set_create(self.h, arr, n, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
         return PatternSet(out)
 
     def tally_set(self, patterns, ignore_case=False):
         """sx_tally_set_create: `patterns` (the limits of pattern_set) compiled into an automaton with output links and two counters
         per keyword in HBM on this Scanner's device, for Result.tally_device().  ignore_case: 'A'..'Z' as 'a'..'z', compiled in."""
-        pats = [bytes(p) for p in patterns]
-        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        arr, n = _pattern_array(patterns)
         out = C.c_void_p()
-        self._chk(lib().sx_tally_set_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
-        return TallySet(out, len(pats))
+        self._chk(lib().sx_tally_set_create(self.h, arr, n, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        return TallySet(out, n)
 
     def regex_set(self, patterns, ignore_case=False):
         """sx_select_regex_create: `patterns` (1..64 bytes objects of 1..1024 bytes: the byte regex language of
         include/stringsext_amd.h, which means what Python's `re` means with `$` read as `\\Z`) compiled into one DFA in HBM on this
         Scanner's device, for Result.select_device().  ignore_case: re.IGNORECASE on a bytes pattern, compiled in.  A refused
         pattern raises SxError (SX_E_INVALID) whose text names the pattern's index, the offset and the reason."""
-        pats = [bytes(p) for p in patterns]
-        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        arr, n = _pattern_array(patterns)
         out = C.c_void_p()
-        self._chk(lib().sx_select_regex_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        self._chk(lib().sx_select_regex_create(self.h, arr, n, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
         return RegexSet(out)
 
     def extract_set(self, patterns, ignore_case=False):
         """sx_extract_regex_create: `patterns` (the language and the limits of regex_set) compiled into one anchored DFA in HBM on
         this Scanner's device, for Result.extract_device().  ignore_case: re.IGNORECASE on a bytes pattern, compiled in.  A refused
         pattern raises SxError (SX_E_INVALID) whose text names the pattern's index, the offset and the reason."""
-        pats = [bytes(p) for p in patterns]
-        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        arr, n = _pattern_array(patterns)
         out = C.c_void_p()
-        self._chk(lib().sx_extract_regex_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        self._chk(lib().sx_extract_regex_create(self.h, arr, n, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
         return ExtractSet(out)
 
     def label_set(self, patterns, ignore_case=False):
@@ -860,11 +789,10 @@ class Scanner:
         one DFA with a mask per state in HBM on this Scanner's device, with two counters per pattern, for Result.label_device().
         ignore_case: re.IGNORECASE on a bytes pattern, compiled in.  A refused pattern raises SxError (SX_E_INVALID) whose text names
         the pattern's index, the offset and the reason."""
-        pats = [bytes(p) for p in patterns]
-        arr = (Pattern * max(1, len(pats)))(*[Pattern(p, len(p)) for p in pats])
+        arr, n = _pattern_array(patterns)
         out = C.c_void_p()
-        self._chk(lib().sx_label_set_create(self.h, arr, len(pats), SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
-        return LabelSet(out, len(pats))
+        self._chk(lib().sx_label_set_create(self.h, arr, n, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        return LabelSet(out, n)
 
     def scan(self, data, file_id=-1, is_last=False):
         """sx_scan: replaces the loop src/main.rs:153-168 for one chunk held in host memory."""

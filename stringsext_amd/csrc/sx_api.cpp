@@ -1,79 +1,9 @@
 // sx_api.cpp — the C-ABI of include/stringsext_amd.h: context and HIP resources, the lower-level
-// stages as entry points, results, utilities.  (sx_scan* live in sx_ingest.cpp.)
+// stages as entry points, results on the host, utilities.  (sx_scan* live in sx_ingest.cpp; what works on a result in HBM, in
+// sx_result_api.cpp.)
 #include "sx_ctx.hpp"
-#include "sx_print_core.hpp"
-#include "sx_select_core.hpp"
-#include "sx_selset_build.hpp"
-#include "sx_selset_core.hpp"
-#include "sx_selre_build.hpp"
-#include "sx_selre_core.hpp"
-#include "sx_extract_build.hpp"
-#include "sx_extract_core.hpp"
-#include "sx_seltally_build.hpp"
-#include "sx_seltally_core.hpp"
-#include "sx_label_build.hpp"
-#include "sx_label_core.hpp"
 
 using namespace sx;
-
-// sx_select_set_create: a compiled keyword list; `mem` = [the class map][the table], device memory of its own
-struct sx_select_set {
-    int device = 0;
-    uint8_t* mem = nullptr;
-    SelsetDevice dev{};
-    sx_select_set_info info{};
-};
-
-// sx_select_regex_create: compiled regular expressions; `mem` as a set's
-struct sx_select_regex {
-    int device = 0;
-    uint8_t* mem = nullptr;
-    SelreDevice dev{};
-    sx_select_regex_info info{};
-};
-
-// sx_extract_regex_create: regular expressions compiled for the extraction; `mem` as a set's
-struct sx_extract_regex {
-    int device = 0;
-    uint8_t* mem = nullptr;
-    ExtractDevice dev{};
-    sx_extract_regex_info info{};
-};
-
-// sx_tally_set_create: a keyword list compiled for the tally; `mem` = [the class map][the table][own][dict][pattern -> unique id]
-// [hits][first], device memory of its own
-struct sx_tally_set {
-    int device = 0;
-    uint8_t* mem = nullptr;
-    SeltallyDevice dev{};
-    const uint32_t* d_unique_of_pattern = nullptr;
-    std::vector<uint32_t> unique_of_pattern;
-    sx_tally_set_info info{};
-};
-
-// sx_label_set_create: regular expressions compiled for the labels; `mem` = [the class map][the table][here][end][findings][first],
-// device memory of its own
-struct sx_label_set {
-    int device = 0;
-    uint8_t* mem = nullptr;
-    LabelDevice dev{};
-    sx_label_set_info info{};
-};
-
-// sx_result_label_device: one result's labels; `mem` = an array per source segment, each 256-byte aligned, device memory of its own.
-// Per segment what tells the source apart: where its records lie, how many they are, and the epoch of its block when it was labelled.
-struct sx_labels {
-    struct Seg {
-        const uint64_t* d = nullptr;
-        const void* recs = nullptr;
-        uint64_t n = 0;
-        std::shared_ptr<std::atomic<uint64_t>> epoch_ref;
-        uint64_t epoch = 0;
-    };
-    int device = 0;
-    uint8_t* mem = nullptr;
-    std::vector<Seg> segs;
-};
 
 namespace sx {
 PinnedPool::Block PinnedPool::take(size_t bytes) {
@@ -250,6 +180,15 @@ static int fetch_to_host(sx_result* r, MissionFindings& s) {
     if (hipMemcpy(blk.p, s.dev_copy, bytes, hipMemcpyDeviceToHost) != hipSuccess) { r->r.pool->give(blk); return SX_E_HIP; }
     s.ext = blk; s.dev_only = false;
     return SX_OK;
+}
+void fill_segment_info(const MissionFindings& s, sx_segment_info* info) {
+    memset(info, 0, sizeof *info);
+    info->packed = s.packed ? 1 : 0;
+    info->input_file_id = -1;
+    if (s.packed && s.info) {
+        info->input_file_id = s.info->file_id; info->slice_base = s.info->slice_base;
+        memcpy(info->position0, s.info->pos0, sizeof info->position0);
+    }
 }
 static int fetch_all_to_host(const sx_result* r) {
     sx_result* w = const_cast<sx_result*>(r);
@@ -623,39 +562,7 @@ int sx_result_segment_packed(const sx_result* r, uint64_t i, const void** findin
     if (arena) *arena = (const uint8_t*)s.strings();
     if (arena_len) *arena_len = s.strings_len();
     if (packed) *packed = s.packed ? 1 : 0;
-    if (info) {
-        memset(info, 0, sizeof *info);
-        info->packed = s.packed ? 1 : 0;
-        info->input_file_id = -1;
-        if (s.packed && s.info) {
-            info->input_file_id = s.info->file_id; info->slice_base = s.info->slice_base;
-            memcpy(info->position0, s.info->pos0, sizeof info->position0);
-        }
-    }
-    return SX_OK;
-}
-int sx_result_segment_device(const sx_result* r, uint64_t i, const void** d_records, uint64_t* n_findings, const uint8_t** d_arena,
-                             uint64_t* arena_len, int* packed, sx_segment_info* info) {
-    if (!r || i >= r->r.segs.size()) return SX_E_INVALID;
-    const MissionFindings& s = r->r.segs[(size_t)i];
-    if (d_records) *d_records = nullptr;
-    if (d_arena) *d_arena = nullptr;
-    if (n_findings) *n_findings = s.count();
-    if (arena_len) *arena_len = s.strings_len();
-    if (packed) *packed = s.packed ? 1 : 0;
-    if (info) {
-        memset(info, 0, sizeof *info);
-        info->packed = s.packed ? 1 : 0;
-        info->input_file_id = -1;
-        if (s.packed && s.info) {
-            info->input_file_id = s.info->file_id; info->slice_base = s.info->slice_base;
-            memcpy(info->position0, s.info->pos0, sizeof info->position0);
-        }
-    }
-    if (!s.dev_only) return SX_OK;   // (in host memory: the host accessors)
-    if (!s.keep_on_device || !s.dev_epoch_ref || s.dev_epoch_ref->load() != s.dev_epoch) return SX_E_STATE;
-    if (d_records) *d_records = s.dev_copy;
-    if (d_arena) *d_arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size();
+    if (info) fill_segment_info(s, info);
     return SX_OK;
 }
 // The contiguous view: joins the segments on first use (a copy; none if there is one segment).
@@ -683,636 +590,6 @@ int sx_print_findings(const sx_ctx* ctx, const sx_result* r, int n_inputs, int r
     memcpy(*out, s.data(), s.size());
     *out_len = s.size();
     return SX_OK;
-}
-
-// What sx_print_findings_device and sx_result_select_device ask of a result: every segment in HBM, in memory of this context — the result
-// block of the last scan call or one of the two selection blocks — that has not been written again since.
-static int result_on_device(sx_ctx* ctx, const sx_result* r, const char* host_call) {
-    const std::string in_host = std::string("the result is in host memory: ") + host_call;
-    if (r->r.segs.empty()) { ctx->set_err(in_host); return SX_E_STATE; }
-    for (const MissionFindings& s : r->r.segs) {
-        if (!s.dev_only || !s.keep_on_device || s.ext_nf == 0) { ctx->set_err(in_host); return SX_E_STATE; }
-        const bool ours = s.dev_epoch_ref && (s.dev_epoch_ref == ctx->dev_epoch || s.dev_epoch_ref == ctx->select_epoch[0] || s.dev_epoch_ref == ctx->select_epoch[1]);
-        if (!ours || s.dev_epoch_ref->load() != s.dev_epoch) {
-            ctx->set_err("a later scan or selection has reused the result's device memory");
-            return SX_E_STATE;
-        }
-    }
-    return SX_OK;
-}
-
-// Finding::print where the findings lie (sx_print_dev.hip): pass 1 of every segment, one wait for the segments' text bytes, the text
-// block, pass 2 of every segment at its 64-bit base, one more wait.  The result is read, never moved.
-int sx_print_findings_device(sx_ctx* ctx, const sx_result* r, int n_inputs, int radix, int no_metadata, const uint8_t** d_text,
-                             uint64_t* text_len) {
-    if (d_text) *d_text = nullptr;
-    if (text_len) *text_len = 0;
-    if (!ctx || !r || !d_text || !text_len) return SX_E_INVALID;
-    if (radix != 0 && radix != 'x' && radix != 'd' && radix != 'o') { ctx->set_err("radix must be 0, 'x', 'd' or 'o'"); return SX_E_INVALID; }
-    if (ctx->host_only) { ctx->set_err("host-only context: no device print"); return SX_E_STATE; }
-    { const int rc = result_on_device(ctx, r, "sx_print_findings"); if (rc != SX_OK) return rc; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->post_stream;
-    if (!ctx->d_print_missions) {
-        std::vector<PrintMission> tab(256);
-        memset(tab.data(), 0, tab.size() * sizeof(PrintMission));
-        for (size_t k = ctx->missions.size(); k-- > 0;) {   // (print_findings takes the first Mission of an id)
-            const Mission& m = ctx->missions[k];
-            const char* name = m.c.print_encoding_as_ascii ? "ascii" : m.encoding_name();
-            const std::string label = name ? name : "";
-            PrintMission& t = tab[m.c.mission_id];
-            if (label.size() > sizeof t.label) { ctx->set_err("encoding label longer than 14 bytes"); return SX_E_STATE; }
-            t.present = 1; t.len = (uint8_t)label.size();
-            memcpy(t.label, label.data(), label.size());
-        }
-        uint8_t* p = nullptr;
-        if (hipMalloc((void**)&p, tab.size() * sizeof(PrintMission)) != hipSuccess) { (void)hipGetLastError(); ctx->set_err("device print: no memory for the Mission table"); return SX_E_NOMEM; }
-        const hipError_t e = hipMemcpy(p, tab.data(), tab.size() * sizeof(PrintMission), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(p); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
-        ctx->d_print_missions = p;
-    }
-    const size_t ns = r->r.segs.size();
-    uint64_t scratch = 0;
-    for (const MissionFindings& s : r->r.segs) scratch += print_scratch_bytes(s.ext_nf);
-    if (scratch > ctx->d_print_scratch_cap) {
-        if (ctx->d_print_scratch) (void)hipFree(ctx->d_print_scratch);
-        ctx->d_print_scratch = nullptr; ctx->d_print_scratch_cap = 0;
-        if (hipMalloc((void**)&ctx->d_print_scratch, scratch) != hipSuccess) { (void)hipGetLastError(); ctx->d_print_scratch = nullptr; ctx->set_err("device print: no memory for the offsets"); return SX_E_NOMEM; }
-        ctx->d_print_scratch_cap = scratch;
-    }
-    std::vector<PrintParams> P(ns);
-    std::vector<const uint64_t*> d_total(ns);
-    uint64_t at = 0;
-    for (size_t i = 0; i < ns; i++) {
-        const MissionFindings& s = r->r.segs[i];
-        PrintParams& p = P[i];
-        memset(&p, 0, sizeof p);
-        p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
-        p.file_id = s.packed && s.info ? s.info->file_id : -1;
-        p.several_inputs = n_inputs > 1; p.radix = (uint32_t)radix; p.no_metadata = no_metadata != 0; p.several_missions = ctx->missions.size() > 1;
-        p.missions = (const PrintMission*)ctx->d_print_missions;
-        const size_t bytes = print_scratch_bytes(s.ext_nf);
-        HIP_TRY(ctx, print_measure(p, ctx->d_print_scratch + at, bytes, st, &p.wbase, &d_total[i]));
-        at += bytes;
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    uint64_t total = 0;
-    for (size_t i = 0; i < ns; i++) {
-        uint64_t t = 0;
-        HIP_TRY(ctx, hipMemcpy(&t, d_total[i], sizeof t, hipMemcpyDeviceToHost));
-        P[i].base = total;
-        total += t;
-    }
-    if (total > ctx->d_text_cap) {
-        if (ctx->d_text) (void)hipFree(ctx->d_text);
-        ctx->d_text = nullptr; ctx->d_text_cap = 0;
-        if (hipMalloc((void**)&ctx->d_text, total) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->d_text = nullptr;
-            ctx->set_err("device print: no memory for " + std::to_string(total) + " bytes of text");
-            return SX_E_NOMEM;
-        }
-        ctx->d_text_cap = total;
-    }
-    for (size_t i = 0; i < ns; i++) {
-        P[i].text = ctx->d_text;
-        HIP_TRY(ctx, print_write(P[i], st));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    *d_text = ctx->d_text;
-    *text_len = total;
-    return SX_OK;
-}
-
-// (a grow-only device buffer of the selection: SX_E_NOMEM leaves it empty)
-static int grow_device(sx_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t bytes, const char* what) {
-    if (bytes <= *cap) return SX_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    if (hipMalloc((void**)p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        ctx->set_err(std::string("device select: no memory for ") + std::to_string(bytes) + " bytes of " + what);
-        return SX_E_NOMEM;
-    }
-    *cap = bytes;
-    return SX_OK;
-}
-
-// grep where the findings lie (sx_select_dev.hip), for the three entry points, whose arguments are checked: pass 1 of every segment —
-// select_match_kernel with `patterns`, selset_match_kernel with the compiled `set`, or selre_match_kernel with the compiled `re` —, one wait for the segments' totals, the
-// selection block, pass 2 of every segment that has selected findings, one more wait.  The source is read, never moved.
-// grep -o (sx_extract_dev.hip), for the fourth: with the compiled `ex` the two passes are extract_measure and extract_place, an output
-// record is a match, not a finding, and a segment may get more records than it had; the blocks, their turns and the epochs are the same.
-// By label (sx_label_dev.hip), for the fifth: with `labels` (made from r: checked here) and masks = { any, all, none } pass 1 is
-// label_pick_kernel, which reads no string byte; everything behind it is the selection's.
-static int select_on_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, const SelsetDevice* set, const SelreDevice* re, const ExtractDevice* ex, uint32_t flags, sx_result** out,
-                            const sx_labels* labels = nullptr, const uint64_t* masks = nullptr) {
-    if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
-    { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
-    if (labels) {
-        bool same = labels->segs.size() == r->r.segs.size();
-        for (size_t i = 0; same && i < labels->segs.size(); i++) {
-            const sx_labels::Seg& l = labels->segs[i];
-            const MissionFindings& s = r->r.segs[i];
-            same = l.recs == s.dev_copy && l.n == s.ext_nf && l.epoch_ref == s.dev_epoch_ref && l.epoch == s.dev_epoch;
-        }
-        if (!same) { ctx->set_err("the labels were not made from this result"); return SX_E_INVALID; }
-    }
-    // the block this call writes: a source that lies there was made two selections ago
-    const int slot = (int)(ctx->select_calls & 1u);
-    for (const MissionFindings& s : r->r.segs)
-        if (s.dev_epoch_ref == ctx->select_epoch[slot]) { ctx->set_err("this selection reuses the source's device memory: it was selected two calls ago"); return SX_E_STATE; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->post_stream;
-    const size_t ns = r->r.segs.size();
-    uint64_t scratch = 0;
-    for (const MissionFindings& s : r->r.segs) scratch += ex ? extract_scratch_bytes(s.ext_nf) : select_scratch_bytes(s.ext_nf);
-    { const int rc = grow_device(ctx, &ctx->d_select_scratch, &ctx->d_select_scratch_cap, scratch, "wavefront tables"); if (rc != SX_OK) return rc; }
-    std::vector<SelectParams> P(ex ? 0 : ns);
-    std::vector<ExtractParams> X(ex ? ns : 0);
-    std::vector<const uint32_t*> d_count(ns);
-    std::vector<const uint64_t*> d_count64(ns), d_bytes(ns);
-    uint64_t at = 0;
-    for (size_t i = 0; i < ns; i++) {
-        const MissionFindings& s = r->r.segs[i];
-        if (ex) {
-            ExtractParams& x = X[i];
-            memset(&x, 0, sizeof x);
-            x.recs = s.dev_copy; x.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); x.n = s.ext_nf; x.packed = s.packed ? 1u : 0u;
-            x.ex = *ex;
-            const size_t bytes = extract_scratch_bytes(s.ext_nf);
-            HIP_TRY(ctx, extract_measure(&x, ctx->d_select_scratch + at, bytes, st, &d_count64[i], &d_bytes[i]));
-            at += bytes;
-            continue;
-        }
-        SelectParams& p = P[i];
-        memset(&p, 0, sizeof p);
-        p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
-        if (set || re) p.pat.invert = (flags & SX_SELECT_INVERT) ? 1u : 0u;
-        else select_fill_patterns(&p.pat, patterns, n_patterns, flags);
-        const size_t bytes = select_scratch_bytes(s.ext_nf);
-        LabelPick pick{ nullptr, 0, 0, 0 };
-        if (labels) pick = LabelPick{ labels->segs[i].d, masks[0], masks[1], masks[2] };
-        HIP_TRY(ctx, select_measure(&p, set, re, ctx->d_select_scratch + at, bytes, st, &d_count[i], &d_bytes[i], labels ? &pick : nullptr));
-        at += bytes;
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::vector<uint64_t> n_sel(ns), b_sel(ns), base(ns);
-    uint64_t block = 0, scratch2 = 0;
-    for (size_t i = 0; i < ns; i++) {
-        uint64_t c = 0;
-        if (ex) HIP_TRY(ctx, hipMemcpy(&c, d_count64[i], sizeof c, hipMemcpyDeviceToHost));
-        else { uint32_t c32 = 0; HIP_TRY(ctx, hipMemcpy(&c32, d_count[i], sizeof c32, hipMemcpyDeviceToHost)); c = c32; }
-        HIP_TRY(ctx, hipMemcpy(&b_sel[i], d_bytes[i], sizeof(uint64_t), hipMemcpyDeviceToHost));
-        if (c >= 0xFFFFFFFFull) {      // (an extraction: a selection has no more records than its source)
-            ctx->set_err("segment " + std::to_string(i) + " has " + std::to_string(c) + " matches: more than the 32-bit counters of a segment hold");
-            return SX_E_INVALID;
-        }
-        n_sel[i] = c;
-        if (!c) continue;
-        base[i] = block;
-        block += (c * r->r.segs[i].rec_size() + b_sel[i] + 255) / 256 * 256;
-        scratch2 = std::max<uint64_t>(scratch2, ex ? extract_place_scratch_bytes(c) : select_place_scratch_bytes(c));
-    }
-    // from here on the call counts: the block of the selection before the last one is written again
-    ctx->select_epoch[slot]->fetch_add(1);
-    ctx->select_calls++;
-    ResultHolder res;
-    res.r->r.pool = ctx->pool;
-    if (block) {
-        { const int rc = grow_device(ctx, &ctx->d_select[slot], &ctx->d_select_cap[slot], block, "selected findings"); if (rc != SX_OK) return rc; }
-        { const int rc = grow_device(ctx, &ctx->d_select_scratch2, &ctx->d_select_scratch2_cap, scratch2, "string offsets"); if (rc != SX_OK) return rc; }
-        for (size_t i = 0; i < ns; i++) {
-            if (!n_sel[i]) continue;
-            const MissionFindings& s = r->r.segs[i];
-            uint8_t* recs = ctx->d_select[slot] + base[i];
-            if (ex) HIP_TRY(ctx, extract_place(X[i], recs, n_sel[i], recs + n_sel[i] * s.rec_size(), ctx->d_select_scratch2, extract_place_scratch_bytes(n_sel[i]), st));
-            else HIP_TRY(ctx, select_place(P[i], recs, n_sel[i], recs + n_sel[i] * s.rec_size(), ctx->d_select_scratch2, select_place_scratch_bytes(n_sel[i]), st));
-            MissionFindings o;
-            o.ext_nf = n_sel[i]; o.ext_na = b_sel[i]; o.dev_copy = recs; o.dev_only = true; o.keep_on_device = true;
-            o.dev_epoch_ref = ctx->select_epoch[slot]; o.dev_epoch = ctx->select_epoch[slot]->load();
-            o.packed = s.packed; o.info = s.info;
-            res.r->r.segs.push_back(std::move(o));
-        }
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    *out = res.release();
-    return SX_OK;
-}
-
-int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, uint32_t flags, sx_result** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !r || !patterns || !out) return SX_E_INVALID;
-    if (n_patterns < 1 || n_patterns > SX_SELECT_MAX_PATTERNS) { ctx->set_err("n_patterns must be 1..16"); return SX_E_INVALID; }
-    if (flags & ~(uint32_t)(SX_SELECT_ASCII_NOCASE | SX_SELECT_INVERT)) { ctx->set_err("unknown selection flags"); return SX_E_INVALID; }
-    for (int p = 0; p < n_patterns; p++)
-        if (!patterns[p].bytes || patterns[p].len < 1 || patterns[p].len > SX_SELECT_MAX_PATTERN_BYTES) { ctx->set_err("a pattern must have 1..64 bytes"); return SX_E_INVALID; }
-    return select_on_device(ctx, r, patterns, n_patterns, nullptr, nullptr, nullptr, flags, out);
-}
-
-int sx_select_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_set** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !patterns || !out) return SX_E_INVALID;
-    SelsetTable T;
-    std::string err;
-    { const int rc = selset_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("pattern set: " + err); return rc; } }
-    if (ctx->host_only) { ctx->set_err("host-only context: no device for the pattern set"); return SX_E_STATE; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t table = (T.next.size() + 15) / 16 * 16;   // (selset_match_kernel copies the LDS rows in 16-byte chunks)
-    uint8_t* mem = nullptr;
-    if (hipMalloc((void**)&mem, sizeof T.map + table) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->set_err("pattern set: no device memory for " + std::to_string(sizeof T.map + table) + " bytes of table");
-        return SX_E_NOMEM;
-    }
-    hipError_t e = hipMemcpy(mem, T.map, sizeof T.map, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mem + sizeof T.map, T.next.data(), T.next.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(mem); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
-    sx_select_set* set = new (std::nothrow) sx_select_set;
-    if (!set) { (void)hipFree(mem); return SX_E_NOMEM; }
-    set->device = ctx->device; set->mem = mem;
-    set->dev = SelsetDevice{ mem, mem + sizeof T.map, T.states, T.classes, T.lds_states, T.matched, T.entry_bytes, 0 };
-    set->info = sx_select_set_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)T.next.size(), T.lds_states, 0 };
-    *out = set;
-    return SX_OK;
-}
-
-int sx_select_set_info_get(const sx_select_set* set, sx_select_set_info* out) {
-    if (!set || !out) return SX_E_INVALID;
-    *out = set->info;
-    return SX_OK;
-}
-
-void sx_select_set_free(sx_select_set* set) {
-    if (!set) return;
-    (void)hipFree(set->mem);
-    delete set;
-}
-
-int sx_result_select_set_device(sx_ctx* ctx, const sx_result* r, const sx_select_set* set, uint32_t flags, sx_result** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !r || !set || !out) return SX_E_INVALID;
-    if (flags & ~(uint32_t)SX_SELECT_INVERT) { ctx->set_err("a pattern set is selected with SX_SELECT_INVERT or no flag: the fold is compiled into the set"); return SX_E_INVALID; }
-    if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
-    if (set->device != ctx->device) { ctx->set_err("the pattern set lies on another device"); return SX_E_INVALID; }
-    return select_on_device(ctx, r, nullptr, 0, &set->dev, nullptr, nullptr, flags, out);
-}
-
-int sx_select_regex_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_regex** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !patterns || !out) return SX_E_INVALID;
-    SelreTable T;
-    std::string err;
-    { const int rc = selre_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("regex set: " + err); return rc; } }
-    if (ctx->host_only) { ctx->set_err("host-only context: no device for the regex set"); return SX_E_STATE; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = T.next.size() * sizeof(uint16_t), table = (bytes + 15) / 16 * 16;   // (selre_match_kernel copies the LDS rows in 16-byte chunks)
-    uint8_t* mem = nullptr;
-    if (hipMalloc((void**)&mem, sizeof T.map + table) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->set_err("regex set: no device memory for " + std::to_string(sizeof T.map + table) + " bytes of table");
-        return SX_E_NOMEM;
-    }
-    hipError_t e = hipMemcpy(mem, T.map, sizeof T.map, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mem + sizeof T.map, T.next.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(mem); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
-    sx_select_regex* re = new (std::nothrow) sx_select_regex;
-    if (!re) { (void)hipFree(mem); return SX_E_NOMEM; }
-    re->device = ctx->device; re->mem = mem;
-    re->dev = SelreDevice{ mem, (const uint16_t*)(mem + sizeof T.map), T.states, T.classes, T.lds_states, T.end_first, T.stop_first, T.matched, T.root_end, 0 };
-    re->info = sx_select_regex_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)bytes, T.lds_states, T.end_states };
-    *out = re;
-    return SX_OK;
-}
-
-int sx_select_regex_info_get(const sx_select_regex* re, sx_select_regex_info* out) {
-    if (!re || !out) return SX_E_INVALID;
-    *out = re->info;
-    return SX_OK;
-}
-
-void sx_select_regex_free(sx_select_regex* re) {
-    if (!re) return;
-    (void)hipFree(re->mem);
-    delete re;
-}
-
-int sx_result_select_regex_device(sx_ctx* ctx, const sx_result* r, const sx_select_regex* re, uint32_t flags, sx_result** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !r || !re || !out) return SX_E_INVALID;
-    if (flags & ~(uint32_t)SX_SELECT_INVERT) { ctx->set_err("a regex set is selected with SX_SELECT_INVERT or no flag: the fold is compiled into the set"); return SX_E_INVALID; }
-    if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
-    if (re->device != ctx->device) { ctx->set_err("the regex set lies on another device"); return SX_E_INVALID; }
-    return select_on_device(ctx, r, nullptr, 0, nullptr, &re->dev, nullptr, flags, out);
-}
-
-int sx_extract_regex_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_extract_regex** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !patterns || !out) return SX_E_INVALID;
-    ExtractTable T;
-    std::string err;
-    { const int rc = extract_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("extract set: " + err); return rc; } }
-    if (ctx->host_only) { ctx->set_err("host-only context: no device for the extract set"); return SX_E_STATE; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = T.next.size() * sizeof(uint16_t), table = (bytes + 15) / 16 * 16;   // (the kernels copy the LDS rows in 16-byte chunks)
-    uint8_t* mem = nullptr;
-    if (hipMalloc((void**)&mem, sizeof T.map + table) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->set_err("extract set: no device memory for " + std::to_string(sizeof T.map + table) + " bytes of table");
-        return SX_E_NOMEM;
-    }
-    hipError_t e = hipMemcpy(mem, T.map, sizeof T.map, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mem + sizeof T.map, T.next.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(mem); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
-    sx_extract_regex* ex = new (std::nothrow) sx_extract_regex;
-    if (!ex) { (void)hipFree(mem); return SX_E_NOMEM; }
-    ex->device = ctx->device; ex->mem = mem;
-    ex->dev = ExtractDevice{ mem, (const uint16_t*)(mem + sizeof T.map), T.states, T.classes, T.lds_states, T.end_first, T.here_first, T.dead_first, T.start0, T.start1 };
-    ex->info = sx_extract_regex_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)bytes, T.lds_states, 0 };
-    *out = ex;
-    return SX_OK;
-}
-
-int sx_extract_regex_info_get(const sx_extract_regex* ex, sx_extract_regex_info* out) {
-    if (!ex || !out) return SX_E_INVALID;
-    *out = ex->info;
-    return SX_OK;
-}
-
-void sx_extract_regex_free(sx_extract_regex* ex) {
-    if (!ex) return;
-    (void)hipFree(ex->mem);
-    delete ex;
-}
-
-int sx_result_extract_regex_device(sx_ctx* ctx, const sx_result* r, const sx_extract_regex* ex, uint32_t flags, sx_result** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !r || !ex || !out) return SX_E_INVALID;
-    if (flags) { ctx->set_err("an extraction takes no flag: the fold is compiled into the set"); return SX_E_INVALID; }
-    if (ctx->host_only) { ctx->set_err("host-only context: no device extraction"); return SX_E_STATE; }
-    if (ex->device != ctx->device) { ctx->set_err("the extract set lies on another device"); return SX_E_INVALID; }
-    return select_on_device(ctx, r, nullptr, 0, nullptr, nullptr, &ex->dev, flags, out);
-}
-
-int sx_tally_set_reset(sx_tally_set* set) {
-    if (!set) return SX_E_INVALID;
-    if (hipSetDevice(set->device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
-    hipError_t e = hipMemset(set->dev.hits, 0, (size_t)set->dev.unique * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMemset(set->dev.first, 0xFF, (size_t)set->dev.unique * sizeof(uint64_t));   // SX_TALLY_NEVER
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (a device memset may return before it is done, and the tally runs on a stream that does not wait for this one)
-    if (e != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
-    return SX_OK;
-}
-
-int sx_tally_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_tally_set** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !patterns || !out) return SX_E_INVALID;
-    SeltallyTable T;
-    std::string err;
-    { const int rc = seltally_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("tally set: " + err); return rc; } }
-    if (ctx->host_only) { ctx->set_err("host-only context: no device for the tally set"); return SX_E_STATE; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t table = (T.next.size() + 15) / 16 * 16;   // (seltally_kernel copies the LDS rows in 16-byte chunks)
-    const size_t per_state = (size_t)T.states * sizeof(uint32_t), map_words = (((size_t)T.n_patterns + 1) & ~(size_t)1) * sizeof(uint32_t);
-    const size_t counters = (size_t)T.unique * sizeof(uint64_t);
-    const size_t at_own = sizeof T.map + table, at_dict = at_own + per_state, at_map = at_dict + per_state;
-    const size_t at_hits = (at_map + map_words + 7) / 8 * 8, bytes = at_hits + 2 * counters;
-    uint8_t* mem = nullptr;
-    if (hipMalloc((void**)&mem, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->set_err("tally set: no device memory for " + std::to_string(bytes) + " bytes of tables and counters");
-        return SX_E_NOMEM;
-    }
-    hipError_t e = hipMemcpy(mem, T.map, sizeof T.map, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mem + sizeof T.map, T.next.data(), T.next.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mem + at_own, T.own.data(), per_state, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mem + at_dict, T.dict.data(), per_state, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mem + at_map, T.unique_of_pattern.data(), (size_t)T.n_patterns * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(mem); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
-    sx_tally_set* set = new (std::nothrow) sx_tally_set;
-    if (!set) { (void)hipFree(mem); return SX_E_NOMEM; }
-    set->device = ctx->device; set->mem = mem;
-    set->dev = SeltallyDevice{ mem, mem + sizeof T.map, (const uint32_t*)(mem + at_own), (const uint32_t*)(mem + at_dict),
-                               (uint64_t*)(mem + at_hits), (uint64_t*)(mem + at_hits + counters),
-                               T.states, T.classes, T.lds_states, T.entry_bytes, T.unique, T.unique < kSeltallyLdsIds ? T.unique : kSeltallyLdsIds };
-    set->d_unique_of_pattern = (const uint32_t*)(mem + at_map);
-    set->info = sx_tally_set_info{ T.n_patterns, T.unique, T.states, T.classes, T.nocase, T.entry_bytes,
-                                   (uint64_t)(sizeof T.map + T.next.size() + 2 * per_state + (size_t)T.n_patterns * sizeof(uint32_t)), T.lds_states, 0 };
-    set->unique_of_pattern = std::move(T.unique_of_pattern);
-    if (sx_tally_set_reset(set) != SX_OK) { ctx->set_err("tally set: the counters could not be reset"); sx_tally_set_free(set); return SX_E_HIP; }
-    *out = set;
-    return SX_OK;
-}
-
-int sx_tally_set_info_get(const sx_tally_set* set, sx_tally_set_info* out) {
-    if (!set || !out) return SX_E_INVALID;
-    *out = set->info;
-    return SX_OK;
-}
-
-void sx_tally_set_free(sx_tally_set* set) {
-    if (!set) return;
-    (void)hipFree(set->mem);
-    delete set;
-}
-
-// The tally where the findings lie (sx_seltally_dev.hip): the source is checked as a whole, then one kernel per segment, each with the
-// ordinal of its first record, on the selections' stream, and one wait.  Only the set's counters are written.
-int sx_result_tally_device(sx_ctx* ctx, const sx_result* r, sx_tally_set* set, uint64_t ordinal_base, uint64_t* n_findings) {
-    if (n_findings) *n_findings = 0;
-    if (!ctx || !r || !set) return SX_E_INVALID;
-    if (ctx->host_only) { ctx->set_err("host-only context: no device tally"); return SX_E_STATE; }
-    if (set->device != ctx->device) { ctx->set_err("the tally set lies on another device"); return SX_E_INVALID; }
-    { const int rc = result_on_device(ctx, r, "count on the host"); if (rc != SX_OK) return rc; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->post_stream;
-    uint64_t walked = 0;
-    for (const MissionFindings& s : r->r.segs) {
-        SeltallyParams p;
-        memset(&p, 0, sizeof p);
-        p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
-        p.ordinal = ordinal_base + walked;
-        p.set = set->dev;
-        HIP_TRY(ctx, seltally_launch(p, st));
-        walked += s.ext_nf;
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (n_findings) *n_findings = walked;
-    return SX_OK;
-}
-
-int sx_tally_set_read(const sx_tally_set* set, uint64_t* hits, uint64_t* first, uint32_t n_patterns) {
-    if (!set || n_patterns != set->info.n_patterns) return SX_E_INVALID;
-    if (hipSetDevice(set->device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
-    std::vector<uint64_t> u(set->dev.unique);
-    for (int k = 0; k < 2; k++) {
-        uint64_t* out = k ? first : hits;
-        if (!out) continue;
-        if (hipMemcpy(u.data(), k ? set->dev.first : set->dev.hits, u.size() * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
-        for (uint32_t p = 0; p < n_patterns; p++) out[p] = u[set->unique_of_pattern[p]];
-    }
-    return SX_OK;
-}
-
-int sx_tally_set_counters_device(const sx_tally_set* set, const uint64_t** d_hits, const uint64_t** d_first,
-                                 const uint32_t** d_unique_of_pattern, uint32_t* unique) {
-    if (!set) return SX_E_INVALID;
-    if (d_hits) *d_hits = set->dev.hits;
-    if (d_first) *d_first = set->dev.first;
-    if (d_unique_of_pattern) *d_unique_of_pattern = set->d_unique_of_pattern;
-    if (unique) *unique = set->dev.unique;
-    return SX_OK;
-}
-
-int sx_label_set_reset(sx_label_set* set) {
-    if (!set) return SX_E_INVALID;
-    if (hipSetDevice(set->device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
-    hipError_t e = hipMemset(set->dev.findings, 0, kLabelBits * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMemset(set->dev.first, 0xFF, kLabelBits * sizeof(uint64_t));   // SX_LABEL_NEVER
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (as sx_tally_set_reset: the labelling runs on a stream that does not wait for this one)
-    if (e != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
-    return SX_OK;
-}
-
-int sx_label_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_label_set** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !patterns || !out) return SX_E_INVALID;
-    LabelTable T;
-    std::string err;
-    { const int rc = label_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("label set: " + err); return rc; } }
-    if (ctx->host_only) { ctx->set_err("host-only context: no device for the label set"); return SX_E_STATE; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t next_bytes = T.next.size() * sizeof(uint16_t), table = (next_bytes + 15) / 16 * 16;   // (label_match_kernel copies the LDS rows in 16-byte chunks)
-    const size_t here_bytes = T.here.size() * sizeof(uint64_t), end_bytes = T.end.size() * sizeof(uint64_t), counters = kLabelBits * sizeof(uint64_t);
-    const size_t at_here = sizeof T.map + table, at_end = at_here + here_bytes, at_findings = at_end + end_bytes, bytes = at_findings + 2 * counters;
-    uint8_t* mem = nullptr;
-    if (hipMalloc((void**)&mem, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->set_err("label set: no device memory for " + std::to_string(bytes) + " bytes of tables and counters");
-        return SX_E_NOMEM;
-    }
-    hipError_t e = hipMemcpy(mem, T.map, sizeof T.map, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mem + sizeof T.map, T.next.data(), next_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && here_bytes) e = hipMemcpy(mem + at_here, T.here.data(), here_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mem + at_end, T.end.data(), end_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(mem); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
-    sx_label_set* set = new (std::nothrow) sx_label_set;
-    if (!set) { (void)hipFree(mem); return SX_E_NOMEM; }
-    set->device = ctx->device; set->mem = mem;
-    set->dev = LabelDevice{ mem, (const uint16_t*)(mem + sizeof T.map), (const uint64_t*)(mem + at_here), (const uint64_t*)(mem + at_end),
-                            (uint64_t*)(mem + at_findings), (uint64_t*)(mem + at_findings + counters), T.root_here, T.all,
-                            T.states, T.classes, T.lds_states, T.here_first, T.dead, T.n_patterns };
-    set->info = sx_label_set_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)(sizeof T.map + next_bytes + here_bytes + end_bytes), T.lds_states, (uint32_t)T.here.size() };
-    if (sx_label_set_reset(set) != SX_OK) { ctx->set_err("label set: the counters could not be reset"); sx_label_set_free(set); return SX_E_HIP; }
-    *out = set;
-    return SX_OK;
-}
-
-int sx_label_set_info_get(const sx_label_set* set, sx_label_set_info* out) {
-    if (!set || !out) return SX_E_INVALID;
-    *out = set->info;
-    return SX_OK;
-}
-
-void sx_label_set_free(sx_label_set* set) {
-    if (!set) return;
-    (void)hipFree(set->mem);
-    delete set;
-}
-
-int sx_label_set_read(const sx_label_set* set, uint64_t* findings, uint64_t* first, uint32_t n_patterns) {
-    if (!set || n_patterns != set->info.n_patterns) return SX_E_INVALID;
-    if (hipSetDevice(set->device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
-    for (int k = 0; k < 2; k++) {
-        uint64_t* out = k ? first : findings;
-        if (!out) continue;
-        if (hipMemcpy(out, k ? set->dev.first : set->dev.findings, (size_t)n_patterns * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
-    }
-    return SX_OK;
-}
-
-int sx_label_set_counters_device(const sx_label_set* set, const uint64_t** d_findings, const uint64_t** d_first) {
-    if (!set) return SX_E_INVALID;
-    if (d_findings) *d_findings = set->dev.findings;
-    if (d_first) *d_first = set->dev.first;
-    return SX_OK;
-}
-
-// The labels where the findings lie (sx_label_dev.hip): the source is checked as a whole, the labels' memory is had, then one kernel per
-// segment, each with the ordinal of its first record, on the selections' stream, and one wait.  Only the labels and the set's counters
-// are written.
-int sx_result_label_device(sx_ctx* ctx, const sx_result* r, sx_label_set* set, uint64_t ordinal_base, sx_labels** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !r || !set || !out) return SX_E_INVALID;
-    if (ctx->host_only) { ctx->set_err("host-only context: no device labels"); return SX_E_STATE; }
-    if (set->device != ctx->device) { ctx->set_err("the label set lies on another device"); return SX_E_INVALID; }
-    { const int rc = result_on_device(ctx, r, "label on the host"); if (rc != SX_OK) return rc; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->post_stream;
-    sx_labels* lab = new (std::nothrow) sx_labels;
-    if (!lab) return SX_E_NOMEM;
-    lab->device = ctx->device;
-    uint64_t bytes = 0;
-    for (const MissionFindings& s : r->r.segs) bytes += ((uint64_t)s.ext_nf * sizeof(uint64_t) + 255) / 256 * 256;
-    if (hipMalloc((void**)&lab->mem, bytes ? bytes : 256) != hipSuccess) {
-        (void)hipGetLastError();
-        delete lab;
-        ctx->set_err("device labels: no memory for " + std::to_string(bytes) + " bytes of labels");
-        return SX_E_NOMEM;
-    }
-    uint64_t walked = 0, at = 0;
-    hipError_t e = hipSuccess;
-    for (const MissionFindings& s : r->r.segs) {
-        sx_labels::Seg seg;
-        seg.d = (const uint64_t*)(lab->mem + at); seg.recs = s.dev_copy; seg.n = s.ext_nf; seg.epoch_ref = s.dev_epoch_ref; seg.epoch = s.dev_epoch;
-        lab->segs.push_back(seg);
-        LabelParams p;
-        memset(&p, 0, sizeof p);
-        p.recs = s.dev_copy; p.arena = (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(); p.n = s.ext_nf; p.packed = s.packed ? 1u : 0u;
-        p.ordinal = ordinal_base + walked;
-        p.labels = (uint64_t*)(lab->mem + at);
-        p.set = set->dev;
-        e = label_launch(p, st);
-        if (e != hipSuccess) break;
-        walked += s.ext_nf;
-        at += ((uint64_t)s.ext_nf * sizeof(uint64_t) + 255) / 256 * 256;
-    }
-    const hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) {
-        sx_labels_free(lab);
-        ctx->set_err(std::string("device labels: ") + hipGetErrorString(e));
-        return SX_E_HIP;
-    }
-    *out = lab;
-    return SX_OK;
-}
-
-uint64_t sx_labels_segments(const sx_labels* labels) { return labels ? labels->segs.size() : 0; }
-
-int sx_labels_segment_device(const sx_labels* labels, uint64_t segment, const uint64_t** d_labels, uint64_t* n_findings) {
-    if (d_labels) *d_labels = nullptr;
-    if (n_findings) *n_findings = 0;
-    if (!labels || segment >= labels->segs.size()) return SX_E_INVALID;
-    if (d_labels) *d_labels = labels->segs[segment].d;
-    if (n_findings) *n_findings = labels->segs[segment].n;
-    return SX_OK;
-}
-
-void sx_labels_free(sx_labels* labels) {
-    if (!labels) return;
-    (void)hipFree(labels->mem);
-    delete labels;
-}
-
-int sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels, uint64_t any, uint64_t all, uint64_t none, sx_result** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !r || !labels || !out) return SX_E_INVALID;
-    if (ctx->host_only) { ctx->set_err("host-only context: no device selection"); return SX_E_STATE; }
-    if (labels->device != ctx->device) { ctx->set_err("the labels lie on another device"); return SX_E_INVALID; }
-    const uint64_t masks[3] = { any, all, none };
-    return select_on_device(ctx, r, nullptr, 0, nullptr, nullptr, nullptr, 0, out, labels, masks);
 }
 
 int sx_get_stats(const sx_ctx* ctx, sx_stats* out) {

@@ -321,6 +321,7 @@ int ensure_cache(sx_ctx* ctx, uint64_t bytes);
 unsigned usable_cpus();
 unsigned replay_threads(const sx_ctx* ctx);
 void begin_call(sx_ctx* ctx);
+void fill_segment_info(const MissionFindings& s, sx_segment_info* info);   // what the accessors of a segment say of it, host or device
 
 // ---- stage A (sx_stage_a.cpp)
 ScanParams scan_params(const sx_ctx* ctx, int mission, const ScanSlot& s, const uint8_t* d_bytes, uint64_t len,

@@ -262,6 +262,7 @@ hipError_t launch_merge_cuts(const sx_finding* f, uint64_t n, uint64_t nb, const
 size_t merge_findings_scratch_bytes(uint64_t n_findings, int n_missions, int ordered = 0);
 // the strings of n placed records (recs; sx_finding16 if packed), each still at src[i], to their places in record order in `arena`,
 // str_off rewritten; scratch: order_strings_scratch_bytes(n), 256-aligned
+inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }   // (scratch tables and output blocks are 256-byte aligned)
 size_t order_strings_scratch_bytes(uint64_t n);
 hipError_t order_part_strings(void* recs, uint64_t n, int packed, const uint64_t* src, uint8_t* arena, void* scratch, size_t scratch_bytes,
                               hipStream_t stream);
@@ -276,19 +277,27 @@ hipError_t print_write(const PrintParams& P, hipStream_t stream);
 // pass 1 — fills P's per-wavefront tables inside `scratch` (select_scratch_bytes(n), 256-aligned); *count, *bytes = the device words with
 // the selected records' number and string bytes, valid once `stream` has got there; select_place: the selected records to out_recs, their
 // strings back to back to out_arena (scratch: select_place_scratch_bytes(n_sel), 256-aligned; order_part_strings inside)
-// (set: NULL, or a compiled keyword set — sx_selset_core.hpp —, whose selset_match_kernel then is pass 1: sx_selset_dev.hip; re: NULL, or
-// a compiled regex set — sx_selre_core.hpp —, whose selre_match_kernel then is pass 1: sx_selre_dev.hip; pick: NULL, or the segment's
-// labels and three masks — sx_label_core.hpp —, whose label_pick_kernel then is pass 1: sx_label_dev.hip; at most one of the three)
+// What pass 1 looks for, one kind: SelectBy::kPatterns = P.pat's patterns (select_match_kernel); kSet = a compiled keyword set —
+// sx_selset_core.hpp —, whose selset_match_kernel then is pass 1: sx_selset_dev.hip; kRegex = a compiled regex set — sx_selre_core.hpp —,
+// selre_match_kernel: sx_selre_dev.hip; kLabels = the segment's labels and three masks — sx_label_core.hpp —, label_pick_kernel:
+// sx_label_dev.hip.  Of P.pat the three read `invert` at most.
 struct SelectParams;
 struct SelsetDevice;
 struct SelreDevice;
 struct LabelPick;
+struct SelectBy {
+    enum Kind { kPatterns, kSet, kRegex, kLabels } kind = kPatterns;
+    union {
+        const SelsetDevice* set = nullptr;
+        const SelreDevice* re;
+        const LabelPick* pick;
+    };
+};
 size_t select_scratch_bytes(uint64_t n);
 hipError_t selset_launch_match(const SelectParams& P, const SelsetDevice& set, uint64_t waves, hipStream_t stream);
 hipError_t selre_launch_match(const SelectParams& P, const SelreDevice& re, uint64_t waves, hipStream_t stream);
 hipError_t label_launch_pick(const SelectParams& P, const LabelPick& pick, uint64_t waves, hipStream_t stream);
-hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreDevice* re, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes,
-                          const LabelPick* pick = nullptr);
+hipError_t select_measure(SelectParams* P, const SelectBy& by, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes);
 size_t select_place_scratch_bytes(uint64_t n_sel);
 hipError_t select_place(const SelectParams& P, void* out_recs, uint64_t n_sel, uint8_t* out_arena, void* scratch, size_t scratch_bytes, hipStream_t stream);
 // The regex extraction on the device (sx_extract_dev.hip, ExtractParams: sx_extract_core.hpp), a segment at a time, in the shape of the

@@ -10,6 +10,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "sx_device.hpp"
+#include "sx_rows_dev.hpp"
 
 #define SXD __device__ __forceinline__
 #include "sx_extract_build.hpp"
@@ -17,27 +18,14 @@
 
 namespace sx {
 
-constexpr uint32_t kExtractWaves = 8;          // wavefronts per workgroup, which share the rows in LDS
-constexpr uint32_t kExtractGroupsPerCu = 3;    // 3 x (48 KiB of rows + the map) <= 160 KiB; 24 wavefronts per CU
-
-struct alignas(16) Extract16 { uint32_t w[4]; };
-
-// the class map and the first lds_states rows into LDS (the table's allocation is a multiple of 16 bytes)
-__device__ __forceinline__ void extract_load_rows(const ExtractDevice& ex, uint8_t* map, Extract16* rows16) {
-    if (threadIdx.x < 256 / 4) ((uint32_t*)map)[threadIdx.x] = ((const uint32_t*)ex.map)[threadIdx.x];
-    const uint32_t chunks = (ex.lds_states * ex.classes * 2u + 15u) / 16u;
-    for (uint32_t c = threadIdx.x; c < chunks; c += 64 * kExtractWaves) rows16[c] = ((const Extract16*)ex.next)[c];
-    __syncthreads();
-}
-
 // wavefronts [0, waves]: the last one (behind the last record) has no match, so that the scans' last words are the segment's totals
-__global__ __launch_bounds__(64 * kExtractWaves) void extract_count_kernel(ExtractParams P, uint64_t waves) {
+__global__ __launch_bounds__(64 * kRowsWaves) void extract_count_kernel(ExtractParams P, uint64_t waves) {
     __shared__ uint8_t map[256];
-    __shared__ Extract16 rows16[kSelsetLdsBytes / 16];
-    extract_load_rows(P.ex, map, rows16);
+    __shared__ Rows16 rows16[kSelsetLdsBytes / 16];
+    rows_load(P.ex.map, P.ex.next, P.ex.lds_states, P.ex.classes, 2u, map, rows16);
     const uint16_t* rows = (const uint16_t*)rows16;
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    for (uint64_t w = (uint64_t)blockIdx.x * kExtractWaves + wv; w <= waves; w += (uint64_t)gridDim.x * kExtractWaves) {
+    for (uint64_t w = (uint64_t)blockIdx.x * kRowsWaves + wv; w <= waves; w += (uint64_t)gridDim.x * kRowsWaves) {
         ExtractLane L = extract_begin_lane(P, w, lane);
         uint32_t count = 0;
         uint64_t bytes = 0;
@@ -56,13 +44,13 @@ __global__ __launch_bounds__(64 * kExtractWaves) void extract_count_kernel(Extra
     }
 }
 
-__global__ __launch_bounds__(64 * kExtractWaves) void extract_place_kernel(ExtractParams P, uint64_t waves) {
+__global__ __launch_bounds__(64 * kRowsWaves) void extract_place_kernel(ExtractParams P, uint64_t waves) {
     __shared__ uint8_t map[256];
-    __shared__ Extract16 rows16[kSelsetLdsBytes / 16];
-    extract_load_rows(P.ex, map, rows16);
+    __shared__ Rows16 rows16[kSelsetLdsBytes / 16];
+    rows_load(P.ex.map, P.ex.next, P.ex.lds_states, P.ex.classes, 2u, map, rows16);
     const uint16_t* rows = (const uint16_t*)rows16;
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    for (uint64_t w = (uint64_t)blockIdx.x * kExtractWaves + wv; w < waves; w += (uint64_t)gridDim.x * kExtractWaves) {
+    for (uint64_t w = (uint64_t)blockIdx.x * kRowsWaves + wv; w < waves; w += (uint64_t)gridDim.x * kRowsWaves) {
         const uint64_t i = w * kSelectRecs + lane;
         // the lane's base: the wavefront's, plus the matches of the wavefront's earlier records
         const uint32_t own = i < P.n ? P.rcount[i] : 0u;
@@ -88,7 +76,6 @@ __global__ __launch_bounds__(64 * kExtractWaves) void extract_place_kernel(Extra
     }
 }
 
-static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 static size_t extract_scan_bytes(uint64_t items) {
     size_t a = 0;
     (void)rocprim::exclusive_scan(nullptr, a, (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)items, rocprim::plus<uint64_t>(), (hipStream_t)0);
@@ -101,21 +88,11 @@ size_t extract_scratch_bytes(uint64_t n) {
 }
 
 static hipError_t extract_check(const ExtractDevice& ex) {
-    if (ex.classes < 1 || ex.classes > 256 || ex.states < 1 || ex.states > SX_SELECT_REGEX_MAX_STATES) return hipErrorInvalidValue;
-    if ((uint64_t)ex.lds_states * ex.classes * 2u > kSelsetLdsBytes || ex.lds_states > ex.states) return hipErrorInvalidValue;
+    const hipError_t e = rows_check(ex.classes, ex.states, ex.lds_states, 2u, kSelsetLdsBytes);
+    if (e != hipSuccess) return e;
+    if (ex.states < 1 || ex.states > SX_SELECT_REGEX_MAX_STATES) return hipErrorInvalidValue;
     if (ex.end_first > ex.here_first || ex.here_first > ex.dead_first || ex.dead_first > ex.states) return hipErrorInvalidValue;
     if (ex.start0 >= ex.states || ex.start1 >= ex.states) return hipErrorInvalidValue;
-    return hipSuccess;
-}
-
-static hipError_t extract_grid(uint64_t wavefronts, dim3* grid) {
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
-    const uint64_t groups = (wavefronts + kExtractWaves - 1) / kExtractWaves, most = (uint64_t)(cus > 0 ? cus : 1) * kExtractGroupsPerCu;
-    *grid = dim3((unsigned)(groups < most ? groups : most));
     return hipSuccess;
 }
 
@@ -136,9 +113,9 @@ hipError_t extract_measure(ExtractParams* P, void* scratch, size_t scratch_bytes
     uint64_t* bsum = (uint64_t*)at; at += w8;
     size_t tmp_bytes = scratch_bytes - (size_t)(at - (uint8_t*)scratch);
     dim3 grid;
-    e = extract_grid(waves + 1, &grid);
+    e = rows_grid(waves + 1, kRowsWaves, kRowsGroupsPerCu, &grid);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(extract_count_kernel, grid, dim3(64 * kExtractWaves), 0, stream, *P, waves);
+    hipLaunchKernelGGL(extract_count_kernel, grid, dim3(64 * kRowsWaves), 0, stream, *P, waves);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = rocprim::exclusive_scan(at, tmp_bytes, (const uint64_t*)P->wcount, wbase, (uint64_t)0, (size_t)(waves + 1), rocprim::plus<uint64_t>(), stream);
@@ -163,9 +140,9 @@ hipError_t extract_place(const ExtractParams& P0, void* out_recs, uint64_t n_out
     P.out_src = (uint64_t*)scratch;
     const uint64_t waves = (P.n + kSelectRecs - 1) / kSelectRecs;
     dim3 grid;
-    hipError_t e = extract_grid(waves, &grid);
+    hipError_t e = rows_grid(waves, kRowsWaves, kRowsGroupsPerCu, &grid);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(extract_place_kernel, grid, dim3(64 * kExtractWaves), 0, stream, P, waves);
+    hipLaunchKernelGGL(extract_place_kernel, grid, dim3(64 * kRowsWaves), 0, stream, P, waves);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const size_t src_bytes = up256((size_t)n_out * 8);

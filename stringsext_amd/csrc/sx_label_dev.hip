@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sx_device.hpp"
+#include "sx_rows_dev.hpp"
 
 #define SXD __device__ __forceinline__
 #include "sx_label_build.hpp"
@@ -17,27 +18,19 @@
 
 namespace sx {
 
-constexpr uint32_t kLabelWaves = 8;          // wavefronts per workgroup, which share the rows and the counters in LDS
-constexpr uint32_t kLabelGroupsPerCu = 3;    // 3 x 50 176 bytes <= 160 KiB; 24 wavefronts per CU
 constexpr uint32_t kLabelPickWaves = 4;      // wavefronts per workgroup of the pick: they share nothing
 
-struct alignas(16) Label16 { uint32_t w[4]; };
-
 // wavefronts [0, waves): waves = ceil(n / 64)
-__global__ __launch_bounds__(64 * kLabelWaves) void label_match_kernel(LabelParams P, uint64_t waves) {
+__global__ __launch_bounds__(64 * kRowsWaves) void label_match_kernel(LabelParams P, uint64_t waves) {
     __shared__ uint8_t map[256];
-    __shared__ Label16 rows16[kSelsetLdsBytes / 16];
+    __shared__ Rows16 rows16[kSelsetLdsBytes / 16];
     __shared__ uint32_t counts[kLabelBits];
     __shared__ uint64_t mins[kLabelBits];
-    if (threadIdx.x < 256 / 4) ((uint32_t*)map)[threadIdx.x] = ((const uint32_t*)P.set.map)[threadIdx.x];
-    // (the table's allocation is a multiple of 16 bytes)
-    const uint32_t chunks = (P.set.lds_states * P.set.classes * 2u + 15u) / 16u;
-    for (uint32_t c = threadIdx.x; c < chunks; c += 64 * kLabelWaves) rows16[c] = ((const Label16*)P.set.next)[c];
     if (threadIdx.x < kLabelBits) { counts[threadIdx.x] = 0; mins[threadIdx.x] = ~(uint64_t)0; }
-    __syncthreads();
+    rows_load(P.set.map, P.set.next, P.set.lds_states, P.set.classes, 2u, map, rows16);
     const uint16_t* rows = (const uint16_t*)rows16;
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    for (uint64_t w = (uint64_t)blockIdx.x * kLabelWaves + wv; w < waves; w += (uint64_t)gridDim.x * kLabelWaves) {
+    for (uint64_t w = (uint64_t)blockIdx.x * kRowsWaves + wv; w < waves; w += (uint64_t)gridDim.x * kRowsWaves) {
         LabelLane L = label_begin_lane(P, w, lane);
         while (__ballot(L.active ? 1 : 0) != 0)
             if (L.active) label_step_lane(P, map, rows, L);
@@ -65,30 +58,23 @@ __global__ __launch_bounds__(64 * kLabelPickWaves) void label_pick_kernel(Select
     if (w > waves) return;      // (a whole wavefront)
     uint32_t len;
     const bool sel = label_pick_lane(S, K, w, lane, &len);
-    const uint64_t mask = __ballot(sel ? 1 : 0);
-    uint64_t bytes = len;
-#pragma unroll
-    for (int d = 32; d; d >>= 1) bytes += __shfl_xor(bytes, d, 64);
-    if (lane == 0) { S.wmask[w] = mask; S.wcount[w] = (uint32_t)__popcll(mask); S.wbytes[w] = bytes; }
+    wave_store_selected(S.wmask, S.wcount, S.wbytes, w, sel, len);
 }
 
 // The labels of one segment: P = the segment, its first record's ordinal, the place of its labels and the set.
 hipError_t label_launch(const LabelParams& P, hipStream_t stream) {
     const LabelDevice& set = P.set;
-    if (set.classes < 1 || set.classes > 256 || set.states < 1 || set.states > SX_SELECT_REGEX_MAX_STATES) return hipErrorInvalidValue;
-    if ((uint64_t)set.lds_states * set.classes * 2u > kSelsetLdsBytes || set.lds_states > set.states) return hipErrorInvalidValue;
+    hipError_t e = rows_check(set.classes, set.states, set.lds_states, 2u, kSelsetLdsBytes);
+    if (e != hipSuccess) return e;
+    if (set.states < 1 || set.states > SX_SELECT_REGEX_MAX_STATES) return hipErrorInvalidValue;
     if (set.here_first < 1 || set.here_first > set.states || set.n_patterns < 1 || set.n_patterns > kLabelBits) return hipErrorInvalidValue;
     if (P.n == 0) return hipSuccess;
     if (!P.labels) return hipErrorInvalidValue;
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
     const uint64_t waves = (P.n + kSelectRecs - 1) / kSelectRecs;
-    const uint64_t groups = (waves + kLabelWaves - 1) / kLabelWaves, most = (uint64_t)(cus > 0 ? cus : 1) * kLabelGroupsPerCu;
-    const dim3 grid((unsigned)(groups < most ? groups : most)), block(64 * kLabelWaves);
-    hipLaunchKernelGGL(label_match_kernel, grid, block, 0, stream, P, waves);
+    dim3 grid;
+    e = rows_grid(waves, kRowsWaves, kRowsGroupsPerCu, &grid);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(label_match_kernel, grid, dim3(64 * kRowsWaves), 0, stream, P, waves);
     return hipGetLastError();
 }
 

@@ -40,7 +40,6 @@ __global__ __launch_bounds__(64 * kPrintWaves) void print_write_kernel(PrintPara
     if (w * kPrintRecs < P.n) print_copy_lane(P, w, lane, offs[wv], srcs[wv], plens[wv], pre[wv]);
 }
 
-static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 static size_t print_scan_bytes(uint64_t items) {
     size_t t = 0;
     (void)rocprim::exclusive_scan(nullptr, t, (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)items, rocprim::plus<uint64_t>(), (hipStream_t)0);

@@ -1,0 +1,736 @@
+// sx_result_api.cpp — the C-ABI of include/stringsext_amd.h for a result that stays in HBM (SX_OPT_RESULT_ON_DEVICE): the print, the
+// selections, the extraction, the tally and the labels, and the compiled sets they take.  What the operations share is here once — the
+// view of a segment, a set's upload, a handle's device and memory, the counters' reset, the two passes of whatever writes a new
+// result —; what tells them apart is in their lane functions (sx_*_core.hpp) and kernels (sx_*_dev.hip).
+#include "sx_ctx.hpp"
+#include "sx_print_core.hpp"
+#include "sx_select_core.hpp"
+#include "sx_selset_build.hpp"
+#include "sx_selset_core.hpp"
+#include "sx_selre_build.hpp"
+#include "sx_selre_core.hpp"
+#include "sx_extract_build.hpp"
+#include "sx_extract_core.hpp"
+#include "sx_seltally_build.hpp"
+#include "sx_seltally_core.hpp"
+#include "sx_label_build.hpp"
+#include "sx_label_core.hpp"
+
+using namespace sx;
+
+// What every handle of this file has: device memory of its own, `mem`, on `device`
+struct sx_device_handle {
+    int device = 0;
+    uint8_t* mem = nullptr;
+};
+
+// sx_select_set_create: a compiled keyword list; `mem` = [the class map][the table]
+struct sx_select_set : sx_device_handle {
+    SelsetDevice dev{};
+    sx_select_set_info info{};
+};
+
+// sx_select_regex_create: compiled regular expressions; `mem` as a set's
+struct sx_select_regex : sx_device_handle {
+    SelreDevice dev{};
+    sx_select_regex_info info{};
+};
+
+// sx_extract_regex_create: regular expressions compiled for the extraction; `mem` as a set's
+struct sx_extract_regex : sx_device_handle {
+    ExtractDevice dev{};
+    sx_extract_regex_info info{};
+};
+
+// sx_tally_set_create: a keyword list compiled for the tally; `mem` = [the class map][the table][own][dict][pattern -> unique id]
+// [hits][first]
+struct sx_tally_set : sx_device_handle {
+    SeltallyDevice dev{};
+    const uint32_t* d_unique_of_pattern = nullptr;
+    std::vector<uint32_t> unique_of_pattern;
+    sx_tally_set_info info{};
+};
+
+// sx_label_set_create: regular expressions compiled for the labels; `mem` = [the class map][the table][here][end][findings][first]
+struct sx_label_set : sx_device_handle {
+    LabelDevice dev{};
+    sx_label_set_info info{};
+};
+
+// sx_result_label_device: one result's labels; `mem` = an array per source segment, each 256-byte aligned.
+// Per segment what tells the source apart: where its records lie, how many they are, and the epoch of its block when it was labelled.
+struct sx_labels : sx_device_handle {
+    struct Seg {
+        const uint64_t* d = nullptr;
+        const void* recs = nullptr;
+        uint64_t n = 0;
+        std::shared_ptr<std::atomic<uint64_t>> epoch_ref;
+        uint64_t epoch = 0;
+    };
+    std::vector<Seg> segs;
+};
+
+namespace {
+
+// A segment where it lies in HBM: what every kernel's parameters begin with
+struct SegRef {
+    const void* recs;
+    const uint8_t* arena;
+    uint64_t n;
+    uint32_t packed;
+};
+SegRef seg_ref(const MissionFindings& s) {
+    return SegRef{ s.dev_copy, (const uint8_t*)s.dev_copy + s.ext_nf * s.rec_size(), s.ext_nf, s.packed ? 1u : 0u };
+}
+// (P: PrintParams, SelectParams, ExtractParams, SeltallyParams, LabelParams)
+template <class P>
+P params_of(const SegRef& v) {
+    P p;
+    memset(&p, 0, sizeof p);
+    p.recs = v.recs; p.arena = v.arena; p.n = v.n; p.packed = v.packed;
+    return p;
+}
+
+bool host_only(sx_ctx* ctx, const char* no_device_what) {
+    if (ctx->host_only) ctx->set_err(std::string("host-only context: no device ") + no_device_what);
+    return ctx->host_only;
+}
+// (what_lies: "the pattern set lies", "the labels lie")
+bool on_another_device(sx_ctx* ctx, const sx_device_handle& h, const char* what_lies) {
+    if (h.device != ctx->device) ctx->set_err(std::string(what_lies) + " on another device");
+    return h.device != ctx->device;
+}
+template <class H>
+void handle_free(H* h) {
+    if (!h) return;
+    (void)hipFree(h->mem);
+    delete h;
+}
+template <class H, class Info>
+int handle_info(const H* h, Info* out) {
+    if (!h || !out) return SX_E_INVALID;
+    *out = h->info;
+    return SX_OK;
+}
+
+// One piece of a set's device memory: `bytes` from `src`, in a place of `bytes` rounded up to a multiple of `round`
+struct SetPiece {
+    const void* src;
+    size_t bytes, round;
+};
+// A compiled set's memory on the context's device: the pieces one behind the other, then `counter_bytes` of counters (not written).
+// at[i]: the offset of piece i, at[n_pieces]: the counters'.  kind: the set's name in the messages.
+int upload_set(sx_ctx* ctx, const char* kind, const std::vector<SetPiece>& pieces, size_t counter_bytes, uint8_t** mem, size_t* at) {
+    if (host_only(ctx, (std::string("for the ") + kind).c_str())) return SX_E_STATE;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    size_t bytes = 0;
+    for (size_t i = 0; i < pieces.size(); i++) { at[i] = bytes; bytes += (pieces[i].bytes + pieces[i].round - 1) / pieces[i].round * pieces[i].round; }
+    at[pieces.size()] = bytes;
+    bytes += counter_bytes;
+    if (hipMalloc((void**)mem, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *mem = nullptr;
+        ctx->set_err(std::string(kind) + ": no device memory for " + std::to_string(bytes) + " bytes of " + (counter_bytes ? "tables and counters" : "table"));
+        return SX_E_NOMEM;
+    }
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; e == hipSuccess && i < pieces.size(); i++)
+        if (pieces[i].bytes) e = hipMemcpy(*mem + at[i], pieces[i].src, pieces[i].bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(*mem); *mem = nullptr; ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
+    return SX_OK;
+}
+// (the handle of an uploaded set; NULL: no host memory, and `mem` is freed)
+template <class H>
+H* new_handle(const sx_ctx* ctx, uint8_t* mem) {
+    H* h = new (std::nothrow) H;
+    if (!h) { (void)hipFree(mem); return nullptr; }
+    h->device = ctx->device; h->mem = mem;
+    return h;
+}
+
+// A set's two counter arrays of n words as they are before the first call: `zeros` 0, `never` all ones (SX_TALLY_NEVER, SX_LABEL_NEVER)
+int reset_counters(int device, uint64_t* zeros, uint64_t* never, size_t n) {
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    hipError_t e = hipMemset(zeros, 0, n * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMemset(never, 0xFF, n * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (a device memset may return before it is done, and the kernels run on a stream that does not wait for this one)
+    if (e != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    return SX_OK;
+}
+// n words of a set's counters to the host (out: NULL = not asked for)
+int read_counters(int device, const uint64_t* d, uint64_t* out, size_t n) {
+    if (!out) return SX_OK;
+    if (hipSetDevice(device) != hipSuccess || hipMemcpy(out, d, n * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    return SX_OK;
+}
+
+// What the device operations ask of a result: every segment in HBM, in memory of this context — the result block of the last scan call
+// or one of the two selection blocks — that has not been written again since.
+int result_on_device(sx_ctx* ctx, const sx_result* r, const char* host_call) {
+    const std::string in_host = std::string("the result is in host memory: ") + host_call;
+    if (r->r.segs.empty()) { ctx->set_err(in_host); return SX_E_STATE; }
+    for (const MissionFindings& s : r->r.segs) {
+        if (!s.dev_only || !s.keep_on_device || s.ext_nf == 0) { ctx->set_err(in_host); return SX_E_STATE; }
+        const bool ours = s.dev_epoch_ref && (s.dev_epoch_ref == ctx->dev_epoch || s.dev_epoch_ref == ctx->select_epoch[0] || s.dev_epoch_ref == ctx->select_epoch[1]);
+        if (!ours || s.dev_epoch_ref->load() != s.dev_epoch) {
+            ctx->set_err("a later scan or selection has reused the result's device memory");
+            return SX_E_STATE;
+        }
+    }
+    return SX_OK;
+}
+
+// (a grow-only device buffer of the selection: SX_E_NOMEM leaves it empty)
+int grow_device(sx_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t bytes, const char* what) {
+    if (bytes <= *cap) return SX_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    if (hipMalloc((void**)p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        ctx->set_err(std::string("device select: no memory for ") + std::to_string(bytes) + " bytes of " + what);
+        return SX_E_NOMEM;
+    }
+    *cap = bytes;
+    return SX_OK;
+}
+
+// The two passes of an operation that writes a new result, a segment at a time, as select_on_device drives them.  measure: pass 1
+// of segment i inside `scratch` (scratch_bytes(seg.n), 256-aligned); *count and *bytes = the device words that will hold the output's
+// records — a word of count_bytes() bytes — and string bytes.  place: pass 2 of segment i, its c records to `recs`, their strings to
+// `arena` (scratch: place_scratch_bytes(c)).
+struct TwoPass {
+    virtual ~TwoPass() = default;
+    virtual size_t count_bytes() const = 0;
+    virtual size_t scratch_bytes(uint64_t n) const = 0;
+    virtual hipError_t measure(size_t i, const SegRef& seg, void* scratch, size_t bytes, hipStream_t st, const void** count, const uint64_t** nbytes) = 0;
+    virtual size_t place_scratch_bytes(uint64_t c) const = 0;
+    virtual hipError_t place(size_t i, void* recs, uint64_t c, uint8_t* arena, void* scratch, size_t bytes, hipStream_t st) = 0;
+};
+
+// grep (sx_select_dev.hip): pass 1 by `by.kind` — the patterns of `pat`, a compiled keyword set, a compiled regex set (of `pat` they
+// read `invert`), or `labels` with masks = { any, all, none }, which reads no string byte —, pass 2 the same for all four
+struct Selection final : TwoPass {
+    SelectBy by;
+    SelectPatterns pat{};
+    const sx_labels* labels = nullptr;
+    uint64_t masks[3] = { 0, 0, 0 };
+    std::vector<SelectParams> P;
+    explicit Selection(size_t ns) : P(ns) {}
+    size_t count_bytes() const override { return sizeof(uint32_t); }
+    size_t scratch_bytes(uint64_t n) const override { return select_scratch_bytes(n); }
+    hipError_t measure(size_t i, const SegRef& seg, void* scratch, size_t bytes, hipStream_t st, const void** count, const uint64_t** nbytes) override {
+        P[i] = params_of<SelectParams>(seg);
+        P[i].pat = pat;
+        SelectBy b = by;
+        LabelPick pick{ nullptr, masks[0], masks[1], masks[2] };
+        if (by.kind == SelectBy::kLabels) { pick.labels = labels->segs[i].d; b.pick = &pick; }
+        return select_measure(&P[i], b, scratch, bytes, st, (const uint32_t**)count, nbytes);
+    }
+    size_t place_scratch_bytes(uint64_t c) const override { return select_place_scratch_bytes(c); }
+    hipError_t place(size_t i, void* recs, uint64_t c, uint8_t* arena, void* scratch, size_t bytes, hipStream_t st) override {
+        return select_place(P[i], recs, c, arena, scratch, bytes, st);
+    }
+};
+
+// grep -o (sx_extract_dev.hip): an output record is a match, not a finding, and a segment may get more records than it had
+struct Extraction final : TwoPass {
+    const ExtractDevice& ex;
+    std::vector<ExtractParams> X;
+    Extraction(const ExtractDevice& e, size_t ns) : ex(e), X(ns) {}
+    size_t count_bytes() const override { return sizeof(uint64_t); }
+    size_t scratch_bytes(uint64_t n) const override { return extract_scratch_bytes(n); }
+    hipError_t measure(size_t i, const SegRef& seg, void* scratch, size_t bytes, hipStream_t st, const void** count, const uint64_t** nbytes) override {
+        X[i] = params_of<ExtractParams>(seg);
+        X[i].ex = ex;
+        return extract_measure(&X[i], scratch, bytes, st, (const uint64_t**)count, nbytes);
+    }
+    size_t place_scratch_bytes(uint64_t c) const override { return extract_place_scratch_bytes(c); }
+    hipError_t place(size_t i, void* recs, uint64_t c, uint8_t* arena, void* scratch, size_t bytes, hipStream_t st) override {
+        return extract_place(X[i], recs, c, arena, scratch, bytes, st);
+    }
+};
+
+// A new result out of one in HBM, for the five entry points, whose arguments are checked: pass 1 of every segment, one wait for the
+// segments' totals, the selection block, pass 2 of every segment that has output records, one more wait.  The source is read, never
+// moved.  The blocks take turns: the one this call writes held the selection before the last one.
+int select_on_device(sx_ctx* ctx, const sx_result* r, TwoPass& pass, sx_result** out) {
+    // the block this call writes: a source that lies there was made two selections ago
+    const int slot = (int)(ctx->select_calls & 1u);
+    for (const MissionFindings& s : r->r.segs)
+        if (s.dev_epoch_ref == ctx->select_epoch[slot]) { ctx->set_err("this selection reuses the source's device memory: it was selected two calls ago"); return SX_E_STATE; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    const size_t ns = r->r.segs.size();
+    uint64_t scratch = 0;
+    for (const MissionFindings& s : r->r.segs) scratch += pass.scratch_bytes(s.ext_nf);
+    { const int rc = grow_device(ctx, &ctx->d_select_scratch, &ctx->d_select_scratch_cap, scratch, "wavefront tables"); if (rc != SX_OK) return rc; }
+    std::vector<const void*> d_count(ns);
+    std::vector<const uint64_t*> d_bytes(ns);
+    uint64_t at = 0;
+    for (size_t i = 0; i < ns; i++) {
+        const size_t bytes = pass.scratch_bytes(r->r.segs[i].ext_nf);
+        HIP_TRY(ctx, pass.measure(i, seg_ref(r->r.segs[i]), ctx->d_select_scratch + at, bytes, st, &d_count[i], &d_bytes[i]));
+        at += bytes;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::vector<uint64_t> n_sel(ns), b_sel(ns), base(ns);
+    uint64_t block = 0, scratch2 = 0;
+    for (size_t i = 0; i < ns; i++) {
+        uint64_t c = 0;      // (little-endian: a 32-bit word fills its low half)
+        HIP_TRY(ctx, hipMemcpy(&c, d_count[i], pass.count_bytes(), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(&b_sel[i], d_bytes[i], sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (c >= 0xFFFFFFFFull) {      // (an extraction: a selection has no more records than its source)
+            ctx->set_err("segment " + std::to_string(i) + " has " + std::to_string(c) + " matches: more than the 32-bit counters of a segment hold");
+            return SX_E_INVALID;
+        }
+        n_sel[i] = c;
+        if (!c) continue;
+        base[i] = block;
+        block += up256(c * r->r.segs[i].rec_size() + b_sel[i]);
+        scratch2 = std::max<uint64_t>(scratch2, pass.place_scratch_bytes(c));
+    }
+    // from here on the call counts: the block of the selection before the last one is written again
+    ctx->select_epoch[slot]->fetch_add(1);
+    ctx->select_calls++;
+    ResultHolder res;
+    res.r->r.pool = ctx->pool;
+    if (block) {
+        { const int rc = grow_device(ctx, &ctx->d_select[slot], &ctx->d_select_cap[slot], block, "selected findings"); if (rc != SX_OK) return rc; }
+        { const int rc = grow_device(ctx, &ctx->d_select_scratch2, &ctx->d_select_scratch2_cap, scratch2, "string offsets"); if (rc != SX_OK) return rc; }
+        for (size_t i = 0; i < ns; i++) {
+            if (!n_sel[i]) continue;
+            const MissionFindings& s = r->r.segs[i];
+            uint8_t* recs = ctx->d_select[slot] + base[i];
+            HIP_TRY(ctx, pass.place(i, recs, n_sel[i], recs + n_sel[i] * s.rec_size(), ctx->d_select_scratch2, pass.place_scratch_bytes(n_sel[i]), st));
+            MissionFindings o;
+            o.ext_nf = n_sel[i]; o.ext_na = b_sel[i]; o.dev_copy = recs; o.dev_only = true; o.keep_on_device = true;
+            o.dev_epoch_ref = ctx->select_epoch[slot]; o.dev_epoch = ctx->select_epoch[slot]->load();
+            o.packed = s.packed; o.info = s.info;
+            res.r->r.segs.push_back(std::move(o));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    *out = res.release();
+    return SX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sx_result_segment_device(const sx_result* r, uint64_t i, const void** d_records, uint64_t* n_findings, const uint8_t** d_arena,
+                             uint64_t* arena_len, int* packed, sx_segment_info* info) {
+    if (!r || i >= r->r.segs.size()) return SX_E_INVALID;
+    const MissionFindings& s = r->r.segs[(size_t)i];
+    if (d_records) *d_records = nullptr;
+    if (d_arena) *d_arena = nullptr;
+    if (n_findings) *n_findings = s.count();
+    if (arena_len) *arena_len = s.strings_len();
+    if (packed) *packed = s.packed ? 1 : 0;
+    if (info) fill_segment_info(s, info);
+    if (!s.dev_only) return SX_OK;   // (in host memory: the host accessors)
+    if (!s.keep_on_device || !s.dev_epoch_ref || s.dev_epoch_ref->load() != s.dev_epoch) return SX_E_STATE;
+    const SegRef v = seg_ref(s);
+    if (d_records) *d_records = v.recs;
+    if (d_arena) *d_arena = v.arena;
+    return SX_OK;
+}
+
+// Finding::print where the findings lie (sx_print_dev.hip): pass 1 of every segment, one wait for the segments' text bytes, the text
+// block, pass 2 of every segment at its 64-bit base, one more wait.  The result is read, never moved.
+int sx_print_findings_device(sx_ctx* ctx, const sx_result* r, int n_inputs, int radix, int no_metadata, const uint8_t** d_text,
+                             uint64_t* text_len) {
+    if (d_text) *d_text = nullptr;
+    if (text_len) *text_len = 0;
+    if (!ctx || !r || !d_text || !text_len) return SX_E_INVALID;
+    if (radix != 0 && radix != 'x' && radix != 'd' && radix != 'o') { ctx->set_err("radix must be 0, 'x', 'd' or 'o'"); return SX_E_INVALID; }
+    if (host_only(ctx, "print")) return SX_E_STATE;
+    { const int rc = result_on_device(ctx, r, "sx_print_findings"); if (rc != SX_OK) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    if (!ctx->d_print_missions) {
+        std::vector<PrintMission> tab(256);
+        memset(tab.data(), 0, tab.size() * sizeof(PrintMission));
+        for (size_t k = ctx->missions.size(); k-- > 0;) {   // (print_findings takes the first Mission of an id)
+            const Mission& m = ctx->missions[k];
+            const char* name = m.c.print_encoding_as_ascii ? "ascii" : m.encoding_name();
+            const std::string label = name ? name : "";
+            PrintMission& t = tab[m.c.mission_id];
+            if (label.size() > sizeof t.label) { ctx->set_err("encoding label longer than 14 bytes"); return SX_E_STATE; }
+            t.present = 1; t.len = (uint8_t)label.size();
+            memcpy(t.label, label.data(), label.size());
+        }
+        uint8_t* p = nullptr;
+        if (hipMalloc((void**)&p, tab.size() * sizeof(PrintMission)) != hipSuccess) { (void)hipGetLastError(); ctx->set_err("device print: no memory for the Mission table"); return SX_E_NOMEM; }
+        const hipError_t e = hipMemcpy(p, tab.data(), tab.size() * sizeof(PrintMission), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(p); ctx->set_err(std::string("hipMemcpy: ") + hipGetErrorString(e)); return SX_E_HIP; }
+        ctx->d_print_missions = p;
+    }
+    const size_t ns = r->r.segs.size();
+    uint64_t scratch = 0;
+    for (const MissionFindings& s : r->r.segs) scratch += print_scratch_bytes(s.ext_nf);
+    if (scratch > ctx->d_print_scratch_cap) {
+        if (ctx->d_print_scratch) (void)hipFree(ctx->d_print_scratch);
+        ctx->d_print_scratch = nullptr; ctx->d_print_scratch_cap = 0;
+        if (hipMalloc((void**)&ctx->d_print_scratch, scratch) != hipSuccess) { (void)hipGetLastError(); ctx->d_print_scratch = nullptr; ctx->set_err("device print: no memory for the offsets"); return SX_E_NOMEM; }
+        ctx->d_print_scratch_cap = scratch;
+    }
+    std::vector<PrintParams> P(ns);
+    std::vector<const uint64_t*> d_total(ns);
+    uint64_t at = 0;
+    for (size_t i = 0; i < ns; i++) {
+        const MissionFindings& s = r->r.segs[i];
+        PrintParams& p = P[i];
+        p = params_of<PrintParams>(seg_ref(s));
+        p.file_id = s.packed && s.info ? s.info->file_id : -1;
+        p.several_inputs = n_inputs > 1; p.radix = (uint32_t)radix; p.no_metadata = no_metadata != 0; p.several_missions = ctx->missions.size() > 1;
+        p.missions = (const PrintMission*)ctx->d_print_missions;
+        const size_t bytes = print_scratch_bytes(s.ext_nf);
+        HIP_TRY(ctx, print_measure(p, ctx->d_print_scratch + at, bytes, st, &p.wbase, &d_total[i]));
+        at += bytes;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    uint64_t total = 0;
+    for (size_t i = 0; i < ns; i++) {
+        uint64_t t = 0;
+        HIP_TRY(ctx, hipMemcpy(&t, d_total[i], sizeof t, hipMemcpyDeviceToHost));
+        P[i].base = total;
+        total += t;
+    }
+    if (total > ctx->d_text_cap) {
+        if (ctx->d_text) (void)hipFree(ctx->d_text);
+        ctx->d_text = nullptr; ctx->d_text_cap = 0;
+        if (hipMalloc((void**)&ctx->d_text, total) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->d_text = nullptr;
+            ctx->set_err("device print: no memory for " + std::to_string(total) + " bytes of text");
+            return SX_E_NOMEM;
+        }
+        ctx->d_text_cap = total;
+    }
+    for (size_t i = 0; i < ns; i++) {
+        P[i].text = ctx->d_text;
+        HIP_TRY(ctx, print_write(P[i], st));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    *d_text = ctx->d_text;
+    *text_len = total;
+    return SX_OK;
+}
+
+int sx_result_select_device(sx_ctx* ctx, const sx_result* r, const sx_pattern* patterns, int n_patterns, uint32_t flags, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !patterns || !out) return SX_E_INVALID;
+    if (n_patterns < 1 || n_patterns > SX_SELECT_MAX_PATTERNS) { ctx->set_err("n_patterns must be 1..16"); return SX_E_INVALID; }
+    if (flags & ~(uint32_t)(SX_SELECT_ASCII_NOCASE | SX_SELECT_INVERT)) { ctx->set_err("unknown selection flags"); return SX_E_INVALID; }
+    for (int p = 0; p < n_patterns; p++)
+        if (!patterns[p].bytes || patterns[p].len < 1 || patterns[p].len > SX_SELECT_MAX_PATTERN_BYTES) { ctx->set_err("a pattern must have 1..64 bytes"); return SX_E_INVALID; }
+    if (host_only(ctx, "selection")) return SX_E_STATE;
+    { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
+    Selection sel(r->r.segs.size());
+    select_fill_patterns(&sel.pat, patterns, n_patterns, flags);
+    return select_on_device(ctx, r, sel, out);
+}
+
+int sx_select_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_set** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !out) return SX_E_INVALID;
+    SelsetTable T;
+    std::string err;
+    { const int rc = selset_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("pattern set: " + err); return rc; } }
+    uint8_t* mem = nullptr;
+    size_t at[3];
+    // (the kernels copy the LDS rows in 16-byte chunks: every set's table ends on one)
+    { const int rc = upload_set(ctx, "pattern set", { { T.map, sizeof T.map, 1 }, { T.next.data(), T.next.size(), 16 } }, 0, &mem, at); if (rc != SX_OK) return rc; }
+    sx_select_set* set = new_handle<sx_select_set>(ctx, mem);
+    if (!set) return SX_E_NOMEM;
+    set->dev = SelsetDevice{ mem, mem + at[1], T.states, T.classes, T.lds_states, T.matched, T.entry_bytes, 0 };
+    set->info = sx_select_set_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)T.next.size(), T.lds_states, 0 };
+    *out = set;
+    return SX_OK;
+}
+int sx_select_set_info_get(const sx_select_set* set, sx_select_set_info* out) { return handle_info(set, out); }
+void sx_select_set_free(sx_select_set* set) { handle_free(set); }
+
+int sx_result_select_set_device(sx_ctx* ctx, const sx_result* r, const sx_select_set* set, uint32_t flags, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !set || !out) return SX_E_INVALID;
+    if (flags & ~(uint32_t)SX_SELECT_INVERT) { ctx->set_err("a pattern set is selected with SX_SELECT_INVERT or no flag: the fold is compiled into the set"); return SX_E_INVALID; }
+    if (host_only(ctx, "selection")) return SX_E_STATE;
+    if (on_another_device(ctx, *set, "the pattern set lies")) return SX_E_INVALID;
+    { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
+    Selection sel(r->r.segs.size());
+    sel.by.kind = SelectBy::kSet; sel.by.set = &set->dev;
+    sel.pat.invert = (flags & SX_SELECT_INVERT) ? 1u : 0u;
+    return select_on_device(ctx, r, sel, out);
+}
+
+int sx_select_regex_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_select_regex** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !out) return SX_E_INVALID;
+    SelreTable T;
+    std::string err;
+    { const int rc = selre_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("regex set: " + err); return rc; } }
+    const size_t bytes = T.next.size() * sizeof(uint16_t);
+    uint8_t* mem = nullptr;
+    size_t at[3];
+    { const int rc = upload_set(ctx, "regex set", { { T.map, sizeof T.map, 1 }, { T.next.data(), bytes, 16 } }, 0, &mem, at); if (rc != SX_OK) return rc; }
+    sx_select_regex* re = new_handle<sx_select_regex>(ctx, mem);
+    if (!re) return SX_E_NOMEM;
+    re->dev = SelreDevice{ mem, (const uint16_t*)(mem + at[1]), T.states, T.classes, T.lds_states, T.end_first, T.stop_first, T.matched, T.root_end, 0 };
+    re->info = sx_select_regex_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)bytes, T.lds_states, T.end_states };
+    *out = re;
+    return SX_OK;
+}
+int sx_select_regex_info_get(const sx_select_regex* re, sx_select_regex_info* out) { return handle_info(re, out); }
+void sx_select_regex_free(sx_select_regex* re) { handle_free(re); }
+
+int sx_result_select_regex_device(sx_ctx* ctx, const sx_result* r, const sx_select_regex* re, uint32_t flags, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !re || !out) return SX_E_INVALID;
+    if (flags & ~(uint32_t)SX_SELECT_INVERT) { ctx->set_err("a regex set is selected with SX_SELECT_INVERT or no flag: the fold is compiled into the set"); return SX_E_INVALID; }
+    if (host_only(ctx, "selection")) return SX_E_STATE;
+    if (on_another_device(ctx, *re, "the regex set lies")) return SX_E_INVALID;
+    { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
+    Selection sel(r->r.segs.size());
+    sel.by.kind = SelectBy::kRegex; sel.by.re = &re->dev;
+    sel.pat.invert = (flags & SX_SELECT_INVERT) ? 1u : 0u;
+    return select_on_device(ctx, r, sel, out);
+}
+
+int sx_extract_regex_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_extract_regex** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !out) return SX_E_INVALID;
+    ExtractTable T;
+    std::string err;
+    { const int rc = extract_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("extract set: " + err); return rc; } }
+    const size_t bytes = T.next.size() * sizeof(uint16_t);
+    uint8_t* mem = nullptr;
+    size_t at[3];
+    { const int rc = upload_set(ctx, "extract set", { { T.map, sizeof T.map, 1 }, { T.next.data(), bytes, 16 } }, 0, &mem, at); if (rc != SX_OK) return rc; }
+    sx_extract_regex* ex = new_handle<sx_extract_regex>(ctx, mem);
+    if (!ex) return SX_E_NOMEM;
+    ex->dev = ExtractDevice{ mem, (const uint16_t*)(mem + at[1]), T.states, T.classes, T.lds_states, T.end_first, T.here_first, T.dead_first, T.start0, T.start1 };
+    ex->info = sx_extract_regex_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)bytes, T.lds_states, 0 };
+    *out = ex;
+    return SX_OK;
+}
+int sx_extract_regex_info_get(const sx_extract_regex* ex, sx_extract_regex_info* out) { return handle_info(ex, out); }
+void sx_extract_regex_free(sx_extract_regex* ex) { handle_free(ex); }
+
+int sx_result_extract_regex_device(sx_ctx* ctx, const sx_result* r, const sx_extract_regex* ex, uint32_t flags, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !ex || !out) return SX_E_INVALID;
+    if (flags) { ctx->set_err("an extraction takes no flag: the fold is compiled into the set"); return SX_E_INVALID; }
+    if (host_only(ctx, "extraction")) return SX_E_STATE;
+    if (on_another_device(ctx, *ex, "the extract set lies")) return SX_E_INVALID;
+    { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
+    Extraction x(ex->dev, r->r.segs.size());
+    return select_on_device(ctx, r, x, out);
+}
+
+int sx_tally_set_reset(sx_tally_set* set) {
+    if (!set) return SX_E_INVALID;
+    return reset_counters(set->device, set->dev.hits, set->dev.first, set->dev.unique);
+}
+
+int sx_tally_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_tally_set** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !out) return SX_E_INVALID;
+    SeltallyTable T;
+    std::string err;
+    { const int rc = seltally_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("tally set: " + err); return rc; } }
+    const size_t per_state = (size_t)T.states * sizeof(uint32_t), map_bytes = (size_t)T.n_patterns * sizeof(uint32_t), counters = (size_t)T.unique * sizeof(uint64_t);
+    uint8_t* mem = nullptr;
+    size_t at[6];
+    // (the counters are 64-bit words: the pattern -> unique id map in front of them ends on 8 bytes)
+    { const int rc = upload_set(ctx, "tally set", { { T.map, sizeof T.map, 1 }, { T.next.data(), T.next.size(), 16 }, { T.own.data(), per_state, 1 }, { T.dict.data(), per_state, 1 },
+                                                    { T.unique_of_pattern.data(), map_bytes, 8 } }, 2 * counters, &mem, at); if (rc != SX_OK) return rc; }
+    sx_tally_set* set = new_handle<sx_tally_set>(ctx, mem);
+    if (!set) return SX_E_NOMEM;
+    set->dev = SeltallyDevice{ mem, mem + at[1], (const uint32_t*)(mem + at[2]), (const uint32_t*)(mem + at[3]),
+                               (uint64_t*)(mem + at[5]), (uint64_t*)(mem + at[5] + counters),
+                               T.states, T.classes, T.lds_states, T.entry_bytes, T.unique, T.unique < kSeltallyLdsIds ? T.unique : kSeltallyLdsIds };
+    set->d_unique_of_pattern = (const uint32_t*)(mem + at[4]);
+    set->info = sx_tally_set_info{ T.n_patterns, T.unique, T.states, T.classes, T.nocase, T.entry_bytes,
+                                   (uint64_t)(sizeof T.map + T.next.size() + 2 * per_state + map_bytes), T.lds_states, 0 };
+    set->unique_of_pattern = std::move(T.unique_of_pattern);
+    if (sx_tally_set_reset(set) != SX_OK) { ctx->set_err("tally set: the counters could not be reset"); sx_tally_set_free(set); return SX_E_HIP; }
+    *out = set;
+    return SX_OK;
+}
+int sx_tally_set_info_get(const sx_tally_set* set, sx_tally_set_info* out) { return handle_info(set, out); }
+void sx_tally_set_free(sx_tally_set* set) { handle_free(set); }
+
+// The tally where the findings lie (sx_seltally_dev.hip): the source is checked as a whole, then one kernel per segment, each with the
+// ordinal of its first record, on the selections' stream, and one wait.  Only the set's counters are written.
+int sx_result_tally_device(sx_ctx* ctx, const sx_result* r, sx_tally_set* set, uint64_t ordinal_base, uint64_t* n_findings) {
+    if (n_findings) *n_findings = 0;
+    if (!ctx || !r || !set) return SX_E_INVALID;
+    if (host_only(ctx, "tally")) return SX_E_STATE;
+    if (on_another_device(ctx, *set, "the tally set lies")) return SX_E_INVALID;
+    { const int rc = result_on_device(ctx, r, "count on the host"); if (rc != SX_OK) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    uint64_t walked = 0;
+    for (const MissionFindings& s : r->r.segs) {
+        SeltallyParams p = params_of<SeltallyParams>(seg_ref(s));
+        p.ordinal = ordinal_base + walked;
+        p.set = set->dev;
+        HIP_TRY(ctx, seltally_launch(p, st));
+        walked += s.ext_nf;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (n_findings) *n_findings = walked;
+    return SX_OK;
+}
+
+int sx_tally_set_read(const sx_tally_set* set, uint64_t* hits, uint64_t* first, uint32_t n_patterns) {
+    if (!set || n_patterns != set->info.n_patterns) return SX_E_INVALID;
+    std::vector<uint64_t> u(set->dev.unique);
+    for (int k = 0; k < 2; k++) {
+        uint64_t* out = k ? first : hits;
+        if (!out) continue;
+        { const int rc = read_counters(set->device, k ? set->dev.first : set->dev.hits, u.data(), u.size()); if (rc != SX_OK) return rc; }
+        for (uint32_t p = 0; p < n_patterns; p++) out[p] = u[set->unique_of_pattern[p]];
+    }
+    return SX_OK;
+}
+
+int sx_tally_set_counters_device(const sx_tally_set* set, const uint64_t** d_hits, const uint64_t** d_first,
+                                 const uint32_t** d_unique_of_pattern, uint32_t* unique) {
+    if (!set) return SX_E_INVALID;
+    if (d_hits) *d_hits = set->dev.hits;
+    if (d_first) *d_first = set->dev.first;
+    if (d_unique_of_pattern) *d_unique_of_pattern = set->d_unique_of_pattern;
+    if (unique) *unique = set->dev.unique;
+    return SX_OK;
+}
+
+int sx_label_set_reset(sx_label_set* set) {
+    if (!set) return SX_E_INVALID;
+    return reset_counters(set->device, set->dev.findings, set->dev.first, kLabelBits);
+}
+
+int sx_label_set_create(sx_ctx* ctx, const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, sx_label_set** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !out) return SX_E_INVALID;
+    LabelTable T;
+    std::string err;
+    { const int rc = label_build(patterns, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("label set: " + err); return rc; } }
+    const size_t next_bytes = T.next.size() * sizeof(uint16_t), here_bytes = T.here.size() * sizeof(uint64_t), end_bytes = T.end.size() * sizeof(uint64_t);
+    const size_t counters = kLabelBits * sizeof(uint64_t);
+    uint8_t* mem = nullptr;
+    size_t at[5];
+    { const int rc = upload_set(ctx, "label set", { { T.map, sizeof T.map, 1 }, { T.next.data(), next_bytes, 16 }, { T.here.data(), here_bytes, 1 }, { T.end.data(), end_bytes, 1 } },
+                                2 * counters, &mem, at); if (rc != SX_OK) return rc; }
+    sx_label_set* set = new_handle<sx_label_set>(ctx, mem);
+    if (!set) return SX_E_NOMEM;
+    set->dev = LabelDevice{ mem, (const uint16_t*)(mem + at[1]), (const uint64_t*)(mem + at[2]), (const uint64_t*)(mem + at[3]),
+                            (uint64_t*)(mem + at[4]), (uint64_t*)(mem + at[4] + counters), T.root_here, T.all,
+                            T.states, T.classes, T.lds_states, T.here_first, T.dead, T.n_patterns };
+    set->info = sx_label_set_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)(sizeof T.map + next_bytes + here_bytes + end_bytes), T.lds_states, (uint32_t)T.here.size() };
+    if (sx_label_set_reset(set) != SX_OK) { ctx->set_err("label set: the counters could not be reset"); sx_label_set_free(set); return SX_E_HIP; }
+    *out = set;
+    return SX_OK;
+}
+int sx_label_set_info_get(const sx_label_set* set, sx_label_set_info* out) { return handle_info(set, out); }
+void sx_label_set_free(sx_label_set* set) { handle_free(set); }
+
+int sx_label_set_read(const sx_label_set* set, uint64_t* findings, uint64_t* first, uint32_t n_patterns) {
+    if (!set || n_patterns != set->info.n_patterns) return SX_E_INVALID;
+    const int rc = read_counters(set->device, set->dev.findings, findings, n_patterns);
+    return rc != SX_OK ? rc : read_counters(set->device, set->dev.first, first, n_patterns);
+}
+
+int sx_label_set_counters_device(const sx_label_set* set, const uint64_t** d_findings, const uint64_t** d_first) {
+    if (!set) return SX_E_INVALID;
+    if (d_findings) *d_findings = set->dev.findings;
+    if (d_first) *d_first = set->dev.first;
+    return SX_OK;
+}
+
+// The labels where the findings lie (sx_label_dev.hip): the source is checked as a whole, the labels' memory is had, then one kernel per
+// segment, each with the ordinal of its first record, on the selections' stream, and one wait.  Only the labels and the set's counters
+// are written.
+int sx_result_label_device(sx_ctx* ctx, const sx_result* r, sx_label_set* set, uint64_t ordinal_base, sx_labels** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !set || !out) return SX_E_INVALID;
+    if (host_only(ctx, "labels")) return SX_E_STATE;
+    if (on_another_device(ctx, *set, "the label set lies")) return SX_E_INVALID;
+    { const int rc = result_on_device(ctx, r, "label on the host"); if (rc != SX_OK) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    sx_labels* lab = new (std::nothrow) sx_labels;
+    if (!lab) return SX_E_NOMEM;
+    lab->device = ctx->device;
+    uint64_t bytes = 0;
+    for (const MissionFindings& s : r->r.segs) bytes += up256(s.ext_nf * sizeof(uint64_t));
+    if (hipMalloc((void**)&lab->mem, bytes ? bytes : 256) != hipSuccess) {
+        (void)hipGetLastError();
+        delete lab;
+        ctx->set_err("device labels: no memory for " + std::to_string(bytes) + " bytes of labels");
+        return SX_E_NOMEM;
+    }
+    uint64_t walked = 0, at = 0;
+    hipError_t e = hipSuccess;
+    for (const MissionFindings& s : r->r.segs) {
+        sx_labels::Seg seg;
+        seg.d = (const uint64_t*)(lab->mem + at); seg.recs = s.dev_copy; seg.n = s.ext_nf; seg.epoch_ref = s.dev_epoch_ref; seg.epoch = s.dev_epoch;
+        lab->segs.push_back(seg);
+        LabelParams p = params_of<LabelParams>(seg_ref(s));
+        p.ordinal = ordinal_base + walked;
+        p.labels = (uint64_t*)(lab->mem + at);
+        p.set = set->dev;
+        e = label_launch(p, st);
+        if (e != hipSuccess) break;
+        walked += s.ext_nf;
+        at += up256(s.ext_nf * sizeof(uint64_t));
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) {
+        sx_labels_free(lab);
+        ctx->set_err(std::string("device labels: ") + hipGetErrorString(e));
+        return SX_E_HIP;
+    }
+    *out = lab;
+    return SX_OK;
+}
+
+uint64_t sx_labels_segments(const sx_labels* labels) { return labels ? labels->segs.size() : 0; }
+
+int sx_labels_segment_device(const sx_labels* labels, uint64_t segment, const uint64_t** d_labels, uint64_t* n_findings) {
+    if (d_labels) *d_labels = nullptr;
+    if (n_findings) *n_findings = 0;
+    if (!labels || segment >= labels->segs.size()) return SX_E_INVALID;
+    if (d_labels) *d_labels = labels->segs[segment].d;
+    if (n_findings) *n_findings = labels->segs[segment].n;
+    return SX_OK;
+}
+
+void sx_labels_free(sx_labels* labels) { handle_free(labels); }
+
+int sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels, uint64_t any, uint64_t all, uint64_t none, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !labels || !out) return SX_E_INVALID;
+    if (host_only(ctx, "selection")) return SX_E_STATE;
+    if (on_another_device(ctx, *labels, "the labels lie")) return SX_E_INVALID;
+    { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
+    // the labels are this result's: segment by segment the same records, in a block that has not been written since
+    bool same = labels->segs.size() == r->r.segs.size();
+    for (size_t i = 0; same && i < labels->segs.size(); i++) {
+        const sx_labels::Seg& l = labels->segs[i];
+        const MissionFindings& s = r->r.segs[i];
+        same = l.recs == s.dev_copy && l.n == s.ext_nf && l.epoch_ref == s.dev_epoch_ref && l.epoch == s.dev_epoch;
+    }
+    if (!same) { ctx->set_err("the labels were not made from this result"); return SX_E_INVALID; }
+    Selection sel(r->r.segs.size());
+    sel.by.kind = SelectBy::kLabels;
+    sel.labels = labels;
+    sel.masks[0] = any; sel.masks[1] = all; sel.masks[2] = none;
+    return select_on_device(ctx, r, sel, out);
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "sx_device.hpp"
+#include "sx_rows_dev.hpp"
 
 #define SXD __device__ __forceinline__
 #include "sx_select_core.hpp"
@@ -33,11 +34,7 @@ __global__ __launch_bounds__(64 * kSelectWaves) void select_match_kernel(SelectP
     else select_walk_lane(P, first, lane, offs[wv], lens[wv], hit[wv]);
     __syncthreads();
     const bool sel = select_lane_selected(P, w, lane, hit[wv]);
-    const uint64_t mask = __ballot(sel ? 1 : 0);
-    uint64_t bytes = sel ? lens[wv][lane] : 0u;
-#pragma unroll
-    for (int d = 32; d; d >>= 1) bytes += __shfl_xor(bytes, d, 64);
-    if (lane == 0 && w <= waves) { P.wmask[w] = mask; P.wcount[w] = (uint32_t)__popcll(mask); P.wbytes[w] = bytes; }
+    if (w <= waves) wave_store_selected(P.wmask, P.wcount, P.wbytes, w, sel, lens[wv][lane]);      // (a whole wavefront)
 }
 
 __global__ __launch_bounds__(64 * kSelectWaves) void select_place_kernel(SelectParams P) {
@@ -45,7 +42,6 @@ __global__ __launch_bounds__(64 * kSelectWaves) void select_place_kernel(SelectP
     select_place_lane(P, i / kSelectRecs, (uint32_t)(i % kSelectRecs));
 }
 
-static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 static size_t select_scan_bytes(uint64_t items) {
     size_t a = 0, b = 0;
     (void)rocprim::exclusive_scan(nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)items, rocprim::plus<uint32_t>(), (hipStream_t)0);
@@ -60,11 +56,8 @@ size_t select_scratch_bytes(uint64_t n) {
 
 // Pass 1 of a segment (P.wbase, P.out_recs, P.out_src are not read): fills P.wmask / wcount / wbytes / wbase with places inside
 // `scratch`; *count and *bytes: the device words that will hold the number of selected records and their string bytes, valid when
-// `stream` has run this far.  set: NULL = P.pat's patterns (select_match_kernel); else a compiled set, whose kernel
-// (sx_selset_dev.hip) fills the same per-wavefront words, and of P.pat only `invert` counts; re: the same for a compiled regex set
-// (sx_selre_dev.hip); pick: the same for the segment's labels and three masks (sx_label_dev.hip).  At most one of the three.
-hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreDevice* re, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes,
-                          const LabelPick* pick) {
+// `stream` has run this far.  by: what the pass looks for (sx_device.hpp); the other kinds' kernels fill the same per-wavefront words.
+hipError_t select_measure(SelectParams* P, const SelectBy& by, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes) {
     if (P->n == 0 || P->n >= 0xFFFFFFFFull || scratch_bytes < select_scratch_bytes(P->n) || ((uintptr_t)scratch & 255)) return hipErrorInvalidValue;
     const uint64_t waves = (P->n + kSelectRecs - 1) / kSelectRecs;
     const size_t w8 = up256((size_t)(waves + 1) * 8), w4 = up256((size_t)(waves + 1) * 4);
@@ -76,11 +69,11 @@ hipError_t select_measure(SelectParams* P, const SelsetDevice* set, const SelreD
     uint32_t* wbase = (uint32_t*)at; at += w4;
     size_t tmp_bytes = scratch_bytes - (size_t)(at - (uint8_t*)scratch);
     hipError_t e;
-    if ((set ? 1 : 0) + (re ? 1 : 0) + (pick ? 1 : 0) > 1) return hipErrorInvalidValue;
-    if (pick) e = label_launch_pick(*P, *pick, waves, stream);
-    else if (set) e = selset_launch_match(*P, *set, waves, stream);
-    else if (re) e = selre_launch_match(*P, *re, waves, stream);
-    else {
+    switch (by.kind) {
+    case SelectBy::kLabels: e = by.pick ? label_launch_pick(*P, *by.pick, waves, stream) : hipErrorInvalidValue; break;
+    case SelectBy::kSet: e = by.set ? selset_launch_match(*P, *by.set, waves, stream) : hipErrorInvalidValue; break;
+    case SelectBy::kRegex: e = by.re ? selre_launch_match(*P, *by.re, waves, stream) : hipErrorInvalidValue; break;
+    default:
         hipLaunchKernelGGL(select_match_kernel, dim3((unsigned)((waves + 1 + kSelectWaves - 1) / kSelectWaves)), dim3(64 * kSelectWaves), 0, stream, *P, waves);
         e = hipGetLastError();
     }

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sx_device.hpp"
+#include "sx_rows_dev.hpp"
 
 #define SXD __device__ __forceinline__
 #include "sx_selset_build.hpp"
@@ -13,51 +14,35 @@
 
 namespace sx {
 
-constexpr uint32_t kSelsetWaves = 8;          // wavefronts per workgroup, which share the rows in LDS
-constexpr uint32_t kSelsetGroupsPerCu = 3;    // 3 x (48 KiB of rows + the map) <= 160 KiB; 24 wavefronts per CU
-
-struct alignas(16) Selset16 { uint32_t w[4]; };
-
 // wavefronts [0, waves]: the last one (behind the last record) selects nothing, as in select_match_kernel
 template <class E>
-__global__ __launch_bounds__(64 * kSelsetWaves) void selset_match_kernel(SelsetParams P, uint64_t waves) {
+__global__ __launch_bounds__(64 * kRowsWaves) void selset_match_kernel(SelsetParams P, uint64_t waves) {
     __shared__ uint8_t map[256];
-    __shared__ Selset16 rows16[kSelsetLdsBytes / 16];
-    if (threadIdx.x < 256 / 4) ((uint32_t*)map)[threadIdx.x] = ((const uint32_t*)P.set.map)[threadIdx.x];
-    // (the table's allocation is a multiple of 16 bytes)
-    const uint32_t chunks = (P.set.lds_states * P.set.classes * (uint32_t)sizeof(E) + 15u) / 16u;
-    for (uint32_t c = threadIdx.x; c < chunks; c += 64 * kSelsetWaves) rows16[c] = ((const Selset16*)P.set.next)[c];
-    __syncthreads();
+    __shared__ Rows16 rows16[kSelsetLdsBytes / 16];
+    rows_load(P.set.map, P.set.next, P.set.lds_states, P.set.classes, (uint32_t)sizeof(E), map, rows16);
     const E* rows = (const E*)rows16;
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    for (uint64_t w = (uint64_t)blockIdx.x * kSelsetWaves + wv; w <= waves; w += (uint64_t)gridDim.x * kSelsetWaves) {
+    for (uint64_t w = (uint64_t)blockIdx.x * kRowsWaves + wv; w <= waves; w += (uint64_t)gridDim.x * kRowsWaves) {
         SelsetLane L = selset_begin_lane(P, w, lane);
         while (__ballot(L.active ? 1 : 0) != 0)
             if (L.active) selset_step_lane<E>(P, map, rows, L);
         const bool sel = selset_lane_selected(P, w, lane, L);
-        const uint64_t mask = __ballot(sel ? 1 : 0);
-        uint64_t bytes = sel ? L.len : 0u;
-#pragma unroll
-        for (int d = 32; d; d >>= 1) bytes += __shfl_xor(bytes, d, 64);
-        if (lane == 0) { P.wmask[w] = mask; P.wcount[w] = (uint32_t)__popcll(mask); P.wbytes[w] = bytes; }
+        wave_store_selected(P.wmask, P.wcount, P.wbytes, w, sel, L.len);
     }
 }
 
 // Pass 1 of a segment with a set: S = the segment and the per-wavefront tables of a SelectParams that select_measure has laid out.
 hipError_t selset_launch_match(const SelectParams& S, const SelsetDevice& set, uint64_t waves, hipStream_t stream) {
-    if (set.entry_bytes != 2 && set.entry_bytes != 4) return hipErrorInvalidValue;
-    if ((uint64_t)set.lds_states * set.classes * set.entry_bytes > kSelsetLdsBytes || set.lds_states > set.states) return hipErrorInvalidValue;
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
+    hipError_t e = rows_check(set.classes, set.states, set.lds_states, set.entry_bytes, kSelsetLdsBytes);
     if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    dim3 grid;
+    e = rows_grid(waves + 1, kRowsWaves, kRowsGroupsPerCu, &grid);
     if (e != hipSuccess) return e;
     SelsetParams P{};
     P.recs = S.recs; P.arena = S.arena; P.n = S.n; P.packed = S.packed; P.invert = S.pat.invert;
     P.wmask = S.wmask; P.wcount = S.wcount; P.wbytes = S.wbytes;
     P.set = set;
-    const uint64_t groups = (waves + 1 + kSelsetWaves - 1) / kSelsetWaves, most = (uint64_t)(cus > 0 ? cus : 1) * kSelsetGroupsPerCu;
-    const dim3 grid((unsigned)(groups < most ? groups : most)), block(64 * kSelsetWaves);
+    const dim3 block(64 * kRowsWaves);
     if (set.entry_bytes == 2) hipLaunchKernelGGL(selset_match_kernel<uint16_t>, grid, block, 0, stream, P, waves);
     else hipLaunchKernelGGL(selset_match_kernel<uint32_t>, grid, block, 0, stream, P, waves);
     return hipGetLastError();

@@ -9,62 +9,21 @@
 
 #include <new>
 
+#include "sx_keyword_front.hpp"
+
 namespace sx {
 
-namespace {
-
-struct TallyNode { uint32_t child, sibling; uint8_t cls, ends; };   // child / sibling: 0 = none (the root is nobody's child)
-
-int tally_fail(std::string* err, const char* what) { if (err) *err = what; return SX_E_INVALID; }
-
-}  // namespace
-
 int seltally_build(const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, SeltallyTable* out, std::string* err) {
-    if (!patterns || !out) return tally_fail(err, "a NULL pointer");
-    if (n_patterns < 1 || n_patterns > SX_SELECT_SET_MAX_PATTERNS) return tally_fail(err, "n_patterns must be 1..65536");
-    if (flags & ~(uint32_t)SX_SELECT_ASCII_NOCASE) return tally_fail(err, "a tally set takes SX_SELECT_ASCII_NOCASE and no other flag");
     uint64_t total = 0;
-    for (uint32_t p = 0; p < n_patterns; p++) {
-        if (!patterns[p].bytes || patterns[p].len < 1 || patterns[p].len > SX_SELECT_SET_MAX_PATTERN_BYTES) return tally_fail(err, "a pattern must have 1..255 bytes");
-        total += patterns[p].len;
-    }
-    if (total > SX_SELECT_SET_MAX_TOTAL_BYTES) return tally_fail(err, "the patterns' lengths must sum to at most 1 MiB");
+    { const int rc = kwfront::check("tally set", patterns, n_patterns, flags, out, &total, err); if (rc != SX_OK) return rc; }
     const bool nocase = (flags & SX_SELECT_ASCII_NOCASE) != 0;
-    auto folded = [nocase](uint32_t x) { return nocase && x - 'A' < 26u ? x | 0x20u : x; };
     try {
         SeltallyTable T;
         T.n_patterns = n_patterns; T.nocase = nocase ? 1u : 0u;
-        // the classes
-        bool used[256] = {};
-        for (uint32_t p = 0; p < n_patterns; p++)
-            for (uint32_t j = 0; j < patterns[p].len; j++) used[folded(patterns[p].bytes[j])] = true;
-        bool any_unused = false;
-        for (uint32_t x = 0; x < 256; x++) any_unused |= !used[folded(x)];
-        uint32_t classes = any_unused ? 1u : 0u;
-        for (uint32_t x = 0; x < 256; x++) if (used[x]) T.map[x] = (uint8_t)classes++;
-        for (uint32_t x = 0; x < 256; x++) if (!used[x]) T.map[x] = used[folded(x)] ? T.map[folded(x)] : 0;
-        T.classes = classes;
-        // the trie: a node per distinct prefix; ends_at[p] = the node pattern p ends in
-        std::vector<TallyNode> trie;
-        std::vector<uint32_t> ends_at(n_patterns);
-        trie.reserve((size_t)total + 1);
-        trie.push_back(TallyNode{ 0, 0, 0, 0 });
-        for (uint32_t p = 0; p < n_patterns; p++) {
-            uint32_t u = 0;
-            for (uint32_t j = 0; j < patterns[p].len; j++) {
-                const uint8_t c = T.map[patterns[p].bytes[j]];
-                uint32_t v = trie[u].child;
-                while (v && trie[v].cls != c) v = trie[v].sibling;
-                if (!v) {
-                    v = (uint32_t)trie.size();
-                    trie.push_back(TallyNode{ 0, trie[u].child, c, 0 });
-                    trie[u].child = v;
-                }
-                u = v;
-            }
-            trie[u].ends = 1;
-            ends_at[p] = u;
-        }
+        const uint32_t classes = T.classes = kwfront::classes(patterns, n_patterns, nocase, T.map);
+        // whole: a node per distinct prefix; ends_at[p] = the node pattern p ends in
+        std::vector<uint32_t> ends_at;
+        const std::vector<kwfront::TrieNode> trie = kwfront::trie(patterns, n_patterns, T.map, total, false, &ends_at);
         // breadth first: state s is the trie node queue[s]; fails[s] its failure state; state_of[node] the other way round
         const size_t states = trie.size();
         std::vector<uint32_t> queue, fails, next, state_of(states, 0);

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sx_device.hpp"
+#include "sx_rows_dev.hpp"
 
 #define SXD __device__ __forceinline__
 #include "sx_seltally_build.hpp"
@@ -14,49 +15,37 @@
 
 namespace sx {
 
-constexpr uint32_t kSeltallyWaves = 8;          // wavefronts per workgroup, which share the rows and the counters in LDS
-constexpr uint32_t kSeltallyGroupsPerCu = 3;    // 3 x 49 408 bytes <= 160 KiB; 24 wavefronts per CU
-
-struct alignas(16) Seltally16 { uint32_t w[4]; };
-
 // wavefronts [0, waves): waves = ceil(n / 64)
 template <class E>
-__global__ __launch_bounds__(64 * kSeltallyWaves) void seltally_kernel(SeltallyParams P, uint64_t waves) {
+__global__ __launch_bounds__(64 * kRowsWaves) void seltally_kernel(SeltallyParams P, uint64_t waves) {
     __shared__ uint8_t map[256];
-    __shared__ Seltally16 rows16[kSeltallyLdsBytes / 16];
+    __shared__ Rows16 rows16[kSeltallyLdsBytes / 16];
     __shared__ uint32_t counts[kSeltallyLdsIds];
-    if (threadIdx.x < 256 / 4) ((uint32_t*)map)[threadIdx.x] = ((const uint32_t*)P.set.map)[threadIdx.x];
-    // (the table's allocation is a multiple of 16 bytes)
-    const uint32_t chunks = (P.set.lds_states * P.set.classes * (uint32_t)sizeof(E) + 15u) / 16u;
-    for (uint32_t c = threadIdx.x; c < chunks; c += 64 * kSeltallyWaves) rows16[c] = ((const Seltally16*)P.set.next)[c];
-    for (uint32_t c = threadIdx.x; c < P.set.lds_ids; c += 64 * kSeltallyWaves) counts[c] = 0;
-    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < P.set.lds_ids; c += 64 * kRowsWaves) counts[c] = 0;
+    rows_load(P.set.map, P.set.next, P.set.lds_states, P.set.classes, (uint32_t)sizeof(E), map, rows16);
     const E* rows = (const E*)rows16;
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    for (uint64_t w = (uint64_t)blockIdx.x * kSeltallyWaves + wv; w < waves; w += (uint64_t)gridDim.x * kSeltallyWaves) {
+    for (uint64_t w = (uint64_t)blockIdx.x * kRowsWaves + wv; w < waves; w += (uint64_t)gridDim.x * kRowsWaves) {
         SeltallyLane L = seltally_begin_lane(P, w, lane);
         while (__ballot(L.active ? 1 : 0) != 0)
             if (L.active) seltally_step_lane<E>(P, map, rows, counts, L);
     }
     __syncthreads();
-    for (uint32_t c = threadIdx.x; c < P.set.lds_ids; c += 64 * kSeltallyWaves) seltally_flush_lane(P, counts, c);
+    for (uint32_t c = threadIdx.x; c < P.set.lds_ids; c += 64 * kRowsWaves) seltally_flush_lane(P, counts, c);
 }
 
 // The tally of one segment: P = the segment, its first record's ordinal and the set.
 hipError_t seltally_launch(const SeltallyParams& P, hipStream_t stream) {
     const SeltallyDevice& set = P.set;
-    if (set.entry_bytes != 2 && set.entry_bytes != 4) return hipErrorInvalidValue;
-    if ((uint64_t)set.lds_states * set.classes * set.entry_bytes > kSeltallyLdsBytes || set.lds_states > set.states) return hipErrorInvalidValue;
+    hipError_t e = rows_check(set.classes, set.states, set.lds_states, set.entry_bytes, kSeltallyLdsBytes);
+    if (e != hipSuccess) return e;
     if (set.lds_ids > kSeltallyLdsIds || set.lds_ids > set.unique) return hipErrorInvalidValue;
     if (P.n == 0) return hipSuccess;
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
     const uint64_t waves = (P.n + kSelectRecs - 1) / kSelectRecs;
-    const uint64_t groups = (waves + kSeltallyWaves - 1) / kSeltallyWaves, most = (uint64_t)(cus > 0 ? cus : 1) * kSeltallyGroupsPerCu;
-    const dim3 grid((unsigned)(groups < most ? groups : most)), block(64 * kSeltallyWaves);
+    dim3 grid;
+    e = rows_grid(waves, kRowsWaves, kRowsGroupsPerCu, &grid);
+    if (e != hipSuccess) return e;
+    const dim3 block(64 * kRowsWaves);
     if (set.entry_bytes == 2) hipLaunchKernelGGL(seltally_kernel<uint16_t>, grid, block, 0, stream, P, waves);
     else hipLaunchKernelGGL(seltally_kernel<uint32_t>, grid, block, 0, stream, P, waves);
     return hipGetLastError();

@@ -290,6 +290,7 @@ def test_labels_of_another_result_a_reused_source_and_a_host_only_context(case_d
         plain = sx.Scanner(d["ms"], device=0)
         host = plain.scan(d["data"], file_id=1)
         assert code_of(lambda: host.label_device(ls)) == sx.SX_E_STATE
+        assert code_of(lambda: host.select_device(lab, any=1)) == sx.SX_E_STATE     # in host memory, and not the labels' result: the first refusal wins
         host.free(); plain.close(); none.free()
         # a source whose block a later scan has reused: to label it and to select by its labels
         res2 = sc.scan(d["data"], file_id=1)

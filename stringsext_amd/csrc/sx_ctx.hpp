@@ -27,6 +27,7 @@
 
 #include "sx_host.hpp"
 #include "sx_switches.hpp"
+#include "sx_stage_b_plan.hpp"
 
 namespace sx {
 
@@ -38,7 +39,7 @@ extern int g_tl_on;
 #define SX_TL(...) do { if (sx::g_tl_on) { fprintf(stderr, "[tl %+8.3f] ", sx::now_ms() - sx::g_tl_t0); fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); } } while (0)
 
 // The long runs of one mission over one buffer: owned (host merge, caller-supplied) or a view
-// of the mission's pinned download buffer; `on_device` says MissionDev::d_rp[0] holds the same list.
+// of the mission's pinned download buffer; `on_device` says MissionDev::d_rp[kRpRuns] holds the same list.
 struct RunList {
     std::vector<sx_run> own;
     const sx_run* p = nullptr;
@@ -108,6 +109,26 @@ struct ScanSlot {
     uint64_t n_regions = 0;
     bool fused = false, fused_first = false;   // the launch in flight is a fused one (sx_fused.hip) shared with other Missions; ... and this is its first slot
 };
+// MissionDev::d_rp: a Mission's grow-only device buffers of stage B (ensure_rp)
+enum RpSlot : int {
+    kRpRuns = 0,          // the run list (stage A joins it there: RunList::on_device)
+    kRpRegionOut = 1,     // pass 1: a ReplayRegionOut per run
+    kRpIdx = 2,           // which regions stand (the stitch's flags, or the host's indices)
+    kRpFbase = 3,         // where each writes its findings ...
+    kRpAbase = 4,         // ... and its strings
+    kRpOut0 = 5,          // findings + strings as the result holds them (slab_out_*): two buffers in turn, this one ...
+    kRpStitchBlocks = 6,
+    kRpTotals = 7,        // kTotCount words
+    kRpOut1 = 8,          // ... and this one
+    kRpRunPieces = 9,     // the runs cut into a piece per window (sx_stage_a.cpp)
+    kRpWaveScratch = 10,  // the wave kernels' scratch when the Mission replays on a stream of its own
+    kRpCount = 12,
+    // the wave-cooperative path (sx_wave.cpp) never runs next to the lane-per-region path of the same Mission and reuses two slots:
+    kRpWaveTables = kRpRegionOut,   // per slab totals, per wavefront offsets and pass-1 words
+    kRpWaveDesc = kRpIdx,           // the lane-per-finding writer's descriptors
+};
+inline RpSlot rp_out_slot(uint64_t j) { return (j & 1) ? kRpOut1 : kRpOut0; }   // slab j's output buffer
+
 struct MissionDev {
     hipStream_t stream = nullptr;     // scan kernels only
     hipStream_t stream_b = nullptr;   // everything after them (sort/join, stage B, copies); higher priority
@@ -120,8 +141,8 @@ struct MissionDev {
     uint8_t* d_wave_lut = nullptr;                      // wave-cooperative stage B: Mission::wave_lut (uploaded at its first use)
     sx_run* h_runs = nullptr; uint64_t h_runs_cap = 0;   // pinned: runs joined on the device
     hipEvent_t ev_runs = nullptr;                         // their copy (on sx_ctx::d2h_stream) is done
-    void* d_rp[12] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };  // runs, region outs, idx, fbase, abase, findings+arena
-    uint64_t d_rp_cap[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };  // + stitch blocks, totals, pass-1 output cache, runs cut into pieces, the wave kernels' own scratch (10)
+    void* d_rp[kRpCount] = {};          // stage B's device buffers, by RpSlot
+    uint64_t d_rp_cap[kRpCount] = {};
     // the wave-cooperative stage B of a Mission that runs next to the other Missions' stage B (sx_schedule.cpp: a host thread each):
     // its own stream, totals in its own pinned words, its own timing events (4 per slab: count begin / end, write begin / end)
     hipStream_t stream_w = nullptr;
@@ -330,8 +351,8 @@ int stage_a_launch(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
                    const std::vector<uint32_t>& parity, const std::vector<uint64_t>& min_chars, int si);
 struct ReplayJob;
 int ensure_copy_stream(sx_ctx* ctx);   // sx_stage_b.cpp
-bool result_stays_on_device(const sx_ctx* ctx, const ReplayJob& job);   // sx_stage_b.cpp: SX_OPT_RESULT_ON_DEVICE, several Missions: this call qualifies
-int merge_drain(sx_ctx* ctx);          // sx_stage_b.cpp: waits for what device_merge left in flight (merge_async)
+bool result_stays_on_device(const sx_ctx* ctx, const ReplayJob& job);   // sx_merge.cpp: SX_OPT_RESULT_ON_DEVICE, several Missions: this call qualifies
+int merge_drain(sx_ctx* ctx);          // sx_merge.cpp: waits for what device_merge left in flight (merge_async)
 int slab_copy_drain(sx_ctx* ctx);      // sx_stage_b.cpp: waits for the copy device_replay_mission left in flight (the last slab's)
 int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_bytes, uint64_t len,
                    const std::vector<uint32_t>& parity, const std::vector<uint64_t>& min_chars, int si,
@@ -355,7 +376,56 @@ struct ReplayJob {
     const uint8_t* d_bytes = nullptr;   // the buffer in HBM, if stage B may run on the device
 };
 
+// SX_OPT_RESULT_ON_DEVICE with a single Mission: does its result stay where stage B wrote it?  (One block of the context's: the callers
+// replay in one slab then, and add what only they know.)  result_stays_on_device is the same question for several Missions.
+inline bool single_result_stays_on_device(const sx_ctx* ctx, const ReplayJob& job, uint64_t defer_min_bytes) {
+    return (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) && ctx->missions.size() == 1 && defer_min_bytes == 0 && job.commit_state &&
+           !ctx->sharded_call && ctx->single_piece;
+}
+// the list stays in the context's memory for the caller: valid while the context's epoch stands
+inline void keep_on_device(MissionFindings& mf, const sx_ctx* ctx) {
+    mf.dev_only = true; mf.keep_on_device = true; mf.dev_epoch_ref = ctx->dev_epoch; mf.dev_epoch = ctx->dev_epoch->load();
+}
+// what the packed records of this job's Missions [k0, k1) share
+inline std::shared_ptr<SegInfo> make_seg_info(const sx_ctx* ctx, const ReplayJob& job, size_t k0, size_t k1) {
+    auto si = std::make_shared<SegInfo>();
+    si->file_id = job.file_id; si->slice_base = job.slice_base;
+    for (auto& x : si->pos0) x = 0;
+    for (size_t k = k0; k < k1; k++) si->pos0[ctx->missions[k].c.mission_id] = job.consumed0[k];
+    return si;
+}
+// a Mission's slabs, in order, become out + out->more; out's replay_bytes stay
+inline void fold_slabs(MissionFindings* out, std::vector<MissionFindings>& slabs) {
+    if (slabs.empty()) return;
+    const uint64_t rb = out->replay_bytes;
+    *out = std::move(slabs[0]);
+    for (size_t j = 1; j < slabs.size(); j++) out->more.push_back(std::move(slabs[j]));
+    out->replay_bytes = rb;
+}
 
+// ---- a slab's output (sx_stage_b.cpp), shared by the lane-per-region path (device_replay_slab) and the wave path's slab loop.
+// Contract: the sequence of HIP calls issued per stream does not change — kernel launches, copies, memsets, event records and
+// waits, stream and event synchronisations, in their order and their arguments: these functions issue what each caller issued
+// when it had this code inline, the callers' launches sit between reserve and upload_entry.  The tail is optimised here, for both.
+struct SlabOutPath {                  // what differs between the callers
+    hipStream_t stream = nullptr;     // the Mission's stage-B stream
+    hipEvent_t written = nullptr, copied = nullptr;   // async: pass 2 is done (on `stream`; merge_copy_stream waits for it) / the copy is (on merge_copy_stream)
+    hipEvent_t reuse_after = nullptr; // a copy of an earlier slab reads this buffer until then (nullptr: none)
+    RpSlot slot = kRpOut0;
+    bool async_copy = false;          // the copy runs on merge_copy_stream next to the following slab's kernels
+    bool leaves_copy_running = false; // ... and is left to slab_copy_drain (sets slab_copy_pending); else the caller drains the streams
+    int copy_wgs = 0;                 // SX_REPLAY_COPY_WGS: a synchronous copy of 1 MiB or more as a kernel of so many workgroups
+};
+enum class SlabDest { Keep, Defer, Pinned };   // stays for the caller / waits in HBM for device_merge / travels to a pinned block
+int slab_strings_limit(sx_ctx* ctx, uint64_t string_bytes);   // SX_E_NOMEM + the text: more than str_off's 32 bits reach
+int slab_out_reserve(sx_ctx* ctx, MissionDev& d, const SlabOutPath& p, const plan::SlabOut& lay, uint8_t** d_all);
+int slab_out_upload_entry(sx_ctx* ctx, const SlabOutPath& p, const plan::SlabOut& lay, uint8_t* d_all, const void* recs, const void* strings);
+// deliver queues the copy (Pinned; *blk is set once taken, also when a later call fails); settle waits for what the host must not run
+// ahead of: everything unless the copy is asynchronous, and the entry part's upload (it reads host vectors)
+int slab_out_deliver(sx_ctx* ctx, const SlabOutPath& p, const plan::SlabOut& lay, SlabDest dest, const uint8_t* d_all, PinnedPool::Block* blk);
+int slab_out_settle(sx_ctx* ctx, const SlabOutPath& p, const plan::SlabOut& lay);
+void slab_out_describe(const sx_ctx* ctx, const SlabOutPath& p, const plan::SlabOut& lay, SlabDest dest, const PinnedPool::Block& blk,
+                       const uint8_t* d_all, MissionFindings* seg);
 
 
 // Missions whose stage B already ran (on the device, while later missions were still being scanned).
@@ -379,6 +449,10 @@ int device_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob
 int replay_all(sx_ctx* ctx, ByteView& bytes, const ReplayJob& job, const std::vector<RunList>& runs,
                Result* into, uint64_t* end_pos, PreReplayed* pre = nullptr);
 ReplayJob whole_chunk_job(sx_ctx* ctx, uint64_t len, int file_id, bool is_last);
+// the speculative parts the host replays Mission k's n_runs in (replay_all), and so what download_for_replay fetches for
+unsigned host_parts_wanted(const sx_ctx* ctx, size_t k, size_t n_runs);
+// sx_merge.cpp: several Missions' findings, all still in HBM, interleaved there (or nothing done: merge_findings takes them)
+int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFindings>& per, Result* into);
 int download_for_replay(sx_ctx* ctx, const uint8_t* d_bytes, uint64_t len,
                         const std::vector<RunList>* runs_opt, SparseDeviceBytes* view,
                         const ReplayJob& job, const std::vector<char>* skip = nullptr,

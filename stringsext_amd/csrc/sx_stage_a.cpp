@@ -300,11 +300,11 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
             const size_t sb = std::max(sort_scratch_bytes(nrec), merge_scratch_bytes(nrec));
             int rc = ensure_scratch(ctx, sb); if (rc != SX_OK) return rc;
             if (d.ev_runs) HIP_TRY(ctx, hipEventSynchronize(d.ev_runs));  // the previous list's copy (normally long done)
-            rc = ensure_rp(ctx, d, 0, (uint64_t)nrec * sizeof(sx_run)); if (rc != SX_OK) return rc;
+            rc = ensure_rp(ctx, d, kRpRuns, (uint64_t)nrec * sizeof(sx_run)); if (rc != SX_OK) return rc;
             if (!regions) HIP_TRY(ctx, sort_records(s.d_recs, nrec, len, ctx->d_scratch, ctx->d_scratch_cap, d.stream_b, ctx->sw.timing2));
             if (ctx->sw.timing2) { HIP_TRY(ctx, hipStreamSynchronize(d.stream_b)); fprintf(stderr, "[sx]   sort done +%.2f ms\n", now_ms() - tc0); }
             HIP_TRY(ctx, merge_sorted_records(d_records, nrec, min_chars[k], ctx->d_scratch, ctx->d_scratch_cap,
-                                              (sx_run*)d.d_rp[0], s.d_counters + 2, d.stream_b));
+                                              (sx_run*)d.d_rp[kRpRuns], s.d_counters + 2, d.stream_b));
             HIP_TRY(ctx, hipEventRecord(s.ev_free, d.stream_b));
             s.free_pending = true;
             if (ctx->sw.timing2) { HIP_TRY(ctx, hipStreamSynchronize(d.stream_b)); fprintf(stderr, "[sx]   join done +%.2f ms\n", now_ms() - tc0); }
@@ -312,7 +312,7 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
             { const int rb = read_back_sync(ctx, d, d.stream_b, &nruns32, s.d_counters + 2, 4); if (rb != SX_OK) return rb; }
             uint64_t nruns = nruns32;
             SX_TL("mission %d: joined (%u runs)", which[k], nruns32);
-            const sx_run* d_list = (const sx_run*)d.d_rp[0];
+            const sx_run* d_list = (const sx_run*)d.d_rp[kRpRuns];
             // Runs that cross window starts are cut into one piece per window where the state at those window
             // starts follows from the run alone (sx_replay_core.hpp kPieceCont): stage B then gets a region per
             // window instead of one serial replay per run (text: a run per line, most of them cross a window start).
@@ -327,10 +327,10 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
                 HIP_TRY(ctx, launch_split_count(SP, ctx->d_scratch + 64, ctx->d_scratch_cap - 64, d_total, d.stream_b));
                 uint64_t total = 0;
                 { const int rb = read_back_sync(ctx, d, d.stream_b, &total, d_total, 8); if (rb != SX_OK) return rb; }
-                if (total > nruns && total < (1ull << 32) && ensure_rp(ctx, d, 9, total * sizeof(sx_run)) == SX_OK) {
-                    HIP_TRY(ctx, launch_split_write(SP, ctx->d_scratch + 64, total, (sx_run*)d.d_rp[9], d.stream_b));
+                if (total > nruns && total < (1ull << 32) && ensure_rp(ctx, d, kRpRunPieces, total * sizeof(sx_run)) == SX_OK) {
+                    HIP_TRY(ctx, launch_split_write(SP, ctx->d_scratch + 64, total, (sx_run*)d.d_rp[kRpRunPieces], d.stream_b));
                     HIP_TRY(ctx, hipStreamSynchronize(d.stream_b));   // the list's copy for the host runs on another stream: complete first
-                    d_list = (const sx_run*)d.d_rp[9];
+                    d_list = (const sx_run*)d.d_rp[kRpRunPieces];
                     nruns = total;
                 } else (void)hipGetLastError();
             }

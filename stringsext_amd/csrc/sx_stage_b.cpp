@@ -1,16 +1,15 @@
 // sx_stage_b.cpp — stage B: the exact replay of FindingCollection::from around long runs, on the
-// device (regions, which of them stand, output offsets, interleaving of missions) and on the host
-// (entry/exit of every buffer, missions with few runs, regions the device gives back).
+// device (regions, which of them stand, output offsets) and on the host (entry/exit of every buffer,
+// missions with few runs, regions the device gives back).  The Missions' findings are interleaved by
+// sx_merge.cpp; the drivers' arithmetic is sx_stage_b_plan.hpp's.
 #include "sx_ctx.hpp"
 
 using namespace sx;
 
 namespace sx {
 
-static inline uint64_t win_start_h(uint64_t p, size_t W) {
-    const uint64_t s0 = p / kInputBufLen * kInputBufLen;
-    return s0 + (p - s0) / W * W;
-}
+static_assert(plan::kBufLen == kInputBufLen, "sx_stage_b_plan.hpp counts windows from the input buffers' grid");
+using plan::win_start_h;
 
 bool device_replay_wanted(const sx_ctx* ctx, const ReplayJob& job, size_t k, size_t n_runs) {
     if (!job.d_bytes || ctx->host_only || job.is_last || ctx->missions[k].host_sequential()) return false;
@@ -26,6 +25,65 @@ bool device_replay_wanted(const sx_ctx* ctx, const ReplayJob& job, size_t k, siz
     return (ctx->opt.flags & SX_OPT_DEVICE_REPLAY) || ctx->sw.device_replay || n_runs >= 4096;
 }
 
+// ---- a slab's output (the contract: sx_ctx.hpp)
+int slab_strings_limit(sx_ctx* ctx, uint64_t string_bytes) {
+    if (string_bytes <= 0xFFFFFFFFull) return SX_OK;
+    ctx->set_err("more than 4 GiB of strings in one chunk");
+    return SX_E_NOMEM;
+}
+
+// the slab's output buffer, large enough and free: a copy of an earlier slab may still read it — the stream waits, or the host if
+// the buffer must grow
+int slab_out_reserve(sx_ctx* ctx, MissionDev& d, const SlabOutPath& p, const plan::SlabOut& lay, uint8_t** d_all) {
+    if (p.reuse_after) {
+        if (d.d_rp_cap[p.slot] < lay.bytes + 64) HIP_TRY(ctx, hipEventSynchronize(p.reuse_after));
+        else HIP_TRY(ctx, hipStreamWaitEvent(p.stream, p.reuse_after, 0));
+    }
+    const int rc = ensure_rp(ctx, d, p.slot, lay.bytes + 64); if (rc) return rc;
+    *d_all = (uint8_t*)d.d_rp[p.slot];
+    return SX_OK;
+}
+
+// the host's entry part (a few findings) goes in front of what the device writes: the missions can be interleaved on the device
+int slab_out_upload_entry(sx_ctx* ctx, const SlabOutPath& p, const plan::SlabOut& lay, uint8_t* d_all, const void* recs, const void* strings) {
+    if (!lay.nfh) return SX_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(d_all, recs, lay.nfh * lay.rec, hipMemcpyHostToDevice, p.stream));
+    if (lay.nbh) HIP_TRY(ctx, hipMemcpyAsync(d_all + lay.host_s, strings, lay.nbh, hipMemcpyHostToDevice, p.stream));
+    return SX_OK;
+}
+
+int slab_out_deliver(sx_ctx* ctx, const SlabOutPath& p, const plan::SlabOut& lay, SlabDest dest, const uint8_t* d_all, PinnedPool::Block* blk) {
+    if (dest != SlabDest::Pinned) return SX_OK;
+    *blk = ctx->pool->take(lay.bytes + 64);
+    if (!blk->p) { ctx->set_err("hipHostMalloc failed"); return SX_E_NOMEM; }
+    if (p.async_copy) {   // on the copy stream: the next slab's kernels run meanwhile
+        if (p.leaves_copy_running) ctx->slab_copy_pending = true;   // (from here on the block must not go back to the pool before slab_copy_drain)
+        HIP_TRY(ctx, hipEventRecord(p.written, p.stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->merge_copy_stream, p.written, 0));
+        HIP_TRY(ctx, hipMemcpyAsync(blk->p, d_all, lay.bytes, hipMemcpyDeviceToHost, ctx->merge_copy_stream));
+        HIP_TRY(ctx, hipEventRecord(p.copied, ctx->merge_copy_stream));
+    } else {
+        // (experiments, SX_REPLAY_COPY_WGS=n: the copy as a kernel of n workgroups instead of the runtime's blit, which slows every
+        // kernel next to it — here: the last Mission's scan launch, DESIGN.md section 2 "Schedule")
+        if (p.copy_wgs > 0 && lay.bytes >= (1u << 20)) HIP_TRY(ctx, launch_copy_bytes(blk->p, d_all, lay.bytes, (uint32_t)p.copy_wgs, p.stream, ctx->sw.merge_copy_threads, ctx->sw.merge_copy_nt != 0));
+        else HIP_TRY(ctx, hipMemcpyAsync(blk->p, d_all, lay.bytes, hipMemcpyDeviceToHost, p.stream));
+    }
+    return SX_OK;
+}
+
+int slab_out_settle(sx_ctx* ctx, const SlabOutPath& p, const plan::SlabOut& lay) {
+    if (!p.async_copy || lay.nfh) HIP_TRY(ctx, hipStreamSynchronize(p.stream));
+    return SX_OK;
+}
+
+void slab_out_describe(const sx_ctx* ctx, const SlabOutPath& p, const plan::SlabOut& lay, SlabDest dest, const PinnedPool::Block& blk,
+                       const uint8_t* d_all, MissionFindings* seg) {
+    seg->ext_nf = lay.findings(); seg->ext_na = lay.strings();
+    if (dest == SlabDest::Pinned) { seg->ext = blk; seg->dev_copy = p.async_copy ? nullptr : d_all; return; }
+    seg->dev_only = true; seg->dev_copy = d_all;
+    if (dest == SlabDest::Keep) keep_on_device(*seg, ctx);
+}
+
 // Stage B of one mission on the device (sx_replay_dev.hip) + the little the host keeps:
 // the chunk's strict entry region, regions the device gave back, the exact exit state.
 // One slab = the runs [i0, i1) of the list (all of them unless the mission is replayed in slabs, see device_replay_mission):
@@ -33,11 +91,7 @@ bool device_replay_wanted(const sx_ctx* ctx, const ReplayJob& job, size_t k, siz
 struct Slab {
     size_t i0 = 0, i1 = 0;
     bool first = true, last = true;   // first: the host's entry part belongs to it; last: the exit state
-    int out_slot = 5;                 // d_rp[] index of the output buffer (two in turn)
-    bool async_copy = false;          // leave the copy to the host running (the caller waits for `copied`)
-    hipEvent_t reuse_after = nullptr; // the output buffer is read by a copy until this event
-    hipEvent_t copied = nullptr;
-    hipEvent_t written = nullptr;     // async_copy: pass 2 is done (recorded on stream_b, the copy stream waits for it)
+    SlabOutPath out;                  // its output buffer (two in turn), and whether the copy to the host is left running
     // one of several Missions: what this slab may write at most — from there on the Mission's output could reach the deferral
     // threshold, which only the whole-list path knows (SX_RETRY_WHOLE); 0: no bound
     uint64_t out_budget = 0;
@@ -51,170 +105,201 @@ struct SlabCarry {                    // from slab to slab: where the replay sta
     bool last_is_entry = false, any = false;
 };
 constexpr int SX_RETRY_WHOLE = 1000;  // (internal) a slab met something only the whole-list path handles
+constexpr size_t kEdgeRuns = 8192;    // the part of a list the host may read without the whole copy: [0, kEdgeRuns) and [n - kEdgeRuns, n)
 
-static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& job, const RunList& runs, const Slab& sl,
-                              SlabCarry& carry, MissionFindings* out, uint64_t* end_pos, uint64_t defer_min_bytes) {
-    const Mission& m = ctx->missions[k];
-    MissionDev& d = ctx->dev[k];
-    const size_t n_all = runs.size();
-    const size_t n = sl.i1 - sl.i0;   // the runs this slab's kernels visit (lookups may go on to the list's end)
-    const bool slabbed = !(sl.first && sl.last);
-    const size_t W = m.window;
-    const double t0 = now_ms();
-
-    // ---- pass 1 on the device: every region's extent and output size; then (still on the
-    // device) which regions stand and where each writes.  The host keeps its own version of
-    // that step for buffers with regions the device gave back (kRegionTooLong).
+// One slab's replay: what device_replay_slab's steps hand on to each other.
+struct SlabReplay {
+    sx_ctx* ctx; const size_t k; ByteView& view; const ReplayJob& job; const RunList& runs; const Slab& sl; MissionFindings* out;
+    const Mission& m; MissionDev& d;
+    const size_t n_all, n, W;         // n: the runs this slab's kernels visit (lookups may go on to the list's end)
+    const bool slabbed;
+    // pass 1
     ReplayParams P{};
-    bool fast_pass = false;
-    bool dev_stitch = n > 0 && !ctx->sw.host_stitch;
-    uint64_t* h_tot = nullptr;
-    ReplayRegionOut* ro = nullptr;
-    {
-        // (the regions' records only travel to the host when it decides what stands: 24 bytes per run, 6 GB for C5's floods)
-        int rc = ensure_pinned2(ctx, (dev_stitch ? 0 : n * sizeof(ReplayRegionOut)) + 512);
-        if (rc != SX_OK) return rc;
-        h_tot = (uint64_t*)ctx->h_pin2;   // kTotCount totals; words 32, 33: the fast pre-pass' statistics
-        ro = (ReplayRegionOut*)(ctx->h_pin2 + 384);
-    }
-    if (n) {
-        int rc = ensure_rp(ctx, d, 0, n * sizeof(sx_run)); if (rc) return rc;
-        rc = ensure_rp(ctx, d, 1, n * sizeof(ReplayRegionOut)); if (rc) return rc;
-        rc = ensure_rp(ctx, d, 2, n * 8); if (rc) return rc;
-        rc = ensure_rp(ctx, d, 3, (n + 1) * 8); if (rc) return rc;
-        rc = ensure_rp(ctx, d, 4, (n + 1) * 8); if (rc) return rc;
-        rc = ensure_rp(ctx, d, 6, stitch_blocks_bytes(n, ctx->sw.stitch_block)); if (rc) return rc;
-        rc = ensure_rp(ctx, d, 7, kTotCount * 8); if (rc) return rc;
-        rc = ensure_scratch(ctx, stitch_scratch_bytes(n)); if (rc) return rc;
-        if (!runs.on_device)   // (never slabbed)
-            HIP_TRY(ctx, hipMemcpyAsync(d.d_rp[0], runs.data(), n * sizeof(sx_run), hipMemcpyHostToDevice, d.stream_b));
-        P.data = job.d_bytes; P.len = job.len; P.runs = (runs.on_device ? runs.dev_ptr : (const sx_run*)d.d_rp[0]) + sl.i0; P.n_runs = n;
-        P.n_look = n_all - sl.i0;
-        P.lo = job.lo[k]; P.hi = job.hi; P.consumed0 = job.consumed0[k]; P.stream0 = job.stream0[k];
-        P.slice_base = job.slice_base; P.encoding = m.c.encoding; P.table = d.d_table;
-        P.chars_min_nb = m.c.chars_min_nb; P.same_block = m.c.require_same_unicode_block; P.q = (uint32_t)m.q;
-        P.W = (uint32_t)W; P.long_run = m.long_run; P.skip = ctx->sw.no_replay_skip ? 0u : 1u; P.grep_char = m.c.grep_char; P.mission_id = m.c.mission_id;
-        P.file_id = job.file_id; P.af_lo = m.c.af_lo; P.af_hi = m.c.af_hi; P.ubf = m.c.ubf;
-        P.max_windows = kMaxRegionWindowsDefault;
-        P.entry_skip = m.buf_entry_skip;
-        P.grid_flags = nullptr; P.grid_sub = 0;
-        // (not for gb18030 / GBK — ADVICE round 5: the scan kernel publishes the hang-over of the TWO-byte grammar; a four-byte token that
-        //  straddles a sub-chunk start followed by lead / digit bytes only would start the walk two bytes off and never resynchronise)
-        if (d.grid_of_scan && d.grid_data == job.d_bytes && d.grid_len == job.len && !ctx->sw.no_grid_bound && !enc_is_gb(m.c.encoding)) { P.grid_flags = d.grid_of_scan; P.grid_sub = d.grid_sub; }
-        if (ctx->sw.max_region_windows) P.max_windows = ctx->sw.max_region_windows;
-        // pass-1 output cache: one arena for all replaying regions (slot = arena / their number, on the device)
-        if (dev_stitch && !ctx->sw.no_replay_cache) {
-            // the arena is at most 1 KiB per run; 8 GiB of the 288 GB, and for a flood of runs (a Mission with hundreds of
-            // millions of them: slots of the minimum size, 160 bytes, for as many regions as possible — a region without slot
-            // is replayed twice) up to a third of what is free, at most 40 GiB
-            uint64_t budget = 8192ull << 20;
-            if ((uint64_t)n * 160 > budget) {
-                size_t fr = 0, tot = 0;
-                if (hipMemGetInfo(&fr, &tot) == hipSuccess)
-                    budget = std::max(budget, std::min<uint64_t>(40960ull << 20, ((uint64_t)fr + ctx->d_cache_cap) / 3));
-            }
-            if (ctx->sw.replay_cache_mib >= 0) budget = (uint64_t)ctx->sw.replay_cache_mib << 20;
-            uint64_t arena = std::max<uint64_t>(4096, std::min<uint64_t>(budget, (uint64_t)n * 1024));
-            const uint64_t lists = (uint64_t)(3 * n + 8) * 4 + 512;   // slot_of, n_heads, head_list; (round 5) n_hard, hard_list
-            rc = ensure_cache(ctx, arena + lists);
-            while (rc != SX_OK && arena > (64ull << 20)) {   // the device is short of memory: a smaller arena (more regions are replayed twice)
-                (void)hipGetLastError();
-                arena /= 2;
-                rc = ensure_cache(ctx, arena + lists);
-            }
-            if (rc) return rc;
-            rc = ensure_scratch(ctx, std::max(stitch_scratch_bytes(n), replay_heads_scratch_bytes(n))); if (rc) return rc;
-            uint8_t* base = ctx->d_cache;
-            P.cache_arena = base; P.arena_bytes = arena & ~255ull;
-            uint32_t* slot_of = (uint32_t*)(base + ((arena + 255) & ~255ull));
-            P.slot_of = slot_of; P.n_heads = slot_of + n + 1; P.head_list = slot_of + n + 2;
-            HIP_TRY(ctx, launch_replay_heads(P, slot_of, slot_of + n + 1, slot_of + n + 2, (ReplayRegionOut*)d.d_rp[1], ctx->d_scratch,
-                                             ctx->d_scratch_cap, d.stream_b));
-            // (round 5) the fast pre-pass settles the regions that are one run inside one window; the general kernel gets the rest
-            P.n_hard = slot_of + 2 * n + 4; P.hard_list = slot_of + 2 * n + 5;
-            if (replay_fast_covers(P) && ctx->sw.fast_replay) {
-                HIP_TRY(ctx, hipMemsetAsync(P.n_hard, 0, 4, d.stream_b));
-                HIP_TRY(ctx, launch_replay_fast(P, (ReplayRegionOut*)d.d_rp[1], d.stream_b));
-                fast_pass = true;
-            } else { P.n_hard = nullptr; P.hard_list = nullptr; }
-        }
-        HIP_TRY(ctx, launch_replay_count(P, (ReplayRegionOut*)d.d_rp[1], d.stream_b, ctx->sw.count_waves));
-        if (fast_pass) {   // (statistics: how many regions each pass took; read with the totals below)
-            h_tot[32] = 0; h_tot[33] = 0;
-            { int rb = read_back_async(ctx, d.stream_b, h_tot + 32, P.n_hard, 4); if (rb == SX_OK) rb = read_back_async(ctx, d.stream_b, h_tot + 33, P.n_heads, 4); if (rb != SX_OK) return rb; }
-        }
-        // The host's copy of a device-joined run list: its share of this replay (the buffer's entry region, the exit state)
-        // reads only the list's two ends — a large list is not copied whole (68 MB for the headline's 2.8 M runs, 1.2 ms on
-        // the critical path when nothing else runs); the rest follows on demand (regions the device gives back).
-        if (runs.size() * sizeof(sx_run) <= (4u << 20)) HIP_TRY(ctx, runs.start_copy());
-        if (dev_stitch) {
-            HIP_TRY(ctx, hipMemsetAsync(d.d_rp[7], 0, kTotCount * 8, d.stream_b));
-            HIP_TRY(ctx, launch_stitch_blocks(P, (const ReplayRegionOut*)d.d_rp[1], (uint8_t*)d.d_rp[2], d.d_rp[6],
-                                              (uint64_t*)d.d_rp[7], d.stream_b, ctx->sw.stitch_block));
-        } else
-            HIP_TRY(ctx, hipMemcpyAsync(ro, d.d_rp[1], n * sizeof(ReplayRegionOut), hipMemcpyDeviceToHost, d.stream_b));
-    }
-
-    // ---- meanwhile on the host: the strict entry region (exact carried state), if any
-    constexpr size_t kEdgeRuns = 8192;
-    if (dev_stitch) HIP_TRY(ctx, runs.fetch_edges(kEdgeRuns)); else HIP_TRY(ctx, runs.wait());   // (the host's stitch walks the whole list)
-    // the part of the list the host may read without the whole copy: [0, kEdgeRuns) and [n - kEdgeRuns, n)
-    const size_t head_n = runs.full() ? n_all : kEdgeRuns;
+    uint64_t* h_tot = nullptr;        // kTotCount totals; words 32, 33: the fast pre-pass' statistics
+    ReplayRegionOut* ro = nullptr;    // the regions' records, when the host decides what stands
+    bool dev_stitch, fast_pass = false;
+    // where the replay stands
+    uint64_t E, last_start;           // last_start: start of the last region of any kind (for the exit state)
+    bool last_is_entry;
     std::deque<ReplayPart> host_parts;
     struct Seg { int host_part; size_t v0, v1; };  // host_part >= 0, or device regions [v0, v1) of `valid`
     std::vector<Seg> segs;
-    uint64_t E = std::min(job.lo[k], job.hi);
-    uint64_t last_start = carry.any ? carry.last_start : E;   // start of the last region of any kind (for the exit state)
-    bool last_is_entry = carry.any ? carry.last_is_entry : false;
-    if (job.entry_exact[k]) {
-        // The chunk's first window belongs to the host: only it has the exact carried state
-        // (leftover, cut flag, and the decoder's pending bytes, which cannot be re-derived here).
-        host_parts.emplace_back();
-        replay_part(m, ctx->states[k], job.consumed0[k], job.stream0[k], view, job.len, job.file_id, false, runs.data(), head_n,
-                    job.lo[k], job.lo[k] + 1, true, &host_parts.back());
-        if (head_n < n_all && host_parts.back().end_pos >= runs[head_n - 1].start) {   // it ran into what was not copied: the whole list
-            HIP_TRY(ctx, runs.wait());
-            host_parts.pop_back();
-            host_parts.emplace_back();
-            replay_part(m, ctx->states[k], job.consumed0[k], job.stream0[k], view, job.len, job.file_id, false, runs.data(), n_all,
-                        job.lo[k], job.lo[k] + 1, true, &host_parts.back());
+    // what stands
+    std::vector<uint64_t> valid, fbase, abase;
+    uint64_t nf = 0, nb = 0, n_standing = 0;
+    // pass 2
+    plan::SlabOut lay; SlabOutPath path; SlabDest dest = SlabDest::Pinned;
+    PinnedPool::Block blk{};
+    uint8_t* d_all = nullptr;
+    bool entry_only = false;
+    const MissionFindings* hf0 = nullptr;   // the host's entry part, if it is all the host has
+    std::vector<sx_finding> entry_f;
+
+    SlabReplay(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& job, const RunList& runs, const Slab& sl, const SlabCarry& carry, MissionFindings* out)
+        : ctx(ctx), k(k), view(view), job(job), runs(runs), sl(sl), out(out), m(ctx->missions[k]), d(ctx->dev[k]), n_all(runs.size()),
+          n(sl.i1 - sl.i0), W(m.window), slabbed(!(sl.first && sl.last)), dev_stitch(n > 0 && !ctx->sw.host_stitch),
+          E(std::min(job.lo[k], job.hi)), last_start(carry.any ? carry.last_start : E), last_is_entry(carry.any ? carry.last_is_entry : false) {}
+
+    // the steps, in device_replay_slab's order
+    int pinned_totals(bool with_regions), queue_pass1(), host_entry_part(), finish_stitch(), retry_or_give_back(), what_stands();
+    int pass2_and_deliver(uint64_t defer_min_bytes), exit_state(uint64_t* end_pos);
+    void splice();
+};
+
+// (the regions' records only travel to the host when it decides what stands: 24 bytes per run, 6 GB for C5's floods)
+int SlabReplay::pinned_totals(bool with_regions) {
+    const int rc = ensure_pinned2(ctx, (with_regions ? n * sizeof(ReplayRegionOut) : 0) + 512);
+    if (rc != SX_OK) return rc;
+    h_tot = (uint64_t*)ctx->h_pin2;
+    ro = (ReplayRegionOut*)(ctx->h_pin2 + 384);
+    return SX_OK;
+}
+
+// ---- pass 1 on the device: every region's extent and output size; then (still on the
+// device) which regions stand and where each writes.  The host keeps its own version of
+// that step for buffers with regions the device gave back (kRegionTooLong).
+int SlabReplay::queue_pass1() {
+    int rc = pinned_totals(!dev_stitch);
+    if (rc != SX_OK) return rc;
+    if (!n) return SX_OK;
+    rc = ensure_rp(ctx, d, kRpRuns, n * sizeof(sx_run)); if (rc) return rc;
+    rc = ensure_rp(ctx, d, kRpRegionOut, n * sizeof(ReplayRegionOut)); if (rc) return rc;
+    rc = ensure_rp(ctx, d, kRpIdx, n * 8); if (rc) return rc;
+    rc = ensure_rp(ctx, d, kRpFbase, (n + 1) * 8); if (rc) return rc;
+    rc = ensure_rp(ctx, d, kRpAbase, (n + 1) * 8); if (rc) return rc;
+    rc = ensure_rp(ctx, d, kRpStitchBlocks, stitch_blocks_bytes(n, ctx->sw.stitch_block)); if (rc) return rc;
+    rc = ensure_rp(ctx, d, kRpTotals, kTotCount * 8); if (rc) return rc;
+    rc = ensure_scratch(ctx, stitch_scratch_bytes(n)); if (rc) return rc;
+    ReplayRegionOut* d_ro = (ReplayRegionOut*)d.d_rp[kRpRegionOut];
+    if (!runs.on_device)   // (never slabbed)
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_rp[kRpRuns], runs.data(), n * sizeof(sx_run), hipMemcpyHostToDevice, d.stream_b));
+    P.data = job.d_bytes; P.len = job.len; P.runs = (runs.on_device ? runs.dev_ptr : (const sx_run*)d.d_rp[kRpRuns]) + sl.i0; P.n_runs = n;
+    P.n_look = n_all - sl.i0;
+    P.lo = job.lo[k]; P.hi = job.hi; P.consumed0 = job.consumed0[k]; P.stream0 = job.stream0[k];
+    P.slice_base = job.slice_base; P.encoding = m.c.encoding; P.table = d.d_table;
+    P.chars_min_nb = m.c.chars_min_nb; P.same_block = m.c.require_same_unicode_block; P.q = (uint32_t)m.q;
+    P.W = (uint32_t)W; P.long_run = m.long_run; P.skip = ctx->sw.no_replay_skip ? 0u : 1u; P.grep_char = m.c.grep_char; P.mission_id = m.c.mission_id;
+    P.file_id = job.file_id; P.af_lo = m.c.af_lo; P.af_hi = m.c.af_hi; P.ubf = m.c.ubf;
+    P.max_windows = kMaxRegionWindowsDefault;
+    P.entry_skip = m.buf_entry_skip;
+    P.grid_flags = nullptr; P.grid_sub = 0;
+    // (not for gb18030 / GBK — ADVICE round 5: the scan kernel publishes the hang-over of the TWO-byte grammar; a four-byte token that
+    //  straddles a sub-chunk start followed by lead / digit bytes only would start the walk two bytes off and never resynchronise)
+    if (d.grid_of_scan && d.grid_data == job.d_bytes && d.grid_len == job.len && !ctx->sw.no_grid_bound && !enc_is_gb(m.c.encoding)) { P.grid_flags = d.grid_of_scan; P.grid_sub = d.grid_sub; }
+    if (ctx->sw.max_region_windows) P.max_windows = ctx->sw.max_region_windows;
+    // pass-1 output cache: one arena for all replaying regions (slot = arena / their number, on the device)
+    if (dev_stitch && !ctx->sw.no_replay_cache) {
+        // (plan::cache_arena_bytes: a flood of runs gets slots of the minimum size for as many regions as possible — a region
+        // without slot is replayed twice)
+        uint64_t free_plus_held = 0;
+        if (plan::cache_arena_asks_free(n)) {
+            size_t fr = 0, tot = 0;
+            if (hipMemGetInfo(&fr, &tot) == hipSuccess) free_plus_held = (uint64_t)fr + ctx->d_cache_cap;
         }
-        if (host_parts.back().regions.empty()) host_parts.pop_back();
-        else { segs.push_back({ (int)host_parts.size() - 1, 0, 0 }); last_is_entry = true; E = std::max(E, host_parts.back().end_pos); }
-        E = std::max(E, job.lo[k] + 1);
+        uint64_t arena = plan::cache_arena_bytes(n, free_plus_held, ctx->sw.replay_cache_mib);
+        const uint64_t lists = (uint64_t)(3 * n + 8) * 4 + 512;   // slot_of, n_heads, head_list; (round 5) n_hard, hard_list
+        rc = ensure_cache(ctx, arena + lists);
+        while (rc != SX_OK && arena > (64ull << 20)) {   // the device is short of memory: a smaller arena (more regions are replayed twice)
+            (void)hipGetLastError();
+            arena /= 2;
+            rc = ensure_cache(ctx, arena + lists);
+        }
+        if (rc) return rc;
+        rc = ensure_scratch(ctx, std::max(stitch_scratch_bytes(n), replay_heads_scratch_bytes(n))); if (rc) return rc;
+        uint8_t* base = ctx->d_cache;
+        P.cache_arena = base; P.arena_bytes = arena & ~255ull;
+        uint32_t* slot_of = (uint32_t*)(base + plan::up256(arena));
+        P.slot_of = slot_of; P.n_heads = slot_of + n + 1; P.head_list = slot_of + n + 2;
+        HIP_TRY(ctx, launch_replay_heads(P, slot_of, slot_of + n + 1, slot_of + n + 2, d_ro, ctx->d_scratch, ctx->d_scratch_cap, d.stream_b));
+        // (round 5) the fast pre-pass settles the regions that are one run inside one window; the general kernel gets the rest
+        P.n_hard = slot_of + 2 * n + 4; P.hard_list = slot_of + 2 * n + 5;
+        if (replay_fast_covers(P) && ctx->sw.fast_replay) {
+            HIP_TRY(ctx, hipMemsetAsync(P.n_hard, 0, 4, d.stream_b));
+            HIP_TRY(ctx, launch_replay_fast(P, d_ro, d.stream_b));
+            fast_pass = true;
+        } else { P.n_hard = nullptr; P.hard_list = nullptr; }
     }
+    HIP_TRY(ctx, launch_replay_count(P, d_ro, d.stream_b, ctx->sw.count_waves));
+    if (fast_pass) {   // (statistics: how many regions each pass took; read with the totals below)
+        h_tot[32] = 0; h_tot[33] = 0;
+        rc = read_back_async(ctx, d.stream_b, h_tot + 32, P.n_hard, 4);
+        if (rc == SX_OK) rc = read_back_async(ctx, d.stream_b, h_tot + 33, P.n_heads, 4);
+        if (rc != SX_OK) return rc;
+    }
+    // The host's copy of a device-joined run list: its share of this replay (the buffer's entry region, the exit state)
+    // reads only the list's two ends — a large list is not copied whole (68 MB for the headline's 2.8 M runs, 1.2 ms on
+    // the critical path when nothing else runs); the rest follows on demand (regions the device gives back).
+    if (runs.size() * sizeof(sx_run) <= (4u << 20)) HIP_TRY(ctx, runs.start_copy());
     if (dev_stitch) {
-        HIP_TRY(ctx, launch_stitch_finish(P, (const ReplayRegionOut*)d.d_rp[1], (uint8_t*)d.d_rp[2], d.d_rp[6], E,
-                                          (uint64_t*)d.d_rp[3], (uint64_t*)d.d_rp[4], (uint64_t*)d.d_rp[7], ctx->d_scratch,
+        HIP_TRY(ctx, hipMemsetAsync(d.d_rp[kRpTotals], 0, kTotCount * 8, d.stream_b));
+        HIP_TRY(ctx, launch_stitch_blocks(P, d_ro, (uint8_t*)d.d_rp[kRpIdx], d.d_rp[kRpStitchBlocks], (uint64_t*)d.d_rp[kRpTotals], d.stream_b, ctx->sw.stitch_block));
+    } else
+        HIP_TRY(ctx, hipMemcpyAsync(ro, d_ro, n * sizeof(ReplayRegionOut), hipMemcpyDeviceToHost, d.stream_b));
+    return SX_OK;
+}
+
+// ---- meanwhile on the host: the strict entry region (exact carried state), if any
+int SlabReplay::host_entry_part() {
+    if (dev_stitch) HIP_TRY(ctx, runs.fetch_edges(kEdgeRuns)); else HIP_TRY(ctx, runs.wait());   // (the host's stitch walks the whole list)
+    if (!job.entry_exact[k]) return SX_OK;
+    const size_t head_n = runs.full() ? n_all : kEdgeRuns;
+    // The chunk's first window belongs to the host: only it has the exact carried state
+    // (leftover, cut flag, and the decoder's pending bytes, which cannot be re-derived here).
+    host_parts.emplace_back();
+    replay_part(m, ctx->states[k], job.consumed0[k], job.stream0[k], view, job.len, job.file_id, false, runs.data(), head_n,
+                job.lo[k], job.lo[k] + 1, true, &host_parts.back());
+    if (head_n < n_all && host_parts.back().end_pos >= runs[head_n - 1].start) {   // it ran into what was not copied: the whole list
+        HIP_TRY(ctx, runs.wait());
+        host_parts.pop_back();
+        host_parts.emplace_back();
+        replay_part(m, ctx->states[k], job.consumed0[k], job.stream0[k], view, job.len, job.file_id, false, runs.data(), n_all,
+                    job.lo[k], job.lo[k] + 1, true, &host_parts.back());
+    }
+    if (host_parts.back().regions.empty()) host_parts.pop_back();
+    else { segs.push_back({ (int)host_parts.size() - 1, 0, 0 }); last_is_entry = true; E = std::max(E, host_parts.back().end_pos); }
+    E = std::max(E, job.lo[k] + 1);
+    return SX_OK;
+}
+
+// the stitch from where the entry part ended, the totals' way back, and the one wait of pass 1
+int SlabReplay::finish_stitch() {
+    if (dev_stitch) {
+        HIP_TRY(ctx, launch_stitch_finish(P, (const ReplayRegionOut*)d.d_rp[kRpRegionOut], (uint8_t*)d.d_rp[kRpIdx], d.d_rp[kRpStitchBlocks], E,
+                                          (uint64_t*)d.d_rp[kRpFbase], (uint64_t*)d.d_rp[kRpAbase], (uint64_t*)d.d_rp[kRpTotals], ctx->d_scratch,
                                           ctx->d_scratch_cap, d.stream_b, ctx->sw.stitch_block));
-        { const int rb = read_back_async(ctx, d.stream_b, h_tot, d.d_rp[7], kTotCount * 8); if (rb != SX_OK) return rb; }
+        { const int rb = read_back_async(ctx, d.stream_b, h_tot, d.d_rp[kRpTotals], kTotCount * 8); if (rb != SX_OK) return rb; }
     }
     SX_TL("  replay: pass 1 + stitch queued, host entry part done");
     if (n) HIP_TRY(ctx, hipStreamSynchronize(d.stream_b));
     SX_TL("  replay: pass 1 + stitch done");
+    return SX_OK;
+}
+
+// SX_RETRY_WHOLE: a slab with regions for the host, or one that would take the Mission's output to the deferral threshold.
+// Regions for the host in a whole list: it also decides what stands.
+int SlabReplay::retry_or_give_back() {
     if (dev_stitch && h_tot[kTotTooLong] && slabbed) return SX_RETRY_WHOLE;
     if (dev_stitch && slabbed && sl.out_budget && h_tot[kTotFindings] * sizeof(sx_finding) + h_tot[kTotBytes] >= sl.out_budget) return SX_RETRY_WHOLE;
-    if (dev_stitch && h_tot[kTotTooLong]) {  // regions for the host: it also decides what stands
+    if (dev_stitch && h_tot[kTotTooLong]) {
         dev_stitch = false;
         HIP_TRY(ctx, runs.wait());
         const uint64_t keep32 = h_tot[32], keep33 = h_tot[33];
-        int rc = ensure_pinned2(ctx, n * sizeof(ReplayRegionOut) + 512);
+        const int rc = pinned_totals(true);   // (the totals' values are not read again)
         if (rc != SX_OK) return rc;
-        h_tot = (uint64_t*)ctx->h_pin2;   // (its values are not read again)
         h_tot[32] = keep32; h_tot[33] = keep33;
-        ro = (ReplayRegionOut*)(ctx->h_pin2 + 384);
-        HIP_TRY(ctx, hipMemcpyAsync(ro, d.d_rp[1], n * sizeof(ReplayRegionOut), hipMemcpyDeviceToHost, d.stream_b));
+        HIP_TRY(ctx, hipMemcpyAsync(ro, d.d_rp[kRpRegionOut], n * sizeof(ReplayRegionOut), hipMemcpyDeviceToHost, d.stream_b));
         HIP_TRY(ctx, hipStreamSynchronize(d.stream_b));
     }
-    const double t1 = now_ms();
+    return SX_OK;
+}
+
+// the device's totals, or the host's walk: a region is void if an earlier one ran over its start
+int SlabReplay::what_stands() {
     if (fast_pass && n) {
         std::lock_guard<std::mutex> g(ctx->mu);
         ctx->stats.fast_regions += (uint32_t)h_tot[33] - (uint32_t)h_tot[32];
         ctx->stats.general_regions += (uint32_t)h_tot[32];
     }
-
-    std::vector<uint64_t> valid, fbase, abase;
-    uint64_t nf = 0, nb = 0, n_standing = 0;
     if (dev_stitch) {
         nf = h_tot[kTotFindings]; nb = h_tot[kTotBytes]; n_standing = h_tot[kTotStanding];
         out->replay_bytes += h_tot[kTotReplayBytes];
@@ -224,7 +309,6 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
             last_is_entry = false;
         }
     } else {
-        // ---- which regions stand: a region is void if an earlier one ran over its start
         valid.reserve(n); fbase.reserve(n + 1); abase.reserve(n + 1);
         for (size_t i = 0; i < n; i++) {
             const uint32_t st = ro[i].status;
@@ -251,122 +335,92 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
         n_standing = valid.size();
         for (uint64_t v : valid) out->replay_bytes += ro[v].end - win_start_h(runs[v].start, W);
     }
-    if (nb > 0xFFFFFFFFull) { ctx->err = "more than 4 GiB of strings in one chunk"; return SX_E_NOMEM; }
-    const double t2 = now_ms();
+    return slab_strings_limit(ctx, nb);
+}
 
-    // ---- pass 2: the standing regions write findings and strings, in order; the D2H lands in a
-    // pinned block that becomes the result's storage (no copy).  The host's entry part (the chunk's first
-    // region, replayed from the exact carried state) goes in front of it in the same block: the device writes
-    // its str_off already shifted by that part's strings.  Only regions the device gave back to the host
-    // (somewhere in the middle) need the finding-by-finding splice.
-    PinnedPool::Block blk{};
-    bool deferred = false, keep_dev = false;
-    std::vector<sx_finding> entry_f;
-    const bool entry_only = dev_stitch && host_parts.size() == 1 && true;
-    const MissionFindings* hf0 = entry_only ? &host_parts[0].findings : nullptr;
-    const uint64_t nfh = hf0 ? hf0->v.size() : 0, nbh = hf0 ? hf0->arena.size() : 0;
-    if (nb + nbh > 0xFFFFFFFFull) { ctx->err = "more than 4 GiB of strings in one chunk"; return SX_E_NOMEM; }
-    if (n_standing) {
-        // the device buffer has the block's layout: [host findings][device findings][host strings][device strings]
-        const uint64_t out_bytes = (nfh + nf) * sizeof(sx_finding) + nbh + nb;
-        if (sl.reuse_after) {   // a copy of an earlier slab may still read this buffer
-            if (d.d_rp_cap[sl.out_slot] < out_bytes + 64) HIP_TRY(ctx, hipEventSynchronize(sl.reuse_after));
-            else HIP_TRY(ctx, hipStreamWaitEvent(d.stream_b, sl.reuse_after, 0));
+// ---- pass 2: the standing regions write findings and strings, in order; the D2H lands in a
+// pinned block that becomes the result's storage (no copy).  The host's entry part (the chunk's first
+// region, replayed from the exact carried state) goes in front of it in the same block: the device writes
+// its str_off already shifted by that part's strings.  Only regions the device gave back to the host
+// (somewhere in the middle) need the finding-by-finding splice.
+int SlabReplay::pass2_and_deliver(uint64_t defer_min_bytes) {
+    entry_only = dev_stitch && host_parts.size() == 1;
+    hf0 = entry_only ? &host_parts[0].findings : nullptr;
+    lay = plan::slab_out_layout(hf0 ? hf0->v.size() : 0, nf, hf0 ? hf0->arena.size() : 0, nb, sizeof(sx_finding));
+    int rc = slab_strings_limit(ctx, lay.strings()); if (rc) return rc;
+    if (!n_standing) return SX_OK;
+    path = sl.out; path.stream = d.stream_b; path.copy_wgs = ctx->sw.replay_copy_wgs;
+    rc = slab_out_reserve(ctx, d, path, lay, &d_all); if (rc) return rc;
+    sx_finding* d_f = (sx_finding*)(d_all + lay.dev_f);
+    uint8_t* d_a = d_all + lay.dev_s;
+    if (dev_stitch) {
+        P.str_off_base = (uint32_t)lay.nbh;
+        HIP_TRY(ctx, launch_replay_write_flagged(P, (const ReplayRegionOut*)d.d_rp[kRpRegionOut], (const uint8_t*)d.d_rp[kRpIdx],
+                                                 (const uint64_t*)d.d_rp[kRpFbase], (const uint64_t*)d.d_rp[kRpAbase], d_f, d_a,
+                                                 (nf * sizeof(sx_finding) + nb) / std::max<uint64_t>(1, n_standing), d.stream_b));
+        if (lay.nfh) {
+            entry_f.assign(hf0->v.begin(), hf0->v.end());
+            for (sx_finding& f : entry_f) f.slice_index += job.slice_base;
+            rc = slab_out_upload_entry(ctx, path, lay, d_all, entry_f.data(), hf0->arena.data()); if (rc) return rc;
         }
-        int rc = ensure_rp(ctx, d, sl.out_slot, out_bytes + 64); if (rc) return rc;
-        uint8_t* d_all = (uint8_t*)d.d_rp[sl.out_slot];
-        sx_finding* d_f = (sx_finding*)d_all + nfh;
-        uint8_t* d_a = d_all + (nfh + nf) * sizeof(sx_finding) + nbh;
-        if (dev_stitch) {
-            P.str_off_base = (uint32_t)nbh;
-            HIP_TRY(ctx, launch_replay_write_flagged(P, (const ReplayRegionOut*)d.d_rp[1], (const uint8_t*)d.d_rp[2],
-                                                     (const uint64_t*)d.d_rp[3], (const uint64_t*)d.d_rp[4], d_f, d_a,
-                                                     (nf * sizeof(sx_finding) + nb) / std::max<uint64_t>(1, n_standing), d.stream_b));
-            if (nfh) {   // the host's entry part joins it there (a few findings): the missions can be interleaved on the device
-                entry_f.assign(hf0->v.begin(), hf0->v.end());
-                for (sx_finding& f : entry_f) f.slice_index += job.slice_base;
-                HIP_TRY(ctx, hipMemcpyAsync(d_all, entry_f.data(), nfh * sizeof(sx_finding), hipMemcpyHostToDevice, d.stream_b));
-                if (nbh) HIP_TRY(ctx, hipMemcpyAsync(d_all + (nfh + nf) * sizeof(sx_finding), hf0->arena.data(), nbh, hipMemcpyHostToDevice, d.stream_b));
-            }
-        } else {
-            const size_t nv = valid.size();
-            HIP_TRY(ctx, hipMemcpyAsync(d.d_rp[2], valid.data(), nv * 8, hipMemcpyHostToDevice, d.stream_b));
-            HIP_TRY(ctx, hipMemcpyAsync(d.d_rp[3], fbase.data(), (nv + 1) * 8, hipMemcpyHostToDevice, d.stream_b));
-            HIP_TRY(ctx, hipMemcpyAsync(d.d_rp[4], abase.data(), (nv + 1) * 8, hipMemcpyHostToDevice, d.stream_b));
-            HIP_TRY(ctx, launch_replay_write(P, (const uint64_t*)d.d_rp[2], (const uint64_t*)d.d_rp[3],
-                                             (const uint64_t*)d.d_rp[4], nv, d_f, d_a, d.stream_b));
-        }
-        // a large output of one of several missions: the caller interleaves the missions on the device first, one copy instead of two
-        deferred = defer_min_bytes && nf * sizeof(sx_finding) + nb >= defer_min_bytes && dev_stitch && (host_parts.empty() || entry_only);
-        // SX_OPT_RESULT_ON_DEVICE (round 5): one Mission, the whole buffer in this one slab, nothing the host has to splice in — it stays here
-        keep_dev = (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) && ctx->missions.size() == 1 && defer_min_bytes == 0 && job.commit_state && !ctx->sharded_call &&
-                   ctx->single_piece && sl.first && sl.last && !sl.async_copy && dev_stitch && (host_parts.empty() || entry_only);
-        deferred = deferred || keep_dev;
-        if (!deferred) {
-            blk = ctx->pool->take(out_bytes + 64);
-            if (!blk.p) { ctx->err = "hipHostMalloc failed"; return SX_E_NOMEM; }
-            if (sl.async_copy) {   // on the copy stream: the next slab's kernels run meanwhile
-                ctx->slab_copy_pending = true;   // (from here on the block must not go back to the pool before slab_copy_drain)
-                HIP_TRY(ctx, hipEventRecord(sl.written, d.stream_b));
-                HIP_TRY(ctx, hipStreamWaitEvent(ctx->merge_copy_stream, sl.written, 0));
-                HIP_TRY(ctx, hipMemcpyAsync(blk.p, d_all, out_bytes, hipMemcpyDeviceToHost, ctx->merge_copy_stream));
-                HIP_TRY(ctx, hipEventRecord(sl.copied, ctx->merge_copy_stream));
-            } else {
-                // (experiments, SX_REPLAY_COPY_WGS=n: the copy as a kernel of n workgroups instead of the runtime's blit, which slows every
-                // kernel next to it — here: the last Mission's scan launch, DESIGN.md section 2 "Schedule")
-                const int wgs = ctx->sw.replay_copy_wgs;
-                if (wgs > 0 && out_bytes >= (1u << 20)) HIP_TRY(ctx, launch_copy_bytes(blk.p, d_all, out_bytes, (uint32_t)wgs, d.stream_b, ctx->sw.merge_copy_threads, ctx->sw.merge_copy_nt != 0));
-                else HIP_TRY(ctx, hipMemcpyAsync(blk.p, d_all, out_bytes, hipMemcpyDeviceToHost, d.stream_b));
-            }
-        }
-        SX_TL("  replay: pass 2 + copy queued (%llu bytes%s)", (unsigned long long)out_bytes, deferred ? ", stays on the device" : "");
-        if (!sl.async_copy || nfh) HIP_TRY(ctx, hipStreamSynchronize(d.stream_b));   // (nfh: the entry part's upload reads host vectors)
-        SX_TL("  replay: pass 2 + copy done");
-    }
-    const double t3 = now_ms();
-
-    // ---- splice (almost always: device findings only, or the entry part in front of them)
-    if (host_parts.empty() || (entry_only && (blk.p || deferred))) {
-        if (deferred) {
-            out->dev_only = true; out->ext_nf = nfh + nf; out->ext_na = nbh + nb; out->dev_copy = d.d_rp[sl.out_slot];
-            if (keep_dev) { out->keep_on_device = true; out->dev_epoch_ref = ctx->dev_epoch; out->dev_epoch = ctx->dev_epoch->load(); }
-        }
-        else if (blk.p) { out->ext = blk; out->ext_nf = nfh + nf; out->ext_na = nbh + nb; out->dev_copy = sl.async_copy ? nullptr : d.d_rp[sl.out_slot]; }
-        if (hf0) out->replay_bytes += hf0->replay_bytes;
     } else {
-        const sx_finding* dev_f = (const sx_finding*)blk.p;
-        const char* dev_a = blk.p ? (const char*)blk.p + nf * sizeof(sx_finding) : nullptr;
-        if (dev_stitch) {  // only the entry part can be here; everything the device wrote follows it
-            fbase.assign({ 0, nf }); abase.assign({ 0, nb });
-            if (n_standing) segs.push_back({ -1, 0, 1 });
-        }
-        for (const Seg& g : segs) {
-            if (g.host_part >= 0) {
-                const MissionFindings& hf = host_parts[(size_t)g.host_part].findings;
-                const uint32_t base = (uint32_t)out->arena.size();
-                out->arena += hf.arena;
-                for (sx_finding f : hf.v) { f.str_off += base; f.slice_index += job.slice_base; out->v.push_back(f); }
-                out->replay_bytes += hf.replay_bytes;
-            } else if (g.v1 > g.v0) {
-                const uint64_t f0 = fbase[g.v0], f1 = fbase[g.v1], a0 = abase[g.v0], a1 = abase[g.v1];
-                const uint32_t base = (uint32_t)out->arena.size();
-                out->arena.append(dev_a + a0, a1 - a0);
-                for (uint64_t j = f0; j < f1; j++) { sx_finding f = dev_f[j]; f.str_off = f.str_off - (uint32_t)a0 + base; out->v.push_back(f); }
-            }
-        }
-        ctx->pool->give(blk);
+        const size_t nv = valid.size();
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_rp[kRpIdx], valid.data(), nv * 8, hipMemcpyHostToDevice, d.stream_b));
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_rp[kRpFbase], fbase.data(), (nv + 1) * 8, hipMemcpyHostToDevice, d.stream_b));
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_rp[kRpAbase], abase.data(), (nv + 1) * 8, hipMemcpyHostToDevice, d.stream_b));
+        HIP_TRY(ctx, launch_replay_write(P, (const uint64_t*)d.d_rp[kRpIdx], (const uint64_t*)d.d_rp[kRpFbase],
+                                         (const uint64_t*)d.d_rp[kRpAbase], nv, d_f, d_a, d.stream_b));
     }
+    const bool nothing_to_splice = dev_stitch && (host_parts.empty() || entry_only);
+    // a large output of one of several missions: the caller interleaves the missions on the device first, one copy instead of two
+    if (defer_min_bytes && nf * sizeof(sx_finding) + nb >= defer_min_bytes && nothing_to_splice) dest = SlabDest::Defer;
+    // SX_OPT_RESULT_ON_DEVICE (round 5): one Mission, the whole buffer in this one slab, nothing the host has to splice in — it stays here
+    if (single_result_stays_on_device(ctx, job, defer_min_bytes) && sl.first && sl.last && !sl.out.async_copy && nothing_to_splice) dest = SlabDest::Keep;
+    rc = slab_out_deliver(ctx, path, lay, dest, d_all, &blk); if (rc) return rc;
+    SX_TL("  replay: pass 2 + copy queued (%llu bytes%s)", (unsigned long long)lay.bytes, dest != SlabDest::Pinned ? ", stays on the device" : "");
+    rc = slab_out_settle(ctx, path, lay); if (rc) return rc;
+    SX_TL("  replay: pass 2 + copy done");
+    return SX_OK;
+}
 
-    // ---- the state handed to the next chunk: replay the last region and the tail once more
-    // on the host, only for its final state (RangeReplay's tail rule makes it exact)
+// ---- splice (almost always: device findings only, or the entry part in front of them)
+void SlabReplay::splice() {
+    const bool on_device = dest != SlabDest::Pinned;
+    if (host_parts.empty() || (entry_only && (blk.p || on_device))) {
+        if (on_device || blk.p) slab_out_describe(ctx, path, lay, dest, blk, d_all, out);
+        if (hf0) out->replay_bytes += hf0->replay_bytes;
+        return;
+    }
+    const sx_finding* dev_f = (const sx_finding*)blk.p;
+    const char* dev_a = blk.p ? (const char*)blk.p + nf * sizeof(sx_finding) : nullptr;
+    if (dev_stitch) {  // only the entry part can be here; everything the device wrote follows it
+        fbase.assign({ 0, nf }); abase.assign({ 0, nb });
+        if (n_standing) segs.push_back({ -1, 0, 1 });
+    }
+    for (const Seg& g : segs) {
+        if (g.host_part >= 0) {
+            const MissionFindings& hf = host_parts[(size_t)g.host_part].findings;
+            const uint32_t base = (uint32_t)out->arena.size();
+            out->arena += hf.arena;
+            for (sx_finding f : hf.v) { f.str_off += base; f.slice_index += job.slice_base; out->v.push_back(f); }
+            out->replay_bytes += hf.replay_bytes;
+        } else if (g.v1 > g.v0) {
+            const uint64_t f0 = fbase[g.v0], f1 = fbase[g.v1], a0 = abase[g.v0], a1 = abase[g.v1];
+            const uint32_t base = (uint32_t)out->arena.size();
+            out->arena.append(dev_a + a0, a1 - a0);
+            for (uint64_t j = f0; j < f1; j++) { sx_finding f = dev_f[j]; f.str_off = f.str_off - (uint32_t)a0 + base; out->v.push_back(f); }
+        }
+    }
+    ctx->pool->give(blk);
+}
+
+// ---- the state handed to the next chunk: replay the last region and the tail once more
+// on the host, only for its final state (RangeReplay's tail rule makes it exact)
+int SlabReplay::exit_state(uint64_t* end_pos) {
     if (job.commit_state) {
-        const uint64_t tail = job.len ? job.len - 1 : 0;
-        uint64_t ts = win_start_h(tail, W);
-        for (int t = 0; t < 3 && ts > 0; t++) ts = win_start_h(ts - 1, W);
         const uint64_t lo0 = slabbed ? sl.lo0 : job.lo[k];
         const bool exact0 = slabbed ? sl.entry_exact0 : job.entry_exact[k] != 0;
-        uint64_t from = last_is_entry ? lo0 : (E > ts ? last_start : ts);
-        if (from < lo0) from = lo0;
+        const uint64_t from = plan::exit_replay_from(job.len, W, lo0, E, last_start, last_is_entry);
         ReplayPart fin;
         const sx_run* fr = runs.data();
         size_t fn = n_all;
@@ -382,11 +436,29 @@ static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const Repla
         E = job.len;
     }
     if (end_pos) *end_pos = std::max(E, std::min(job.hi, job.len));
-    carry.last_start = last_start; carry.last_is_entry = last_is_entry; carry.any = true;
+    return SX_OK;
+}
+
+static int device_replay_slab(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& job, const RunList& runs, const Slab& sl,
+                              SlabCarry& carry, MissionFindings* out, uint64_t* end_pos, uint64_t defer_min_bytes) {
+    const double t0 = now_ms();
+    SlabReplay r(ctx, k, view, job, runs, sl, carry, out);
+    int rc = r.queue_pass1();               if (rc != SX_OK) return rc;
+    rc = r.host_entry_part();               if (rc != SX_OK) return rc;
+    rc = r.finish_stitch();                 if (rc != SX_OK) return rc;
+    rc = r.retry_or_give_back();            if (rc != SX_OK) return rc;
+    const double t1 = now_ms();
+    rc = r.what_stands();                   if (rc != SX_OK) return rc;
+    const double t2 = now_ms();
+    rc = r.pass2_and_deliver(defer_min_bytes); if (rc != SX_OK) return rc;
+    const double t3 = now_ms();
+    r.splice();
+    rc = r.exit_state(end_pos);             if (rc != SX_OK) return rc;
+    carry.last_start = r.last_start; carry.last_is_entry = r.last_is_entry; carry.any = true;
     if (ctx->sw.timing)
         fprintf(stderr, "[sx] device replay mission %zu: %zu runs, pass1+entry %.2f ms, validity %.2f ms (%zu standing, %zu host parts), "
-                        "pass2+d2h %.2f ms (%llu findings), splice+state %.2f ms\n", k, n, t1 - t0, t2 - t1, (size_t)n_standing,
-                host_parts.size(), t3 - t2, (unsigned long long)nf, now_ms() - t3);
+                        "pass2+d2h %.2f ms (%llu findings), splice+state %.2f ms\n", k, r.n, t1 - t0, t2 - t1, (size_t)r.n_standing,
+                r.host_parts.size(), t3 - t2, (unsigned long long)r.nf, now_ms() - t3);
     return SX_OK;
 }
 
@@ -429,6 +501,109 @@ static bool slabs_next_to_others(const sx_ctx* ctx, size_t k, const ReplayJob& j
     return true;
 }
 
+// how many slabs Mission k's list is cut into, at most
+static size_t slabs_wanted(const sx_ctx* ctx, size_t k, const ReplayJob& job, const RunList& runs, uint64_t defer_min_bytes) {
+    const size_t n = runs.size();
+    const MissionDev& d = ctx->dev[k];
+    size_t K = 1;
+    const bool alone = ctx->missions.size() == 1 && defer_min_bytes == 0;
+    const bool beside = !alone && slabs_next_to_others(ctx, k, job);
+    const bool can = (alone || beside) && runs.on_device && !ctx->sw.host_stitch;
+    const bool keep_dev_wanted = single_result_stays_on_device(ctx, job, defer_min_bytes);   // (one slab then: one block of the context's)
+    // (measured on string-dense and text-like input, one Mission: 3 beats 2, 4 and 6.  Next to other Missions, on the headline — 1.4 M runs
+    // and 60 MB of findings per half —: 2 beats 1, and 3 and 4 lose to 1: a slab costs two host waits, and the half that is replayed first
+    // does so next to the following half's scan, where every kernel and wait takes longer; DESIGN.md section 5)
+    if (can && n >= (1u << 20) && !keep_dev_wanted) {
+        K = beside ? 2 : 3;
+        // (next to other Missions: only with a buffer behind this one — what the others yield, what this one writes per run)
+        if (beside && (!d.last_out_runs || (defer_min_bytes && 2.0 * (double)n * (double)d.last_out_bytes / (double)d.last_out_runs >= (double)defer_min_bytes))) K = 1;
+    }
+    if (ctx->sw.slabs) { K = (size_t)ctx->sw.slabs; if (!can || n < 8 * K) K = 1; }
+    return K;
+}
+
+// where to cut: idx = the slabs' first runs, closed with n; his[j] = where slab j's first region begins
+static int cut_slabs(sx_ctx* ctx, size_t k, const ReplayJob& job, const RunList& runs, size_t K, std::vector<uint64_t>* idx, std::vector<uint64_t>* his) {
+    const size_t n = runs.size();
+    idx->assign(1, 0); his->assign(1, 0);
+    if (K > 1) {
+        MissionDev& d = ctx->dev[k];
+        int rc = ensure_copy_stream(ctx); if (rc != SX_OK) return rc;
+        rc = ensure_scratch(ctx, 4096); if (rc != SX_OK) return rc;
+        rc = ensure_pinned2(ctx, 4096); if (rc != SX_OK) return rc;
+        ReplayParams P{};
+        P.runs = runs.dev_ptr; P.n_runs = n; P.W = (uint32_t)ctx->missions[k].window; P.grep_char = ctx->missions[k].c.grep_char;
+        uint64_t* d_cut = (uint64_t*)ctx->d_scratch;
+        HIP_TRY(ctx, launch_slab_cuts(P, (uint32_t)K, d_cut, d_cut + 64, d.stream_b));
+        { const int rb = read_back_async(ctx, d.stream_b, ctx->h_pin2, d_cut, 128 * 8); if (rb != SX_OK) return rb; }
+        HIP_TRY(ctx, hipStreamSynchronize(d.stream_b));
+        const uint64_t* h = (const uint64_t*)ctx->h_pin2;
+        plan::accept_slab_cuts(h, h + 64, K, n, job.hi, idx, his);
+    }
+    idx->push_back(n);
+    return SX_OK;
+}
+
+static void note_output(MissionDev& d, size_t n_runs, const MissionFindings& out) {   // for the next buffer's estimate
+    uint64_t bytes = out.count() * sizeof(sx_finding) + out.strings_len();
+    for (const MissionFindings& m : out.more) bytes += m.count() * sizeof(sx_finding) + m.strings_len();
+    d.last_out_runs = n_runs; d.last_out_bytes = bytes;
+}
+
+// The slabs one after the other.  SX_RETRY_WHOLE: nothing was produced and nothing is in flight — the whole-list path takes the Mission.
+static int replay_in_slabs(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& job, const RunList& runs, const std::vector<uint64_t>& idx,
+                           const std::vector<uint64_t>& his, MissionFindings* out, uint64_t* end_pos, uint64_t defer_min_bytes) {
+    MissionDev& d = ctx->dev[k];
+    const size_t ns = idx.size() - 1;
+    std::vector<MissionFindings> got;
+    SlabCarry carry;
+    hipEvent_t copied[2] = { ctx->slab_ev[1], ctx->slab_ev[2] };
+    uint64_t e_prev = 0, written = 0;
+    uint64_t fast0 = 0, general0 = 0;   // (a Mission handed to the whole-list path is counted once)
+    { std::lock_guard<std::mutex> g(ctx->mu); fast0 = ctx->stats.fast_regions; general0 = ctx->stats.general_regions; }
+    int rc = SX_OK;
+    for (size_t j = 0; j < ns && rc == SX_OK; j++) {
+        ReplayJob sj = job;
+        sj.hi = j + 1 < ns ? std::min(job.hi, his[j + 1]) : job.hi;
+        if (j > 0) { sj.lo[k] = std::max(job.lo[k], e_prev); sj.entry_exact[k] = 0; }
+        sj.commit_state = job.commit_state && j + 1 == ns;
+        Slab sl;
+        sl.i0 = idx[j]; sl.i1 = idx[j + 1]; sl.first = j == 0; sl.last = j + 1 == ns;
+        sl.out.slot = rp_out_slot(j); sl.out.async_copy = true; sl.out.leaves_copy_running = true;
+        sl.out.reuse_after = j >= 2 ? copied[j & 1] : nullptr; sl.out.copied = copied[j & 1]; sl.out.written = ctx->slab_ev[0];
+        sl.lo0 = job.lo[k]; sl.entry_exact0 = job.entry_exact[k] != 0;
+        if (defer_min_bytes) {
+            if (written >= defer_min_bytes) { rc = SX_RETRY_WHOLE; break; }
+            sl.out_budget = defer_min_bytes - written;
+        }
+        MissionFindings mf;
+        uint64_t e_now = 0;
+        rc = device_replay_slab(ctx, k, view, sj, runs, sl, carry, &mf, &e_now, 0);
+        e_prev = std::max(e_prev, e_now);
+        if (rc == SX_OK) {
+            out->replay_bytes += mf.replay_bytes; mf.replay_bytes = 0;
+            written += mf.count() * sizeof(sx_finding) + mf.strings_len();
+            if (mf.count()) got.push_back(std::move(mf));
+        } else if (mf.ext.p) got.push_back(std::move(mf));
+    }
+    // On success neither stream is waited for here.  The last slab's copy runs on (slab_copy_drain).  So may the tail of its pass 2
+    // on stream_b, while the caller queues the next Mission's stage A or device replay: that is in order only because every
+    // Mission's stream_b is the one ctx->post_stream (sx_api.cpp) — what is queued next runs behind it —, and because d_cache and
+    // d_scratch grow through hipFree, which waits for the device.  A Mission with a stream of its own would need the wait back.
+    if (rc == SX_OK) {
+        fold_slabs(out, got);
+        if (end_pos) *end_pos = e_prev;
+        return SX_OK;
+    }
+    (void)hipStreamSynchronize(ctx->merge_copy_stream);
+    (void)hipStreamSynchronize(d.stream_b);
+    ctx->slab_copy_pending = false;
+    for (auto& g : got) if (g.ext.p) ctx->pool->give(g.ext);
+    out->replay_bytes = 0;
+    if (rc == SX_RETRY_WHOLE) { std::lock_guard<std::mutex> g(ctx->mu); ctx->stats.fast_regions = fast0; ctx->stats.general_regions = general0; }
+    return rc;
+}
+
 int device_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& job, const RunList& runs,
                           MissionFindings* out, uint64_t* end_pos, uint64_t defer_min_bytes) {
     const size_t n = runs.size();
@@ -440,402 +615,20 @@ int device_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob
         if (k < ctx->wave_pred.size()) ctx->wave_pred[k] = 0;
     }
     if (runs.skipped) return SX_NEED_RUNS;
-    auto note_output = [&]() {   // for the next buffer's estimate
-        uint64_t bytes = out->count() * sizeof(sx_finding) + out->strings_len();
-        for (const MissionFindings& m : out->more) bytes += m.count() * sizeof(sx_finding) + m.strings_len();
-        d.last_out_runs = n; d.last_out_bytes = bytes;
-    };
-    size_t K = 1;
-    const bool alone = ctx->missions.size() == 1 && defer_min_bytes == 0;
-    const bool beside = !alone && slabs_next_to_others(ctx, k, job);
-    const bool can = (alone || beside) && runs.on_device && !ctx->sw.host_stitch;
-    const bool keep_dev_wanted = (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) && ctx->missions.size() == 1 && defer_min_bytes == 0 && job.commit_state && !ctx->sharded_call && ctx->single_piece;   // (one slab then: one block of the context's)
-    // (measured on string-dense and text-like input, one Mission: 3 beats 2, 4 and 6.  Next to other Missions, on the headline — 1.4 M runs
-    // and 60 MB of findings per half —: 2 beats 1, and 3 and 4 lose to 1: a slab costs two host waits, and the half that is replayed first
-    // does so next to the following half's scan, where every kernel and wait takes longer; DESIGN.md section 5)
-    if (can && n >= (1u << 20) && !keep_dev_wanted) {
-        K = beside ? 2 : 3;
-        // (next to other Missions: only with a buffer behind this one — what the others yield, what this one writes per run)
-        if (beside && (!d.last_out_runs || (defer_min_bytes && 2.0 * (double)n * (double)d.last_out_bytes / (double)d.last_out_runs >= (double)defer_min_bytes))) K = 1;
-    }
-    if (ctx->sw.slabs) { K = (size_t)ctx->sw.slabs; if (!can || n < 8 * K) K = 1; }
-    std::vector<uint64_t> idx{ 0 }, his{ 0 };
-    if (K > 1) {   // where to cut
-        int rc = ensure_copy_stream(ctx); if (rc != SX_OK) return rc;
-        rc = ensure_scratch(ctx, 4096); if (rc != SX_OK) return rc;
-        rc = ensure_pinned2(ctx, 4096); if (rc != SX_OK) return rc;
-        ReplayParams P{};
-        P.runs = runs.dev_ptr; P.n_runs = n; P.W = (uint32_t)ctx->missions[k].window; P.grep_char = ctx->missions[k].c.grep_char;
-        uint64_t* d_cut = (uint64_t*)ctx->d_scratch;
-        HIP_TRY(ctx, launch_slab_cuts(P, (uint32_t)K, d_cut, d_cut + 64, d.stream_b));
-        { const int rb = read_back_async(ctx, d.stream_b, ctx->h_pin2, d_cut, 128 * 8); if (rb != SX_OK) return rb; }
-        HIP_TRY(ctx, hipStreamSynchronize(d.stream_b));
-        const uint64_t* h = (const uint64_t*)ctx->h_pin2;
-        for (size_t j = 1; j < K; j++)
-            if (h[j - 1] > idx.back() && h[j - 1] < n && h[64 + j - 1] < job.hi) { idx.push_back(h[j - 1]); his.push_back(h[64 + j - 1]); }
-    }
-    idx.push_back(n);
-    const size_t ns = idx.size() - 1;
-    if (ns > 1) {
-        std::vector<MissionFindings> got;
-        SlabCarry carry;
-        hipEvent_t copied[2] = { ctx->slab_ev[1], ctx->slab_ev[2] };
-        uint64_t e_prev = 0, written = 0;
-        uint64_t fast0 = 0, general0 = 0;   // (a Mission handed to the whole-list path is counted once)
-        { std::lock_guard<std::mutex> g(ctx->mu); fast0 = ctx->stats.fast_regions; general0 = ctx->stats.general_regions; }
-        int rc = SX_OK;
-        for (size_t j = 0; j < ns && rc == SX_OK; j++) {
-            ReplayJob sj = job;
-            sj.hi = j + 1 < ns ? std::min(job.hi, his[j + 1]) : job.hi;
-            if (j > 0) { sj.lo[k] = std::max(job.lo[k], e_prev); sj.entry_exact[k] = 0; }
-            sj.commit_state = job.commit_state && j + 1 == ns;
-            Slab sl;
-            sl.i0 = idx[j]; sl.i1 = idx[j + 1]; sl.first = j == 0; sl.last = j + 1 == ns;
-            sl.out_slot = (j & 1) ? 8 : 5; sl.async_copy = true;
-            sl.reuse_after = j >= 2 ? copied[j & 1] : nullptr; sl.copied = copied[j & 1]; sl.written = ctx->slab_ev[0];
-            sl.lo0 = job.lo[k]; sl.entry_exact0 = job.entry_exact[k] != 0;
-            if (defer_min_bytes) {
-                if (written >= defer_min_bytes) { rc = SX_RETRY_WHOLE; break; }
-                sl.out_budget = defer_min_bytes - written;
-            }
-            MissionFindings mf;
-            uint64_t e_now = 0;
-            rc = device_replay_slab(ctx, k, view, sj, runs, sl, carry, &mf, &e_now, 0);
-            e_prev = std::max(e_prev, e_now);
-            if (rc == SX_OK) {
-                out->replay_bytes += mf.replay_bytes; mf.replay_bytes = 0;
-                written += mf.count() * sizeof(sx_finding) + mf.strings_len();
-                if (mf.count()) got.push_back(std::move(mf));
-            } else if (mf.ext.p) got.push_back(std::move(mf));
-        }
-        // On success neither stream is waited for here.  The last slab's copy runs on (slab_copy_drain).  So may the tail of its pass 2
-        // on stream_b, while the caller queues the next Mission's stage A or device replay: that is in order only because every
-        // Mission's stream_b is the one ctx->post_stream (sx_api.cpp) — what is queued next runs behind it —, and because d_cache and
-        // d_scratch grow through hipFree, which waits for the device.  A Mission with a stream of its own would need the wait back.
-        if (rc == SX_OK) {
-            const uint64_t rb = out->replay_bytes;
-            if (!got.empty()) {
-                *out = std::move(got[0]);
-                for (size_t j = 1; j < got.size(); j++) out->more.push_back(std::move(got[j]));
-            }
-            out->replay_bytes = rb;
-            if (end_pos) *end_pos = e_prev;
-            note_output();
-            return SX_OK;
-        }
-        (void)hipStreamSynchronize(ctx->merge_copy_stream);
-        (void)hipStreamSynchronize(d.stream_b);
-        ctx->slab_copy_pending = false;
-        for (auto& g : got) if (g.ext.p) ctx->pool->give(g.ext);
-        out->replay_bytes = 0;
+    std::vector<uint64_t> idx, his;
+    int rc = cut_slabs(ctx, k, job, runs, slabs_wanted(ctx, k, job, runs, defer_min_bytes), &idx, &his);
+    if (rc != SX_OK) return rc;
+    if (idx.size() > 2) {
+        rc = replay_in_slabs(ctx, k, view, job, runs, idx, his, out, end_pos, defer_min_bytes);
+        if (rc == SX_OK) note_output(d, n, *out);
         if (rc != SX_RETRY_WHOLE) return rc;
-        { std::lock_guard<std::mutex> g(ctx->mu); ctx->stats.fast_regions = fast0; ctx->stats.general_regions = general0; }
     }
     Slab sl;
     sl.i1 = n;
     SlabCarry carry;
-    const int rc = device_replay_slab(ctx, k, view, job, runs, sl, carry, out, end_pos, defer_min_bytes);
-    if (rc == SX_OK) note_output();
+    rc = device_replay_slab(ctx, k, view, job, runs, sl, carry, out, end_pos, defer_min_bytes);
+    if (rc == SX_OK) note_output(d, n, *out);
     return rc;
-}
-
-// A mission's findings that were left on the device (dev_only) come to the host after all.
-static int fetch_deferred(sx_ctx* ctx, MissionFindings& mf) {
-    if (!mf.dev_only) return SX_OK;
-    const size_t bytes = mf.ext_nf * sizeof(sx_finding) + mf.ext_na;
-    PinnedPool::Block blk = ctx->pool->take(bytes + 64);
-    if (!blk.p) { ctx->err = "hipHostMalloc failed"; return SX_E_NOMEM; }
-    HIP_TRY(ctx, hipMemcpyAsync(blk.p, mf.dev_copy, bytes, hipMemcpyDeviceToHost, ctx->post_stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->post_stream));
-    mf.ext = blk; mf.dev_only = false;
-    return SX_OK;
-}
-
-// SX_OPT_RESULT_ON_DEVICE with several Missions: does this call's merged result stay in HBM?  (What only shows later — no findings,
-// Missions that count from different origins, no memory for the block — is device_merge's to see.)
-bool result_stays_on_device(const sx_ctx* ctx, const ReplayJob& job) {
-    return (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) && ctx->missions.size() >= 2 && merge_part_can_pack(1, (int)ctx->missions.size()) && !ctx->host_only &&
-           job.d_bytes && job.commit_state && !ctx->sharded_call && ctx->single_piece && !ctx->sw.host_merge;
-}
-
-// ... then a Mission's list that exists on the host only (few runs: the host replayed it; ISO-2022-JP's sequential pass; regions the device
-// gave back) joins the merge as a device list: [records][strings] of all such lists through one pinned block, one copy, into memory of
-// the context's.  SX_E_NOMEM without an error text: no memory for it, the result goes to the host.
-static int upload_host_lists(sx_ctx* ctx, std::vector<MissionFindings>& per, std::vector<char>& uploaded) {
-    uint64_t need = 0;
-    for (auto& mf : per) {
-        if (!mf.count() || mf.dev_copy) continue;
-        if (!mf.more.empty() || mf.packed) return SX_E_NOMEM;   // (a single Mission's forms)
-        need += (mf.count() * sizeof(sx_finding) + mf.strings_len() + 255) & ~(uint64_t)255;
-    }
-    if (!need) return SX_OK;
-    if (ctx->d_result_up_cap < need) {
-        if (ctx->d_result_up) HIP_TRY(ctx, hipFree(ctx->d_result_up));
-        ctx->d_result_up = nullptr; ctx->d_result_up_cap = 0;
-        if (hipMalloc((void**)&ctx->d_result_up, need) != hipSuccess) { (void)hipGetLastError(); ctx->d_result_up = nullptr; return SX_E_NOMEM; }
-        ctx->d_result_up_cap = need;
-    }
-    PinnedPool::Block blk = ctx->pool->take(need);
-    if (!blk.p) return SX_E_NOMEM;
-    uint64_t at = 0;
-    for (size_t k = 0; k < per.size(); k++) {
-        MissionFindings& mf = per[k];
-        if (!mf.count() || mf.dev_copy) continue;
-        const uint64_t fb = mf.count() * sizeof(sx_finding);
-        memcpy((uint8_t*)blk.p + at, mf.data(), fb);
-        memcpy((uint8_t*)blk.p + at + fb, mf.strings(), mf.strings_len());
-        mf.dev_copy = ctx->d_result_up + at; uploaded[k] = 1;
-        at += (fb + mf.strings_len() + 255) & ~(uint64_t)255;
-    }
-    hipError_t e = hipMemcpyAsync(ctx->d_result_up, blk.p, need, hipMemcpyHostToDevice, ctx->post_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->post_stream);
-    ctx->pool->give(blk);
-    if (e != hipSuccess) {
-        for (size_t k = 0; k < per.size(); k++) if (uploaded[k]) { per[k].dev_copy = nullptr; uploaded[k] = 0; }
-        HIP_TRY(ctx, e);
-    }
-    return SX_OK;
-}
-
-int merge_drain(sx_ctx* ctx) {
-    std::lock_guard<std::recursive_mutex> g(ctx->grow_mu);   // (a wave Mission's thread may get here through ensure_rp)
-    if (ctx->post_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->post_stream));
-    if (ctx->merge_copy_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->merge_copy_stream));
-    ctx->merge_copy_pending[0] = ctx->merge_copy_pending[1] = false;
-    ctx->slab_copy_pending = false;
-    ctx->interleave_pending = false;
-    return SX_OK;
-}
-
-// The merger (src/main.rs:118-136) on the device: the missions' findings, each ordered by position and still in HBM, are
-// interleaved there (sx_sort.hip: every finding's place follows from short searches in the other missions' lists) and arrive on
-// the host as they will be printed.  str_off has 32 bits and the place table 32-bit indices: a large output is cut at slice
-// boundaries into parts (each at most SX_MERGE_PART_MIB of strings and SX_MERGE_PART_FINDINGS findings) that become one segment
-// of the result each; the copy of part j runs while part j+1 is interleaved.  If the conditions do not hold the host merges
-// (merge_findings).
-// SX_OPT_RESULT_ON_DEVICE (result_stays_on_device): the parts are written one behind the other, each 256-byte aligned, into the context's
-// result block and stay there — no pinned block, no copy; each becomes a segment the caller reads through sx_result_segment_device.
-// Their strings lie back to back in record order (merge_findings_device_part's `ordered`).  Small results and a single Mission with
-// findings among several take this way too, lists on the host are uploaded first; all segments of a result are on the device or none is.
-static int device_merge(sx_ctx* ctx, const ReplayJob& job, std::vector<MissionFindings>& per, Result* into) {
-    const size_t nm = per.size();
-    size_t with = 0, on_dev = 0, deferred = 0;
-    uint64_t total = 0, bytes = 0;
-    bool same_origin = true;
-    for (size_t k = 0; k < nm; k++) {
-        if (!per[k].count()) continue;
-        with++;
-        if ((per[k].ext.p || per[k].dev_only) && per[k].dev_copy) on_dev++;
-        if (per[k].dev_only) deferred++;
-        total += per[k].count(); bytes += per[k].strings_len();
-        same_origin = same_origin && job.consumed0[k] == job.consumed0[0];
-    }
-    std::vector<char> uploaded(nm, 0);
-    auto give_up = [&]() -> int {
-        for (size_t k = 0; k < nm; k++) if (uploaded[k]) { per[k].dev_copy = nullptr; uploaded[k] = 0; }   // (the host's copy is the list again)
-        for (auto& mf : per) { if (mf.keep_on_device) continue; int rc = fetch_deferred(ctx, mf); if (rc != SX_OK) return rc; }   // (SX_OPT_RESULT_ON_DEVICE: it stays)
-        return SX_OK;
-    };
-    bool keep = result_stays_on_device(ctx, job) && total > 0 && same_origin;
-    if (keep && on_dev != with) {
-        const int rc = upload_host_lists(ctx, per, uploaded);
-        if (rc == SX_E_NOMEM) keep = false;
-        else if (rc != SX_OK) return rc;
-        else on_dev = with;
-    }
-    // (the way to the host: worth it for two lists or more of some size, all of them still in HBM)
-    auto host_way_ok = [&]() { return with >= 2 && on_dev == with && same_origin && total >= 4096 && !ctx->sw.host_merge; };
-    if (!keep && !host_way_ok()) return give_up();
-    const double tm0 = now_ms();
-    // The records cross PCIe as sx_finding16 (include/stringsext_amd.h): half the bytes of what bounds this path.  Not with lines of
-    // more than 16 000 chars (str_len has 16 bits there), nor where the one-pass merger does not apply (SX_PACKED=0: tests).
-    bool pack = ctx->sw.packed;
-    for (size_t k = 0; k < nm; k++) pack = pack && ctx->missions[k].q <= 16000;
-    std::shared_ptr<SegInfo> seg_info;
-    if (pack) {
-        seg_info = std::make_shared<SegInfo>();
-        seg_info->file_id = job.file_id; seg_info->slice_base = job.slice_base;
-        for (auto& x : seg_info->pos0) x = 0;
-        for (size_t k = 0; k < nm; k++) seg_info->pos0[ctx->missions[k].c.mission_id] = job.consumed0[k];
-    }
-    uint64_t part_bytes = 2048ull << 20, part_findings = 96ull << 20;
-    if (ctx->sw.merge_part_mib) part_bytes = ctx->sw.merge_part_mib << 20;
-    if (ctx->sw.merge_part_findings) part_findings = ctx->sw.merge_part_findings;
-    if (part_bytes > (3584ull << 20)) part_bytes = 3584ull << 20;
-    uint64_t K = std::max<uint64_t>(1, std::max((bytes + part_bytes - 1) / part_bytes, (total + part_findings - 1) / part_findings));
-    hipStream_t s = ctx->post_stream;
-    const uint64_t n_slices = (job.len + kInputBufLen - 1) / kInputBufLen;
-    std::vector<std::vector<uint64_t>> idx(nm), off(nm);   // per mission: K + 1 finding indices and string offsets
-    for (int attempt = 0;; attempt++) {
-        if (K > n_slices) K = std::max<uint64_t>(1, n_slices);
-        for (size_t k = 0; k < nm; k++) { idx[k].assign(K + 1, 0); off[k].assign(K + 1, 0); idx[k][K] = per[k].count(); off[k][K] = per[k].strings_len(); }
-        if (K > 1) {
-            std::vector<uint64_t> cuts(K - 1);
-            for (uint64_t j = 1; j < K; j++) cuts[j - 1] = job.consumed0[0] + (n_slices * j / K) * kInputBufLen;
-            const size_t row = (K - 1) * 8;
-            int rc = ensure_scratch(ctx, row * (1 + 2 * nm) + 256);
-            if (rc != SX_OK) return rc;
-            rc = ensure_pinned2(ctx, row * 2 * nm + 256);
-            if (rc != SX_OK) return rc;
-            uint64_t* d_cuts = (uint64_t*)ctx->d_scratch;
-            HIP_TRY(ctx, hipMemcpyAsync(d_cuts, cuts.data(), row, hipMemcpyHostToDevice, s));
-            for (size_t k = 0; k < nm; k++)
-                if (per[k].count())
-                    HIP_TRY(ctx, launch_merge_cuts((const sx_finding*)per[k].dev_copy, per[k].count(), per[k].strings_len(), d_cuts,
-                                                   (uint32_t)(K - 1), d_cuts + (K - 1) * (1 + 2 * k), d_cuts + (K - 1) * (2 + 2 * k), s));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pin2, d_cuts + (K - 1), row * 2 * nm, hipMemcpyDeviceToHost, s));
-            HIP_TRY(ctx, hipStreamSynchronize(s));
-            const uint64_t* h = (const uint64_t*)ctx->h_pin2;
-            for (size_t k = 0; k < nm; k++)
-                if (per[k].count())
-                    for (uint64_t j = 1; j < K; j++) { idx[k][j] = h[(K - 1) * 2 * k + (j - 1)]; off[k][j] = h[(K - 1) * (2 * k + 1) + (j - 1)]; }
-                else
-                    for (uint64_t j = 1; j < K; j++) { idx[k][j] = 0; off[k][j] = 0; }
-        }
-        bool fits = true;
-        for (uint64_t j = 0; j < K && fits; j++) {
-            uint64_t pb = 0, pf = 0;
-            for (size_t k = 0; k < nm; k++) { pb += off[k][j + 1] - off[k][j]; pf += idx[k][j + 1] - idx[k][j]; }
-            fits = pb <= 0xFFFFFFF0ull && (pf <= 2 * part_findings || K >= n_slices);
-        }
-        if (fits) break;
-        if (attempt >= 8 || K >= n_slices) return give_up();   // (one slice alone with more than 4 GiB of strings cannot be)
-        K *= 2;
-    }
-    // the parts, two output buffers in turn: the copy of one runs while the next is sorted
-    uint64_t max_out = 0, max_n = 0;
-    for (uint64_t j = 0; j < K; j++) {
-        uint64_t pb = 0, pf = 0;
-        for (size_t k = 0; k < nm; k++) { pb += off[k][j + 1] - off[k][j]; pf += idx[k][j + 1] - idx[k][j]; }
-        max_out = std::max(max_out, pf * sizeof(sx_finding) + pb); max_n = std::max(max_n, pf);
-    }
-    if (keep) {   // the result block: every part's [records][strings], 256-byte aligned; the merger's scratch is the context's
-        uint64_t need = 0;
-        for (uint64_t j = 0; j < K && keep; j++) {
-            uint64_t pb = 0, pf = 0;
-            for (size_t k = 0; k < nm; k++) { pb += off[k][j + 1] - off[k][j]; pf += idx[k][j + 1] - idx[k][j]; }
-            if (!pf) continue;
-            keep = merge_part_can_pack(pf, (int)nm);   // (else the radix sort, whose arena is grouped by Mission: to the host as ever)
-            need += (pf * (pack ? sizeof(sx_finding16) : sizeof(sx_finding)) + pb + 255) & ~(uint64_t)255;
-        }
-        if (keep) { const int rc = ensure_scratch(ctx, merge_findings_scratch_bytes(max_n, (int)nm, 1) + 512); if (rc != SX_OK) return rc; }
-        if (keep && ctx->d_result_cap < need) {
-            if (ctx->d_result) HIP_TRY(ctx, hipFree(ctx->d_result));   // (what it held went with the epoch)
-            ctx->d_result = nullptr; ctx->d_result_cap = 0;
-            if (hipMalloc((void**)&ctx->d_result, need) != hipSuccess) { (void)hipGetLastError(); ctx->d_result = nullptr; keep = false; }   // no room: the host result
-            else ctx->d_result_cap = need;
-        }
-        if (!keep && !host_way_ok()) return give_up();
-    }
-    uint64_t result_at = 0;
-    const size_t out_room = (max_out + 511) & ~(size_t)255;
-    const size_t n_out = (K > 1 || ctx->merge_async) ? 2 : 1;
-    const size_t tmp_need = merge_findings_scratch_bytes(max_n, (int)nm) + 512;
-    { int rc = ensure_copy_stream(ctx); if (rc != SX_OK) return rc; }
-    if (!keep && (ctx->merge_out_room < out_room || ctx->merge_n_out < n_out || ctx->d_merge_cap < ctx->merge_n_out * ctx->merge_out_room + tmp_need)) {
-        // (the copy of an earlier call's last part may still read the buffers that are about to go)
-        int rc = merge_drain(ctx);
-        if (rc != SX_OK) return rc;
-        if (ctx->d_merge) HIP_TRY(ctx, hipFree(ctx->d_merge));
-        ctx->d_merge = nullptr; ctx->d_merge_cap = 0; ctx->merge_out_room = 0; ctx->merge_n_out = 0;
-        // pieces of one buffer are alike but not equal: a quarter more than this one needs
-        const size_t room = ctx->merge_async ? ((out_room + out_room / 4 + 511) & ~(size_t)255) : out_room;
-        const size_t tmp = ctx->merge_async ? tmp_need + tmp_need / 4 : tmp_need;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_merge, n_out * room + tmp));
-        ctx->d_merge_cap = n_out * room + tmp; ctx->merge_out_room = room; ctx->merge_n_out = n_out;
-    }
-    uint8_t* d_tmp = ctx->d_merge + ctx->merge_n_out * ctx->merge_out_room;
-    const size_t tmp_bytes = ctx->d_merge_cap - ctx->merge_n_out * ctx->merge_out_room;
-    hipStream_t cs = ctx->merge_copy_stream;
-    hipEvent_t ev_sorted = ctx->merge_ev[0], ev_copied[2] = { ctx->merge_ev[1], ctx->merge_ev[2] };
-    std::vector<const sx_finding*> fp(nm);
-    std::vector<const uint8_t*> ap(nm);
-    std::vector<uint64_t> pnf(nm), pnb(nm);
-    std::vector<uint32_t> off0(nm);
-    std::vector<MissionFindings> outs;
-    // leaving early (a HIP error, no pinned memory): no copy may still be writing into a block that goes back to the pool
-    struct Guard {
-        sx_ctx* ctx; std::vector<MissionFindings>* outs; bool done = false;
-        ~Guard() {
-            if (done) return;
-            (void)merge_drain(ctx);
-            for (auto& o : *outs) if (o.ext.p) ctx->pool->give(o.ext);
-            outs->clear();
-        }
-    } guard{ ctx, &outs };
-    uint64_t rb = 0;
-    for (size_t k = 0; k < nm; k++) rb += per[k].replay_bytes;
-    for (uint64_t j = 0; j < K; j++) {
-        uint64_t pb = 0, pf = 0;
-        for (size_t k = 0; k < nm; k++) {
-            const sx_finding* f0 = (const sx_finding*)per[k].dev_copy;
-            const uint8_t* a0 = (const uint8_t*)per[k].dev_copy + per[k].count() * sizeof(sx_finding);
-            fp[k] = f0 ? f0 + idx[k][j] : nullptr; ap[k] = f0 ? a0 + off[k][j] : nullptr;
-            pnf[k] = idx[k][j + 1] - idx[k][j]; pnb[k] = off[k][j + 1] - off[k][j]; off0[k] = (uint32_t)off[k][j];
-            pf += pnf[k]; pb += pnb[k];
-        }
-        if (!pf) continue;
-        if (keep) {
-            const bool pack_part = pack;   // (merge_part_can_pack: checked above)
-            uint8_t* d_part = ctx->d_result + result_at;
-            HIP_TRY(ctx, merge_findings_device_part(fp.data(), ap.data(), pnf.data(), pnb.data(), off0.data(), (int)nm, d_part, ctx->d_scratch, ctx->d_scratch_cap, s, pack_part ? 1 : 0, 1));
-            result_at += (pf * (pack_part ? sizeof(sx_finding16) : sizeof(sx_finding)) + pb + 255) & ~(uint64_t)255;
-            outs.emplace_back();
-            MissionFindings& o = outs.back();
-            o.dev_only = true; o.keep_on_device = true; o.dev_epoch_ref = ctx->dev_epoch; o.dev_epoch = ctx->dev_epoch->load();
-            o.ext_nf = pf; o.ext_na = pb; o.dev_copy = d_part;
-            if (pack_part) { o.packed = true; o.info = seg_info; }
-            continue;
-        }
-        const unsigned ob = ctx->merge_n_out == 2 ? (unsigned)(ctx->merge_parts & 1) : 0u;   // (parts of all calls in turn: merge_async)
-        ctx->merge_parts++;
-        uint8_t* d_out = ctx->d_merge + ob * ctx->merge_out_room;
-        if (ctx->merge_copy_pending[ob]) HIP_TRY(ctx, hipStreamWaitEvent(s, ev_copied[ob], 0));   // the buffer is free again
-        const bool pack_part = pack && merge_part_can_pack(pf, (int)nm);
-        HIP_TRY(ctx, merge_findings_device_part(fp.data(), ap.data(), pnf.data(), pnb.data(), off0.data(), (int)nm, d_out, d_tmp, tmp_bytes, s, pack_part ? 1 : 0));
-        HIP_TRY(ctx, hipEventRecord(ev_sorted, s));
-        const size_t out_bytes = pf * (pack_part ? sizeof(sx_finding16) : sizeof(sx_finding)) + pb;
-        PinnedPool::Block blk = ctx->pool->take(out_bytes + 64);
-        if (!blk.p) { ctx->err = "hipHostMalloc failed"; return SX_E_NOMEM; }
-        HIP_TRY(ctx, hipStreamWaitEvent(cs, ev_sorted, 0));
-        {
-            // Next to the kernels of the following piece (merge_async) the copy is a kernel of two workgroups, each writing one
-            // contiguous half into the pinned block: measured on the MI355X (BASELINE config 5, 2.3 GB per piece), hipMemcpyAsync
-            // — a blit kernel that fills the chip with wavefronts waiting on PCIe — delays every kernel next to it until it is done
-            // (a 6 ms scan takes 45), eight workgroups slow the count passes by half, one does not fill the link; two copy at
-            // ~45 GB/s and cost the count passes 8 %.  With nothing next to it the runtime's copy is the faster one (53 GB/s).
-            const int copy_wgs = ctx->sw.merge_copy_wgs >= 0 ? ctx->sw.merge_copy_wgs : (ctx->merge_async ? 2 : 0);
-            if (copy_wgs > 0) HIP_TRY(ctx, launch_copy_bytes(blk.p, d_out, out_bytes, (uint32_t)copy_wgs, cs, ctx->sw.merge_copy_threads, ctx->sw.merge_copy_nt != 0));
-            else HIP_TRY(ctx, hipMemcpyAsync(blk.p, d_out, out_bytes, hipMemcpyDeviceToHost, cs));
-        }
-        HIP_TRY(ctx, hipEventRecord(ev_copied[ob], cs));
-        ctx->merge_copy_pending[ob] = true;
-        ctx->merged_out_bytes += out_bytes;
-        outs.emplace_back();
-        outs.back().ext = blk; outs.back().ext_nf = pf; outs.back().ext_na = pb;
-        if (pack_part) { outs.back().packed = true; outs.back().info = seg_info; }
-    }
-    if (keep) HIP_TRY(ctx, hipStreamSynchronize(s));   // (the pointers may be read from any stream once the call returns)
-    if (ctx->merge_async) {   // a Mission whose stage B writes on a stream of its own waits for this before it overwrites its findings
-        if (!ctx->ev_interleaved) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_interleaved, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_interleaved, s));
-        ctx->interleave_pending = true;
-    }
-    // (merge_async: the last copies run on while the caller scans the next piece of the buffer; the sorts are in order with
-    // everything else stage B does — post_stream —, so the missions' findings and the scratch may be reused at once)
-    if (!ctx->merge_async) { int rc = merge_drain(ctx); if (rc != SX_OK) return rc; }
-    guard.done = true;
-    for (size_t k = 0; k < nm; k++) {
-        if (per[k].ext.p) ctx->pool->give(per[k].ext);
-        per[k] = MissionFindings{};
-    }
-    if (!outs.empty()) outs[0].replay_bytes = rb; else per[0].replay_bytes = rb;
-    into->pool = ctx->pool;
-    for (auto& o : outs) { ctx->stats.replay_bytes += o.replay_bytes; into->segs.push_back(std::move(o)); o.ext = {}; }
-    if (ctx->sw.timing)
-        fprintf(stderr, "[sx] device merge of %zu missions (%zu held back on the device): %llu findings, %llu parts, %.2f ms\n", with, deferred,
-                (unsigned long long)total, (unsigned long long)K, now_ms() - tm0);
-    return SX_OK;
 }
 
 // A Mission whose decoder state cannot be derived from the bytes near a position (ISO-2022-JP): FindingCollection::from over every
@@ -868,6 +661,12 @@ static int host_sequential_mission(sx_ctx* ctx, size_t k, ByteView& bytes, const
     return SX_OK;
 }
 
+// parts are speculative restarts: worth a thread each only if they hold real work
+unsigned host_parts_wanted(const sx_ctx* ctx, size_t k, size_t n_runs) {
+    if (ctx->missions[k].c.chars_min_nb == 0) return 1;  // no speculative restarts (see device_replay_wanted)
+    return (unsigned)std::min<uint64_t>(replay_threads(ctx), std::max<uint64_t>(1, n_runs / 512));
+}
+
 // Stage B for all missions: every (mission, part) pair is one task for a small thread pool;
 // part 0 of a mission starts from its entry state, the others speculate, and the per-mission
 // stitch verifies/repairs them serially.
@@ -888,11 +687,8 @@ int replay_all(sx_ctx* ctx, ByteView& bytes, const ReplayJob& job, const std::ve
     for (size_t k = 0; k < nm; k++) {
         if (on_device[k]) continue;
         HIP_TRY(ctx, runs[k].wait());
-        // parts are speculative restarts: worth a thread each only if they hold real work
-        unsigned want_parts = (unsigned)std::min<uint64_t>(nthreads, std::max<uint64_t>(1, runs[k].size() / 512));
-        if (ctx->missions[k].c.chars_min_nb == 0) want_parts = 1;  // no speculative restarts (see device_replay_wanted)
         host_runs += runs[k].size();
-        replay_plan_range(std::min(job.lo[k], job.hi), job.hi, want_parts, &bounds[k]);
+        replay_plan_range(std::min(job.lo[k], job.hi), job.hi, host_parts_wanted(ctx, k, runs[k].size()), &bounds[k]);
         parts[k].resize(bounds[k].size() - 1);
         for (size_t p = 0; p + 1 < bounds[k].size(); p++) tasks.emplace_back(k, p);
     }
@@ -997,76 +793,73 @@ int download_for_replay(sx_ctx* ctx, const uint8_t* d_bytes, uint64_t len,
     static const std::vector<RunList> no_runs;
     const std::vector<RunList>& runs = runs_opt ? *runs_opt : no_runs;
     if (used_base) *used_base = false;
-        const double t0 = now_ms();
-        std::vector<std::pair<uint64_t, uint64_t>> rg;
-        // what the host always looks at: the chunk's first windows and its tail
-        rg.emplace_back(0, std::min<uint64_t>(len, 64 * 1024));
-        if (len > 64 * 1024) rg.emplace_back(len - 64 * 1024, len);
-        for (size_t k = 0; k < nm; k++) {
-            if ((skip && (*skip)[k]) || ctx->missions[k].host_sequential() || device_replay_wanted(ctx, job, k, runs[k].size())) continue;  // stage B of this mission runs on the device (or fetches its bytes itself)
-            HIP_TRY(ctx, runs[k].wait());
-            const size_t before = rg.size();
-            // same partition count as replay_all will use
-            unsigned want_parts = (unsigned)std::min<uint64_t>(replay_threads(ctx), std::max<uint64_t>(1, runs[k].size() / 512));
-            if (ctx->missions[k].c.chars_min_nb == 0) want_parts = 1;
-            replay_ranges(ctx->missions[k], ctx->states[k], len, runs[k].data(), runs[k].size(), want_parts, &rg);
-            // a mission's ranges come out almost sorted (runs are); fix up, then merge the sorted lists
-            if (!std::is_sorted(rg.begin() + before, rg.end())) std::sort(rg.begin() + before, rg.end());
-            std::inplace_merge(rg.begin(), rg.begin() + before, rg.end());
-        }
-        const double t_rg = now_ms();
-        std::vector<std::pair<uint64_t, uint64_t>> mg;
-        mg.reserve(rg.size());
-        for (auto& r : rg) {
-            if (!mg.empty() && r.first <= mg.back().second) mg.back().second = std::max(mg.back().second, r.second);
-            else mg.push_back(r);
-        }
-        if (used_base) {  // nothing beyond the base (already in the caller's view)?
-            bool inside = true;
-            for (auto& r : mg)
-                inside = inside && (r.second <= std::min<uint64_t>(len, 64 * 1024) || (len > 64 * 1024 && r.first >= len - 64 * 1024));
-            if (inside) { *used_base = true; return SX_OK; }
-        }
-        // split long ranges so that one gather wavefront never copies more than 64 KiB
-        std::vector<uint64_t> seg_src, seg_dst;
-        std::vector<uint32_t> seg_len;
-        uint64_t total = 0;
+    const double t0 = now_ms();
+    std::vector<std::pair<uint64_t, uint64_t>> rg;
+    // what the host always looks at: the chunk's first windows and its tail
+    rg.emplace_back(0, std::min<uint64_t>(len, 64 * 1024));
+    if (len > 64 * 1024) rg.emplace_back(len - 64 * 1024, len);
+    for (size_t k = 0; k < nm; k++) {
+        if ((skip && (*skip)[k]) || ctx->missions[k].host_sequential() || device_replay_wanted(ctx, job, k, runs[k].size())) continue;  // stage B of this mission runs on the device (or fetches its bytes itself)
+        HIP_TRY(ctx, runs[k].wait());
+        const size_t before = rg.size();
+        replay_ranges(ctx->missions[k], ctx->states[k], len, runs[k].data(), runs[k].size(), host_parts_wanted(ctx, k, runs[k].size()), &rg);
+        // a mission's ranges come out almost sorted (runs are); fix up, then merge the sorted lists
+        if (!std::is_sorted(rg.begin() + before, rg.end())) std::sort(rg.begin() + before, rg.end());
+        std::inplace_merge(rg.begin(), rg.begin() + before, rg.end());
+    }
+    const double t_rg = now_ms();
+    std::vector<std::pair<uint64_t, uint64_t>> mg;
+    mg.reserve(rg.size());
+    for (auto& r : rg) {
+        if (!mg.empty() && r.first <= mg.back().second) mg.back().second = std::max(mg.back().second, r.second);
+        else mg.push_back(r);
+    }
+    if (used_base) {  // nothing beyond the base (already in the caller's view)?
+        bool inside = true;
         for (auto& r : mg)
-            for (uint64_t a = r.first; a < r.second; a += 65536) {
-                const uint64_t n = std::min<uint64_t>(65536, r.second - a);
-                seg_src.push_back(a); seg_dst.push_back(total); seg_len.push_back((uint32_t)n);
-                total += n;
-            }
-        const double t_seg = now_ms();
-        if (total) {
-            hipStream_t s = ctx->dev[0].stream_b;
-            const size_t ns = seg_src.size();
-            const uint64_t seg_bytes = ns * (8 + 8 + 4) + 64;
-            int rc2 = ensure_pinned(ctx, total + 64);
-            if (rc2 != SX_OK) return rc2;
-            rc2 = ensure_scratch(ctx, total + seg_bytes + 256);
-            if (rc2 != SX_OK) return rc2;
-            uint8_t* d_out = ctx->d_scratch;
-            uint64_t* d_src = (uint64_t*)(ctx->d_scratch + ((total + 255) & ~255ull));
-            uint64_t* d_dst = d_src + ns;
-            uint32_t* d_len = (uint32_t*)(d_dst + ns);
-            HIP_TRY(ctx, hipMemcpyAsync(d_src, seg_src.data(), ns * 8, hipMemcpyHostToDevice, s));
-            HIP_TRY(ctx, hipMemcpyAsync(d_dst, seg_dst.data(), ns * 8, hipMemcpyHostToDevice, s));
-            HIP_TRY(ctx, hipMemcpyAsync(d_len, seg_len.data(), ns * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(ctx, launch_gather(d_bytes, d_out, d_src, d_dst, d_len, (uint32_t)ns, s));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pin, d_out, total, hipMemcpyDeviceToHost, s));
-            HIP_TRY(ctx, hipStreamSynchronize(s));
-            uint64_t off = 0;
-            for (auto& r : mg) {
-                if (runs_opt) view->add(r.first, r.second, ctx->h_pin + off);
-                else view->add_copy(r.first, r.second, ctx->h_pin + off);
-                off += r.second - r.first;
-            }
+            inside = inside && (r.second <= std::min<uint64_t>(len, 64 * 1024) || (len > 64 * 1024 && r.first >= len - 64 * 1024));
+        if (inside) { *used_base = true; return SX_OK; }
+    }
+    // split long ranges so that one gather wavefront never copies more than 64 KiB
+    std::vector<uint64_t> seg_src, seg_dst;
+    std::vector<uint32_t> seg_len;
+    uint64_t total = 0;
+    for (auto& r : mg)
+        for (uint64_t a = r.first; a < r.second; a += 65536) {
+            const uint64_t n = std::min<uint64_t>(65536, r.second - a);
+            seg_src.push_back(a); seg_dst.push_back(total); seg_len.push_back((uint32_t)n);
+            total += n;
         }
-        ctx->stats.d2h_ms += now_ms() - t0;
-        if (ctx->sw.timing)
-            fprintf(stderr, "[sx] sparse download: ranges %.2f ms, sort+merge+segments %.2f ms (%zu ranges, %zu segs), gather+d2h %.2f ms (%.1f MB)\n",
-                    t_rg - t0, t_seg - t_rg, mg.size(), seg_src.size(), now_ms() - t_seg, total / 1e6);
+    const double t_seg = now_ms();
+    if (total) {
+        hipStream_t s = ctx->dev[0].stream_b;
+        const size_t ns = seg_src.size();
+        const uint64_t seg_bytes = ns * (8 + 8 + 4) + 64;
+        int rc2 = ensure_pinned(ctx, total + 64);
+        if (rc2 != SX_OK) return rc2;
+        rc2 = ensure_scratch(ctx, total + seg_bytes + 256);
+        if (rc2 != SX_OK) return rc2;
+        uint8_t* d_out = ctx->d_scratch;
+        uint64_t* d_src = (uint64_t*)(ctx->d_scratch + plan::up256(total));
+        uint64_t* d_dst = d_src + ns;
+        uint32_t* d_len = (uint32_t*)(d_dst + ns);
+        HIP_TRY(ctx, hipMemcpyAsync(d_src, seg_src.data(), ns * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_dst, seg_dst.data(), ns * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_len, seg_len.data(), ns * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, launch_gather(d_bytes, d_out, d_src, d_dst, d_len, (uint32_t)ns, s));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pin, d_out, total, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        uint64_t off = 0;
+        for (auto& r : mg) {
+            if (runs_opt) view->add(r.first, r.second, ctx->h_pin + off);
+            else view->add_copy(r.first, r.second, ctx->h_pin + off);
+            off += r.second - r.first;
+        }
+    }
+    ctx->stats.d2h_ms += now_ms() - t0;
+    if (ctx->sw.timing)
+        fprintf(stderr, "[sx] sparse download: ranges %.2f ms, sort+merge+segments %.2f ms (%zu ranges, %zu segs), gather+d2h %.2f ms (%.1f MB)\n",
+                t_rg - t0, t_seg - t_rg, mg.size(), seg_src.size(), now_ms() - t_seg, total / 1e6);
     return SX_OK;
 }
 

@@ -52,7 +52,7 @@ struct Switches {
     int stitch_block = 0;              // SX_STITCH_BLOCK=n (> 0): runs per block of the stitch; 0 unset: 128, 512 from 2^20 runs on (tests)
     int slabs = 0;                     // SX_SLABS=n (1 .. 64): slabs of the device replay of a Mission that may have them (alone, or busy among quiet ones: sx_stage_b.cpp); 0 unset: from 2^20 runs on 3 for a single Mission, 2 next to other Missions (tests)
     int replay_copy_wgs = 0;           // SX_REPLAY_COPY_WGS=n (> 0): the result copy as a kernel of n workgroups, not the runtime's blit (experiments)
-    // ---- the Missions' findings interleaved (sx_stage_b.cpp device_merge, sx_sort.hip, sx_replay.cpp)
+    // ---- the Missions' findings interleaved (sx_merge.cpp device_merge, sx_sort.hip, sx_replay.cpp)
     bool host_merge = false;           // SX_HOST_MERGE presence: interleave on the host (tests)
     bool packed = true;                // SX_PACKED on / off: findings cross PCIe as sx_finding16 (tests)
     uint64_t merge_part_mib = 0;       // SX_MERGE_PART_MIB=n (>= 1): string bytes per part of the device merge; 0 unset: 2048 (tests)

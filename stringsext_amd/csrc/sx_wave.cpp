@@ -148,13 +148,13 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         const uint32_t nwin = (uint32_t)(batches * kWvBatch - kWvWarm);
         n_waves = (n_windows + nwin - 1) / nwin;
         // Slabs of wavefronts: count -> write -> copy to the host, the copy of a slab next to the kernels of the following one.
-        // (Several Missions: one slab; their outputs stay in HBM and are interleaved there, sx_stage_b.cpp device_merge.)
+        // (Several Missions: one slab; their outputs stay in HBM and are interleaved there, sx_merge.cpp device_merge.)
         uint64_t K = 1;
         if (ctx->missions.size() == 1 && defer_min_bytes == 0) K = std::min<uint64_t>(8, std::max<uint64_t>(1, len >> 25));   // >= 32 MiB of input each, eight at most (measured: 256 MiB of text in 4 / 8 / 16 slabs 7.9 / 7.2 / 8.0 ms; `-e ascii -n 4` on 1 GiB in 8 / 16 / 32: 5.15 / 5.27 / 7.0 ms)
         if (ctx->sw.wave_slabs) K = (uint64_t)ctx->sw.wave_slabs;
         if (ctx->missions.size() != 1 || defer_min_bytes != 0) K = 1;
         // SX_OPT_RESULT_ON_DEVICE (round 5): one Mission, no pieces — the result stays where the writer put it (one slab: one block of the context's)
-        const bool keep_dev = (ctx->opt.flags & SX_OPT_RESULT_ON_DEVICE) && ctx->missions.size() == 1 && defer_min_bytes == 0 && job.commit_state && !ctx->sharded_call && ctx->single_piece;
+        const bool keep_dev = single_result_stays_on_device(ctx, job, defer_min_bytes);
         if (keep_dev) K = 1;
         K = std::min<uint64_t>(K, n_waves);
 
@@ -172,18 +172,18 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         }
         // per wavefront: 4 x u32 (pass 1 out) + 2 x u64 (offsets); + totals per slab
         const uint64_t per = 5 * 4 + 2 * 8;   // (+ the two-byte family's grid word)
-        int rc = ensure_rp(ctx, d, 1, n_waves * per + 4096); if (rc) return rc;
+        int rc = ensure_rp(ctx, d, kRpWaveTables, n_waves * per + 4096); if (rc) return rc;
         uint8_t* w_scratch; uint64_t w_scratch_cap;
         if (own_stream) {
-            rc = ensure_rp(ctx, d, 10, wave_scratch_bytes(n_waves)); if (rc) return rc;
-            w_scratch = (uint8_t*)d.d_rp[10]; w_scratch_cap = d.d_rp_cap[10];
+            rc = ensure_rp(ctx, d, kRpWaveScratch, wave_scratch_bytes(n_waves)); if (rc) return rc;
+            w_scratch = (uint8_t*)d.d_rp[kRpWaveScratch]; w_scratch_cap = d.d_rp_cap[kRpWaveScratch];
             if (!d.h_tot) HIP_TRY(ctx, hipHostMalloc((void**)&d.h_tot, 4096, hipHostMallocNonCoherent));
         } else {
             rc = ensure_scratch(ctx, wave_scratch_bytes(n_waves)); if (rc) return rc;
             rc = ensure_pinned2(ctx, 4096); if (rc) return rc;
             w_scratch = ctx->d_scratch; w_scratch_cap = ctx->d_scratch_cap;
         }
-        uint8_t* base = (uint8_t*)d.d_rp[1];
+        uint8_t* base = (uint8_t*)d.d_rp[kRpWaveTables];
         uint64_t* d_tot = (uint64_t*)base;            // 4 x u64 per slab
         uint64_t* d_fb = (uint64_t*)(base + 2048);
         uint64_t* d_ab = d_fb + n_waves;
@@ -204,7 +204,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         uint64_t* d_leads = nullptr;
         uint64_t left_leads = 0;
         if (m.wave_lead_check) {
-            d_leads = (uint64_t*)(((uintptr_t)(d_u + 5 * n_waves) + 7) & ~(uintptr_t)7);   // (inside the 4096 spare bytes of d_rp[1])
+            d_leads = (uint64_t*)(((uintptr_t)(d_u + 5 * n_waves) + 7) & ~(uintptr_t)7);   // (inside the 4096 spare bytes of kRpWaveTables)
             HIP_TRY(ctx, hipMemsetAsync(d_leads, 0, 8, sb));
             for (unsigned char c : st.last_scan_run_leftover) if (c >= 0xC2 && c <= 0xF4 && ((m.c.ubf >> (c & 0x3F)) & 1)) left_leads |= 1ull << (c & 0x3F);
             if (__builtin_popcountll(left_leads) > 1) return SX_WAVE_FALLBACK;
@@ -236,7 +236,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
             if (ctx->sw.wave_desc_cap) cap = (uint64_t)ctx->sw.wave_desc_cap;
             if (too_dense) cap = 0;
             if (cap == 0) { }
-            else if (ensure_rp(ctx, d, 2, n_waves * cap * 12 + 64) == SX_OK) { P.desc = (uint32_t*)d.d_rp[2]; P.desc_cap = (uint32_t)cap; }
+            else if (ensure_rp(ctx, d, kRpWaveDesc, n_waves * cap * 12 + 64) == SX_OK) { P.desc = (uint32_t*)d.d_rp[kRpWaveDesc]; P.desc_cap = (uint32_t)cap; }
             else ctx->set_err(std::string());   // (no room: the other writer)
         }
         if (K > 1) {
@@ -254,10 +254,7 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
         std::shared_ptr<SegInfo> seg_info;
         std::vector<sx_finding16> hf16;
         if (pack) {
-            seg_info = std::make_shared<SegInfo>();
-            seg_info->file_id = job.file_id; seg_info->slice_base = job.slice_base;
-            for (auto& x : seg_info->pos0) x = 0;
-            seg_info->pos0[m.c.mission_id] = job.consumed0[k];
+            seg_info = make_seg_info(ctx, job, k, k + 1);
             hf16.reserve(hf.v.size());
             for (const sx_finding& f : hf.v) hf16.push_back(pack_finding(f));
         }
@@ -317,23 +314,21 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
             const uint64_t nf = h_tot[4 * j], nb = h_tot[4 * j + 1];
             if (ctx->sw.timing2) fprintf(stderr, "[sx]   ... counted %llu findings, %llu bytes at +%.2f ms\n", (unsigned long long)nf, (unsigned long long)nb, now_ms() - t0);
             final_state = (uint32_t)h_tot[4 * j + 3];
-            const uint64_t nfh_j = j == 0 ? nfh : 0, nbh_j = j == 0 ? nbh : 0;   // the host's entry windows go in front of the first slab
-            if (nb + nbh_j > 0xFFFFFFFFull) { ctx->set_err("more than 4 GiB of strings in one chunk"); return abandon(SX_E_NOMEM); }
+            // the host's entry windows go in front of the first slab
+            const plan::SlabOut lay = plan::slab_out_layout(j == 0 ? nfh : 0, nf, j == 0 ? nbh : 0, nb, rec);
+            rc = slab_strings_limit(ctx, lay.strings()); if (rc) return abandon(rc);
             nf_all += nf; nb_all += nb;
-            if (nf + nfh_j == 0) continue;
-            // ---- pass 2 straight into the result's layout: [host findings][device findings][host strings][device strings]
-            const uint64_t out_bytes = (nfh_j + nf) * rec + nbh_j + nb;
-            const int slot = (j & 1) ? 8 : 5;
-            if (pending[j & 1]) {   // the copy of slab j - 2 may still read this buffer
-                if (d.d_rp_cap[slot] < out_bytes + 64) HIP_TRY(ctx, hipEventSynchronize(copied[j & 1]));
-                else HIP_TRY(ctx, hipStreamWaitEvent(sb, copied[j & 1], 0));
-            }
-            rc = ensure_rp(ctx, d, slot, out_bytes + 64); if (rc) return abandon(rc);
-            uint8_t* d_all = (uint8_t*)d.d_rp[slot];
+            if (lay.findings() == 0) continue;
+            // ---- pass 2 straight into the result's layout (slab_out_*, sx_ctx.hpp); the copy of slab j - 2 may still read this buffer
+            SlabOutPath path;
+            path.stream = sb; path.slot = rp_out_slot(j); path.async_copy = K > 1;
+            path.written = ctx->merge_ev[0]; path.copied = copied[j & 1]; path.reuse_after = pending[j & 1] ? copied[j & 1] : nullptr;
+            uint8_t* d_all = nullptr;
+            rc = slab_out_reserve(ctx, d, path, lay, &d_all); if (rc) return abandon(rc);
             if (nf) {
-                P.findings = (sx_finding*)(d_all + nfh_j * rec);
-                P.arena = d_all + (nfh_j + nf) * rec + nbh_j;
-                P.str_off_base = (uint32_t)nbh_j; P.f_sub = 0; P.a_sub = 0;
+                P.findings = (sx_finding*)(d_all + lay.dev_f);
+                P.arena = d_all + lay.dev_s;
+                P.str_off_base = (uint32_t)lay.nbh; P.f_sub = 0; P.a_sub = 0;
                 // (pieces: the interleave of the piece before may still read this Mission's findings — on post_stream, not this stream)
                 if (own_stream && ctx->interleave_pending) HIP_TRY(ctx, hipStreamWaitEvent(sb, ctx->ev_interleaved, 0));
                 HIP_TRY(ctx, hipEventRecord(d.wave_ev[4 * j + 2], sb));
@@ -341,40 +336,20 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
                 HIP_TRY(ctx, hipEventRecord(d.wave_ev[4 * j + 3], sb));
                 wrote[j] = 1;
             }
-            if (nfh_j) {
-                HIP_TRY(ctx, hipMemcpyAsync(d_all, pack ? (const void*)hf16.data() : (const void*)hf.v.data(), nfh_j * rec, hipMemcpyHostToDevice, sb));
-                if (nbh_j) HIP_TRY(ctx, hipMemcpyAsync(d_all + (nfh_j + nf) * rec, hf.arena.data(), nbh_j, hipMemcpyHostToDevice, sb));
-            }
+            rc = slab_out_upload_entry(ctx, path, lay, d_all, pack ? (const void*)hf16.data() : (const void*)hf.v.data(), hf.arena.data());
+            if (rc) return abandon(rc);
             MissionFindings seg;
             if (pack) { seg.packed = true; seg.info = seg_info; }
             deferred = K == 1 && defer_min_bytes && nf * sizeof(sx_finding) + nb >= defer_min_bytes;
-            if (keep_dev) {
-                HIP_TRY(ctx, hipStreamSynchronize(sb));
-                seg.dev_only = true; seg.keep_on_device = true; seg.dev_epoch_ref = ctx->dev_epoch; seg.dev_epoch = ctx->dev_epoch->load();
-                seg.ext_nf = nfh_j + nf; seg.ext_na = nbh_j + nb; seg.dev_copy = d_all;
-            } else if (deferred) {
-                HIP_TRY(ctx, hipStreamSynchronize(sb));
-                if (ctx->sw.timing2) fprintf(stderr, "[sx]   ... written (left on the device) at +%.2f ms\n", now_ms() - t0);
-                seg.dev_only = true; seg.ext_nf = nfh_j + nf; seg.ext_na = nbh_j + nb; seg.dev_copy = d_all;
-            } else {
-                PinnedPool::Block blk = ctx->pool->take(out_bytes + 64);
-                if (!blk.p) { ctx->set_err("hipHostMalloc failed"); return abandon(SX_E_NOMEM); }
-                seg.ext = blk; seg.ext_nf = nfh_j + nf; seg.ext_na = nbh_j + nb;
-                if (K > 1) {   // on the copy stream: the next slab's kernels run meanwhile
-                    segs.push_back(std::move(seg));
-                    HIP_TRY(ctx, hipEventRecord(ctx->merge_ev[0], sb));
-                    HIP_TRY(ctx, hipStreamWaitEvent(ctx->merge_copy_stream, ctx->merge_ev[0], 0));
-                    HIP_TRY(ctx, hipMemcpyAsync(blk.p, d_all, out_bytes, hipMemcpyDeviceToHost, ctx->merge_copy_stream));
-                    HIP_TRY(ctx, hipEventRecord(copied[j & 1], ctx->merge_copy_stream));
-                    pending[j & 1] = true;
-                    if (nfh_j) HIP_TRY(ctx, hipStreamSynchronize(sb));   // (the entry part's upload reads host vectors)
-                    continue;
-                }
-                HIP_TRY(ctx, hipMemcpyAsync(blk.p, d_all, out_bytes, hipMemcpyDeviceToHost, sb));
-                HIP_TRY(ctx, hipStreamSynchronize(sb));
-                seg.dev_copy = d_all;
-            }
-            segs.push_back(std::move(seg));
+            const SlabDest dest = keep_dev ? SlabDest::Keep : deferred ? SlabDest::Defer : SlabDest::Pinned;
+            PinnedPool::Block blk{};
+            rc = slab_out_deliver(ctx, path, lay, dest, d_all, &blk);
+            if (rc == SX_OK) rc = slab_out_settle(ctx, path, lay);
+            slab_out_describe(ctx, path, lay, dest, blk, d_all, &seg);
+            if (rc == SX_OK || blk.p) segs.push_back(std::move(seg));   // (a block that was taken goes back through abandon)
+            if (rc) return abandon(rc);
+            if (path.async_copy) pending[j & 1] = true;
+            if (dest == SlabDest::Defer && ctx->sw.timing2) fprintf(stderr, "[sx]   ... written (left on the device) at +%.2f ms\n", now_ms() - t0);
         }
         if (K > 1) {
             HIP_TRY(ctx, hipStreamSynchronize(ctx->merge_copy_stream));
@@ -392,12 +367,8 @@ int wave_replay_mission(sx_ctx* ctx, size_t k, ByteView& view, const ReplayJob& 
     } else if (nfh) {   // the host's windows were the whole buffer
         out->v = std::move(hf.v); out->arena = std::move(hf.arena);
     }
-    if (!segs.empty()) {
-        const uint64_t rb = out->replay_bytes;
-        *out = std::move(segs[0]);
-        for (size_t j = 1; j < segs.size(); j++) out->more.push_back(std::move(segs[j]));
-        out->replay_bytes = rb;
-    } else if (g_lo < g_all && nfh) { out->v = std::move(hf.v); out->arena = std::move(hf.arena); }
+    if (!segs.empty()) fold_slabs(out, segs);
+    else if (g_lo < g_all && nfh) { out->v = std::move(hf.v); out->arena = std::move(hf.arena); }
     out->replay_bytes += len;
     { std::lock_guard<std::mutex> g(ctx->mu); ctx->stats.wave_windows += g_all - g_lo; }
     // the next whole buffer of this Mission does without stage A (sx_schedule.cpp) as long as this one was string-dense

@@ -30,7 +30,12 @@ def build_classify():
     return _build("libclassify_host.so", "classify_host.cpp", ("sx_classify_ranges.hpp", "sx_device.hpp"))
 
 
+def build_stage_b_plan():
+    return _build("libstage_b_plan_host.so", "stage_b_plan_host.cpp", ("sx_stage_b_plan.hpp",))
+
+
 if __name__ == "__main__":
     print(build_replay_core())
     print(build_wave_core())
     print(build_classify())
+    print(build_stage_b_plan())

@@ -507,7 +507,7 @@ def test_every_switch_gives_the_same_text(env, monkeypatch):
                                  {"SX_SEQ_PIECE_KIB": "1024", "SX_DEFER_MIN_BYTES": "1", "SX_WAVE_REPLAY": "1"}],
                          ids=lambda e: "+".join(f"{k[3:]}={v}" for k, v in e.items()) or "default")
 def test_device_merge_in_parts(env, monkeypatch):
-    """The merger on the device (sx_stage_b.cpp device_merge): several missions with many findings each, their output held
+    """The merger on the device (sx_merge.cpp device_merge): several missions with many findings each, their output held
     back on the device (SX_DEFER_MIN_BYTES) or already copied, interleaved in one part or in many (one result segment each);
     SX_SEQ_PIECE_KIB: the buffer in pieces scanned one after the other, a piece's findings copied while the next piece is
     scanned (scan_common's sequential pieces, as for a buffer whose output is gigabytes)."""

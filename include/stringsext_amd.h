@@ -780,6 +780,43 @@ void sx_labels_free(sx_labels* labels);
 int  sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels,
                                     uint64_t any, uint64_t all, uint64_t none, sx_result** out);
 
+/* The DUPLICATE STRINGS of a result whose segments ALL lie in HBM: `sort -u` / `uniq -c` / `uniq -d` / `uniq -u` over the findings'
+ * strings in the result's own order, decided on the device where the findings lie (csrc/sx_distinct_dev.hip) without a sort, as
+ * labels that sx_result_select_labels_device takes.
+ * THE RULE.  Two findings of r are EQUAL iff their strings — arena[str_off, str_off + str_len), the UTF-8 the result holds — are byte
+ * for byte equal; with flags = SX_SELECT_ASCII_NOCASE iff they are equal after 'A'..'Z' became 'a'..'z' (no other byte is folded).
+ * Equality is across Missions and across segments; position and metadata play no part; empty strings are equal to each other.  The
+ * ORDER is the result's print order — segment 0's records, then segment 1's, and so on.  *out (sx_labels_free) holds one 64-bit word
+ * per finding, laid out as sx_result_label_device lays its labels out (sx_labels_segments, sx_labels_segment_device):
+ *   bit 0  SX_DISTINCT_FIRST     no earlier finding of r is equal to this one
+ *   bit 1  SX_DISTINCT_REPEATED  some other finding of r is equal to this one
+ *   bits 32..63                  the number of findings of r equal to this one, itself included (word >> SX_DISTINCT_COUNT_SHIFT); it
+ *                                saturates at 2^32 - 1 and is the same in every member of a class
+ *   every other bit              0
+ * so that sx_result_select_labels_device(r, *out, any, all, none) gives: any = FIRST `sort -u` in the original order; none = FIRST the
+ * duplicates that were dropped; all = FIRST | REPEATED `uniq -d`; any = FIRST, none = REPEATED `uniq -u`; and `uniq -c` is the high
+ * half of the words that have bit 0.  *info (may be NULL): findings = the words written, distinct = the classes, repeated = the classes
+ * of two or more members, rounds and table_log2 = what the method below took.
+ * THE METHOD is a tournament by hash that is exact whatever the hash does (csrc/sx_distinct_core.hpp): per round every finding without
+ * a class hashes its string with the round's seed into a table of 2^table_log2 slots — the power of two >= 2 x findings —, the smallest
+ * key (segment << 32 | record) in a slot wins it, and whoever EQUALS its slot's winner, compared byte for byte, has found its class:
+ * equal strings share every slot, so a class is resolved as a whole, to its first member.  Every round resolves at least the winners'
+ * classes; the host reads one counter per round and stops at 0.  Words and counters are sums and minima: deterministic.
+ * The call reads r and never moves it, writes neither the result block nor a selection block and ages no selection: it is no selection.
+ * Its tables — 8 x 2^table_log2 + 16 x findings bytes — are memory of the context's that only this call uses, grown on demand and freed
+ * by sx_destroy; the labels are the caller's.  It returns when the kernels are done.  SX_E_INVALID: a NULL pointer (info may be), flags other than 0 or SX_SELECT_ASCII_NOCASE.
+ * SX_E_STATE: a host-only context; a result in host memory, or one whose device memory a later call has reused — as
+ * sx_result_label_device refuses them.  SX_E_NOMEM: the labels or the tables cannot be allocated.  *out is NULL on every error.
+ * Not built: classes per Mission, Unicode folding, the counts carried through a selection (they are in the labels of the source:
+ * distinct the selection again, or read the words), a sorted output, classes across several results or buffers. */
+enum { SX_DISTINCT_FIRST = 1u, SX_DISTINCT_REPEATED = 2u };
+#define SX_DISTINCT_COUNT_SHIFT 32
+typedef struct sx_distinct_info {
+    uint64_t findings, distinct, repeated;
+    uint32_t rounds, table_log2;
+} sx_distinct_info;
+int  sx_result_distinct_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_labels** out, sx_distinct_info* info);
+
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);
 

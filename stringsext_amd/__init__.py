@@ -25,6 +25,7 @@ SX_SELECT_REGEX_MAX_PATTERNS, SX_SELECT_REGEX_MAX_PATTERN_BYTES, SX_SELECT_REGEX
 SX_SELECT_REGEX_MAX_POSITIONS, SX_SELECT_REGEX_MAX_STATES = 65536, 65536
 SX_TALLY_NEVER = (1 << 64) - 1   # sx_tally_set_read: first[k] of a keyword without a hit
 SX_LABEL_NEVER = (1 << 64) - 1   # sx_label_set_read: first[p] of a pattern without a finding
+SX_DISTINCT_FIRST, SX_DISTINCT_REPEATED, SX_DISTINCT_COUNT_SHIFT = 1, 2, 32   # sx_result_distinct_device (Result.distinct_device): a word's bits
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -48,7 +49,7 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_result_extract_regex_device", "sx_tally_set_create", "sx_tally_set_info_get", "sx_tally_set_free", "sx_tally_set_reset",
            "sx_result_tally_device", "sx_tally_set_read", "sx_tally_set_counters_device",
            "sx_label_set_create", "sx_label_set_info_get", "sx_label_set_free", "sx_label_set_reset", "sx_label_set_read", "sx_label_set_counters_device",
-           "sx_result_label_device", "sx_labels_segment_device", "sx_labels_segments", "sx_labels_free", "sx_result_select_labels_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
+           "sx_result_label_device", "sx_labels_segment_device", "sx_labels_segments", "sx_labels_free", "sx_result_select_labels_device", "sx_result_distinct_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
 
@@ -203,6 +204,10 @@ class LabelSetInfo(C.Structure):   # sx_label_set_info
                 ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32), ("here_states", C.c_uint32)]
 
 
+class DistinctInfo(C.Structure):   # sx_distinct_info
+    _fields_ = [("findings", C.c_uint64), ("distinct", C.c_uint64), ("repeated", C.c_uint64), ("rounds", C.c_uint32), ("table_log2", C.c_uint32)]
+
+
 class Run(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("chars", C.c_uint64)]
 
@@ -306,6 +311,7 @@ def lib():
     L.sx_labels_segments.argtypes, L.sx_labels_segments.restype = [vp], u64
     L.sx_labels_free.argtypes, L.sx_labels_free.restype = [vp], None
     L.sx_result_select_labels_device.argtypes = [vp, vp, vp, u64, u64, u64, C.POINTER(vp)]
+    L.sx_result_distinct_device.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(DistinctInfo)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -519,6 +525,22 @@ class Result:
         self._s._chk(lib().sx_result_label_device(self._s.h, self.h, label_set.h, ordinal_base, C.byref(out)))
         return Labels(self._s, out)
 
+    def distinct_device(self, ignore_case=False):
+        """sx_result_distinct_device: WHICH findings of this Result repeat an earlier finding's string — Labels, one 64-bit word per
+        finding in HBM: bit 0 (SX_DISTINCT_FIRST) no earlier finding has the same string, bit 1 (SX_DISTINCT_REPEATED) another finding
+        has it, word >> SX_DISTINCT_COUNT_SHIFT how many have it.  select_device(labels, any=SX_DISTINCT_FIRST) is `sort -u` in the
+        original order, none=SX_DISTINCT_FIRST the duplicates, all=FIRST | REPEATED `uniq -d`, any=FIRST with none=REPEATED `uniq -u`.
+        ignore_case: 'A'..'Z' compare as 'a'..'z' (no other byte is folded).  The Labels' .info is sx_distinct_info as a dict:
+        findings, distinct, repeated, rounds, table_log2.  This Result is read, not moved, and no selection ages.  Raises SxError:
+        SX_E_STATE wherever printed_device() would refuse this Result."""
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        out, info = C.c_void_p(), DistinctInfo()
+        self._s._chk(lib().sx_result_distinct_device(self._s.h, self.h, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out), C.byref(info)))
+        labels = Labels(self._s, out)
+        labels.info = {k: getattr(info, k) for k, _ in DistinctInfo._fields_}
+        return labels
+
     def free(self):
         if self.h:
             lib().sx_result_free(self.h)
@@ -687,11 +709,12 @@ class LabelSet(_DeviceHandle):
 
 
 class Labels(_DeviceHandle):
-    """One Result's labels in HBM (sx_result_label_device; Result.label_device makes them): a 64-bit word per finding, an array per
-    segment of the Result.  Result.select_device() of the SAME Result takes them with the masks any, all, none.  They own their
+    """One Result's labels in HBM (sx_result_label_device; Result.label_device makes them — or sx_result_distinct_device,
+    Result.distinct_device, which also sets .info —): a 64-bit word per finding, an array per segment of the Result.  Result.select_device() of the SAME Result takes them with the masks any, all, none.  They own their
     device memory: free() them before or after the Scanner's close()."""
 
     _free, _freed = "sx_labels_free", "the Labels have been freed"
+    info = None      # distinct_device(): sx_distinct_info as a dict
 
     def __init__(self, scanner, handle):
         self._s, self.h = scanner, handle

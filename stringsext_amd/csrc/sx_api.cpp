@@ -405,6 +405,7 @@ void sx_destroy(sx_ctx* ctx) {
         for (uint8_t* p : ctx->d_select) if (p) (void)hipFree(p);
         if (ctx->d_select_scratch) (void)hipFree(ctx->d_select_scratch);
         if (ctx->d_select_scratch2) (void)hipFree(ctx->d_select_scratch2);
+        if (ctx->d_distinct) (void)hipFree(ctx->d_distinct);
         for (hipEvent_t e : ctx->merge_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ctx->slab_ev) if (e) (void)hipEventDestroy(e);
         if (ctx->ev_interleaved) (void)hipEventDestroy(ctx->ev_interleaved);

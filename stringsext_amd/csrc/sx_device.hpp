@@ -318,6 +318,12 @@ hipError_t seltally_launch(const SeltallyParams& P, hipStream_t stream);
 // labels and adds to the set's counters; nothing else is written, and both are valid once `stream` has got there
 struct LabelParams;
 hipError_t label_launch(const LabelParams& P, hipStream_t stream);
+// The duplicate strings on the device (sx_distinct_dev.hip, DistinctParams: sx_distinct_core.hpp), one phase of one segment per launch:
+// claim and resolve of a round — every segment's claim in front of any segment's resolve —, finalize behind the last round.  Only the
+// call's own tables and, in finalize, the segment's words are written
+struct DistinctParams;
+enum DistinctPhase { kDistinctClaim = 0, kDistinctResolve = 1, kDistinctFinalize = 2 };
+hipError_t distinct_launch(const DistinctParams& P, int phase, hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
 hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit

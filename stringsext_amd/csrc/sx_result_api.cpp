@@ -1,7 +1,7 @@
 // sx_result_api.cpp — the C-ABI of include/stringsext_amd.h for a result that stays in HBM (SX_OPT_RESULT_ON_DEVICE): the print, the
-// selections, the extraction, the tally and the labels, and the compiled sets they take.  What the operations share is here once — the
-// view of a segment, a set's upload, a handle's device and memory, the counters' reset, the two passes of whatever writes a new
-// result —; what tells them apart is in their lane functions (sx_*_core.hpp) and kernels (sx_*_dev.hip).
+// selections, the extraction, the tally, the labels and the duplicate strings, and the compiled sets they take.  What the operations
+// share is here once — the view of a segment, a set's upload, a handle's device and memory, the counters' reset, the two passes of
+// whatever writes a new result —; what tells them apart is in their lane functions (sx_*_core.hpp) and kernels (sx_*_dev.hip).
 #include "sx_ctx.hpp"
 #include "sx_print_core.hpp"
 #include "sx_select_core.hpp"
@@ -15,6 +15,7 @@
 #include "sx_seltally_core.hpp"
 #include "sx_label_build.hpp"
 #include "sx_label_core.hpp"
+#include "sx_distinct_core.hpp"
 
 using namespace sx;
 
@@ -731,6 +732,113 @@ int sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_lab
     sel.labels = labels;
     sel.masks[0] = any; sel.masks[1] = all; sel.masks[2] = none;
     return select_on_device(ctx, r, sel, out);
+}
+
+// The duplicate strings where the findings lie (sx_distinct_dev.hip): the source is checked as a whole, the words' memory is had as the
+// labels' is, then the call's own tables — [the segments][the counter and the totals][rep][count][the table], each 256-byte aligned, in
+// sx_ctx::d_distinct, which grows on demand and is no selection block —, then the rounds on the selections' stream: the table emptied,
+// every segment's claim, every segment's resolve, and one read of the counter, until it is 0; a round that does not lower it is an
+// error.  Then every segment's finalize and one read of the totals.  Only the words and the tables are written.
+int sx_result_distinct_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_labels** out, sx_distinct_info* info) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !out) return SX_E_INVALID;
+    if (flags & ~(uint32_t)SX_SELECT_ASCII_NOCASE) { ctx->set_err("distinct: flags other than SX_SELECT_ASCII_NOCASE"); return SX_E_INVALID; }
+    if (host_only(ctx, "distinct")) return SX_E_STATE;
+    { const int rc = result_on_device(ctx, r, "compare the strings on the host"); if (rc != SX_OK) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    const size_t n_segs = r->r.segs.size();
+    std::vector<DistinctSeg> segs;
+    uint64_t findings = 0, label_bytes = 0;
+    for (const MissionFindings& s : r->r.segs) {
+        const SegRef v = seg_ref(s);
+        if (v.n >> 32 || n_segs >> 31) { ctx->set_err("distinct: a segment of 2^32 findings or more"); return SX_E_INVALID; }
+        segs.push_back(DistinctSeg{ v.recs, v.arena, v.n, v.packed, 0u, findings });
+        findings += v.n;
+        label_bytes += up256(v.n * sizeof(uint64_t));
+    }
+    uint32_t table_log2 = 1;
+    if (ctx->sw.distinct_table_log2 >= 0) table_log2 = (uint32_t)ctx->sw.distinct_table_log2;
+    else while (((uint64_t)1 << table_log2) < 2 * findings) table_log2++;
+    sx_labels* lab = new (std::nothrow) sx_labels;
+    if (!lab) return SX_E_NOMEM;
+    lab->device = ctx->device;
+    const uint64_t at_words = up256(n_segs * sizeof(DistinctSeg)), at_rep = at_words + 256, at_count = at_rep + up256(findings * sizeof(uint64_t)),
+                   at_table = at_count + up256(findings * sizeof(uint64_t)), table_bytes = sizeof(uint64_t) << table_log2;
+    // (the tables: grown on demand, SX_E_NOMEM leaves them empty; then the words)
+    bool room = at_table + table_bytes <= ctx->d_distinct_cap;
+    if (!room) {
+        if (ctx->d_distinct) (void)hipFree(ctx->d_distinct);
+        ctx->d_distinct = nullptr; ctx->d_distinct_cap = 0;
+        room = hipMalloc((void**)&ctx->d_distinct, at_table + table_bytes) == hipSuccess;
+        if (room) ctx->d_distinct_cap = at_table + table_bytes;
+        else ctx->d_distinct = nullptr;
+    }
+    if (!room || hipMalloc((void**)&lab->mem, label_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        lab->mem = nullptr;
+        ctx->set_err("device distinct: no memory for " + std::to_string(label_bytes) + " bytes of words and " + std::to_string(at_table + table_bytes) + " bytes of tables");
+        sx_labels_free(lab);
+        return SX_E_NOMEM;
+    }
+    uint8_t* const tab = ctx->d_distinct;
+    DistinctParams base;
+    memset(&base, 0, sizeof base);
+    base.segs = (const DistinctSeg*)tab; base.n_segs = (uint32_t)n_segs; base.nocase = flags & SX_SELECT_ASCII_NOCASE ? 1u : 0u; base.table_log2 = table_log2;
+    base.unresolved = (uint64_t*)(tab + at_words); base.totals = base.unresolved + 1;
+    base.rep = (uint64_t*)(tab + at_rep); base.count = (uint64_t*)(tab + at_count); base.table = (uint64_t*)(tab + at_table);
+    uint64_t lab_at = 0;
+    for (const MissionFindings& s : r->r.segs) {
+        sx_labels::Seg seg;
+        seg.d = (const uint64_t*)(lab->mem + lab_at); seg.recs = s.dev_copy; seg.n = s.ext_nf; seg.epoch_ref = s.dev_epoch_ref; seg.epoch = s.dev_epoch;
+        lab->segs.push_back(seg);
+        lab_at += up256(s.ext_nf * sizeof(uint64_t));
+    }
+    // one phase over every segment, in order
+    auto phase = [&](int which, uint32_t round) {
+        for (size_t i = 0; i < n_segs; i++) {
+            DistinctParams p = base;
+            p.recs = segs[i].recs; p.arena = segs[i].arena; p.n = segs[i].n; p.packed = segs[i].packed; p.seg = (uint32_t)i; p.base = segs[i].base;
+            p.round = round; p.labels = (uint64_t*)lab->segs[i].d;
+            const hipError_t pe = distinct_launch(p, which, st);
+            if (pe != hipSuccess) return pe;
+        }
+        return hipSuccess;
+    };
+    hipError_t e = hipMemcpy(tab, segs.data(), n_segs * sizeof(DistinctSeg), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(tab + at_words, 0, 256, st);
+    if (e == hipSuccess) e = hipMemsetAsync(base.rep, 0xFF, findings * sizeof(uint64_t), st);          // (the top bit: no class yet)
+    if (e == hipSuccess) e = hipMemsetAsync(base.count, 0, findings * sizeof(uint64_t), st);
+    uint64_t left = findings, words[3] = { 0, 0, 0 };
+    uint32_t rounds = 0;
+    bool stuck = false;
+    while (e == hipSuccess && left != 0) {
+        const uint64_t before = left;
+        e = hipMemsetAsync(base.table, 0xFF, table_bytes, st);
+        if (e == hipSuccess) e = hipMemsetAsync(base.unresolved, 0, sizeof(uint64_t), st);
+        if (e == hipSuccess) e = phase(kDistinctClaim, rounds);
+        if (e == hipSuccess) e = phase(kDistinctResolve, rounds);
+        if (e == hipSuccess) e = hipMemcpyAsync(&left, base.unresolved, sizeof left, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+        rounds++;
+        if (ctx->sw.timing) fprintf(stderr, "[sx] distinct round %u: %llu of %llu findings left, 2^%u slots\n", rounds - 1, (unsigned long long)left, (unsigned long long)findings, table_log2);
+        if (left >= before) { stuck = true; break; }      // (every round resolves its winners' classes: this is an error, not a reason to go on)
+    }
+    if (e == hipSuccess && !stuck) e = phase(kDistinctFinalize, rounds);
+    if (e == hipSuccess && !stuck) e = hipMemcpyAsync(words, base.unresolved, sizeof words, hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess || stuck) {
+        (void)hipGetLastError();
+        sx_labels_free(lab);
+        ctx->set_err(stuck ? "device distinct: round " + std::to_string(rounds - 1) + " left " + std::to_string(left) + " findings without a class, no fewer than the round before"
+                           : std::string("device distinct: ") + hipGetErrorString(e));
+        return SX_E_HIP;
+    }
+    if (info) *info = sx_distinct_info{ findings, words[1], words[2], rounds, table_log2 };
+    *out = lab;
+    return SX_OK;
 }
 
 }  // extern "C"

@@ -79,6 +79,7 @@ Switches Switches::from_env() {
     s.wave_fail = present("SX_WAVE_FAIL");
     if (const char* e = getenv("SX_WAVE_REPAIR")) s.wave_repair = atoi(e) ? std::max(1, atoi(e)) : 0;
     s.wave_same = on_unless_0("SX_WAVE_SAME");
+    s.distinct_table_log2 = clamped_or("SX_DISTINCT_TABLE_LOG2", 0, 40, s.distinct_table_log2);
     if (const char* e = getenv("SX_SCAN_STREAM_MIB")) s.scan_stream_mib = (uint64_t)atoll(e);
     s.ingest_mmap = present("SX_INGEST_MMAP");
     return s;

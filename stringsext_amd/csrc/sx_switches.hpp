@@ -87,6 +87,8 @@ struct Switches {
     bool wave_fail = false;            // SX_WAVE_FAIL presence: the wave replay gives every buffer back (tests of the way back)
     int wave_repair = -1;              // SX_WAVE_REPAIR=0 / n: no repair launches / n at most (>= 1); -1 unset: 48 (tests)
     bool wave_same = true;             // SX_WAVE_SAME on / off: -r inside the wave kernels, Mission::wave_same (tests)
+    // ---- device-resident results (sx_result_api.cpp)
+    int distinct_table_log2 = -1;      // SX_DISTINCT_TABLE_LOG2=n (0 .. 40): sx_result_distinct_device's table has 2^n slots, 0 = one slot and a round per distinct string; -1 unset: the power of two >= 2 x findings (tests)
     // ---- ingest (sx_ingest.cpp)
     uint64_t scan_stream_mib = 0;      // SX_SCAN_STREAM_MIB=n: sx_scan of >= 2n MiB goes through the chunked ingest pipeline; 0: never (tests)
     bool ingest_mmap = false;          // SX_INGEST_MMAP presence: sx_scan_file maps the file instead of reading it (tests)

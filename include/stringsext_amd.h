@@ -808,7 +808,7 @@ int  sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_la
  * SX_E_STATE: a host-only context; a result in host memory, or one whose device memory a later call has reused — as
  * sx_result_label_device refuses them.  SX_E_NOMEM: the labels or the tables cannot be allocated.  *out is NULL on every error.
  * Not built: classes per Mission, Unicode folding, the counts carried through a selection (they are in the labels of the source:
- * distinct the selection again, or read the words), a sorted output, classes across several results or buffers. */
+ * distinct the selection again, or read the words), a sorted output.  (Classes across several results or buffers: the seen set below.) */
 enum { SX_DISTINCT_FIRST = 1u, SX_DISTINCT_REPEATED = 2u };
 #define SX_DISTINCT_COUNT_SHIFT 32
 typedef struct sx_distinct_info {
@@ -816,6 +816,61 @@ typedef struct sx_distinct_info {
     uint32_t rounds, table_log2;
 } sx_distinct_info;
 int  sx_result_distinct_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_labels** out, sx_distinct_info* info);
+
+/* The SEEN SET: strings remembered in HBM from one result to the next — every string once over a stream or a directory of files
+ * (`sort -u` of the whole run), and baseline subtraction or intersection (`comm`) against a known-good image —, on the device where
+ * the findings lie (csrc/sx_seen_dev.hip).
+ * sx_seen_set_create: an exact, open-addressed hash set of byte strings of FIXED capacity — capacity_strings strings whose entries
+ * take capacity_bytes at most, a string of len bytes taking SX_SEEN_ENTRY_BYTES(len) —, empty.  flags: 0, or SX_SELECT_ASCII_NOCASE:
+ * the fold is a property of the SET, which stores the folded bytes.  The table has the power of two >= 2 x capacity_strings slots (at
+ * least 2), so a probe always ends.  SX_E_INVALID: a NULL pointer, other flags, capacity_strings == 0, either capacity above 2^40.
+ * SX_E_STATE: a host-only context.  SX_E_NOMEM: no device memory for it.  *out = NULL on every error.  The set owns its device
+ * memory as a label set does: it may be freed before or after sx_destroy and used with any context on the same HIP device (another
+ * device: SX_E_INVALID).  sx_seen_set_info_get: strings and bytes = what it holds, the capacities, table_log2, nocase, tag_bits.
+ * sx_seen_set_reset: the set is empty again, its capacity is kept.
+ * sx_result_seen_device gives every finding of r the word sx_result_distinct_device(r, the set's fold) gives it PLUS ONE BIT:
+ *   bits 0, 1, 32..63            exactly sx_result_distinct_device's
+ *   bit 2  SX_DISTINCT_SEEN      the set held an equal string WHEN THE CALL BEGAN; the same in every member of a class
+ *   every other bit              0
+ * — equality is the distinct call's, byte for byte or after 'A'..'Z' became 'a'..'z' —, so that of sx_result_select_labels_device
+ * any = FIRST, none = SEEN is the stream's `sort -u` (every string new to the stream, once), none = SEEN baseline subtraction, and
+ * any = SEEN intersection.  *out is laid out as the distinct call's.  Then, unless flags = SX_SEEN_LOOKUP_ONLY, the call ADDS: after
+ * it the set holds (what it held) united with (the strings of r), each once.  *info (may be NULL): findings, distinct, repeated,
+ * rounds, table_log2 as sx_distinct_info; seen_findings = the words with SEEN, seen_distinct = the classes with SEEN;
+ * added_strings = the classes without SEEN and added_bytes = the sum of SX_SEEN_ENTRY_BYTES(len) over them — what the call put into
+ * the set, both 0 for a lookup-only call.
+ * CAPACITY is fixed.  If strings + added_strings > capacity_strings or bytes + added_bytes > capacity_bytes the call returns
+ * SX_E_NOMEM, sx_last_error names both sums, *out = NULL and THE SET IS UNCHANGED: the host decides it from the lookup's totals before
+ * anything is added.  A lookup-only call never fails for capacity.  Growth is not built: create a larger set.
+ * THE METHOD (csrc/sx_seen_core.hpp): behind the distinct pass a lookup pass — a lane per finding hashes its string, walks from its
+ * home slot, and compares with an entry only where the slot's tag equals its hash's — and, behind one read of its totals, an add pass
+ * in which only the first finding of a class the set did not hold acts: a wavefront takes its entries' room with one add, a lane
+ * writes its entry and takes the first empty slot from its home slot on by compare-and-swap.  No lane waits for another.
+ * Words, *info and the set's strings / bytes are deterministic; WHERE an entry lies in the set is not, and is no part of the contract.
+ * Sources, refusals and lifetime are exactly sx_result_distinct_device's — SX_E_STATE where that refuses —: r is read and never moved,
+ * no result or selection block is written, no selection ages.  SX_E_INVALID also: a NULL set, flags other than 0 or
+ * SX_SEEN_LOOKUP_ONLY, a set on another device.  Not thread-safe: one call per set at a time, and no reset or info during it.
+ * Not built: growth, removing strings, a count per stored string over the stream, dumping or loading a set, Unicode folding, sharded
+ * entry points, a host-memory source. */
+typedef struct sx_seen_set sx_seen_set;         /* the slots, the entries and their cursors, in HBM */
+enum { SX_DISTINCT_SEEN = 4u };                 /* bit 2 of a word made by sx_result_seen_device */
+#define SX_SEEN_LOOKUP_ONLY 0x100u              /* call flag: mark, add nothing */
+#define SX_SEEN_ENTRY_BYTES(len) (8u + (((uint64_t)(len) + 7u) & ~(uint64_t)7u))
+typedef struct sx_seen_set_info {
+    uint64_t strings, bytes, capacity_strings, capacity_bytes;
+    uint32_t table_log2, nocase, tag_bits, reserved;
+} sx_seen_set_info;
+typedef struct sx_seen_info {
+    uint64_t findings, distinct, repeated;      /* as sx_distinct_info */
+    uint64_t seen_findings, seen_distinct;      /* findings / classes with SX_DISTINCT_SEEN */
+    uint64_t added_strings, added_bytes;        /* what this call put into the set */
+    uint32_t rounds, table_log2;                /* as sx_distinct_info: the distinct pass's */
+} sx_seen_info;
+int  sx_seen_set_create(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capacity_bytes, uint32_t flags, sx_seen_set** out);
+int  sx_seen_set_info_get(const sx_seen_set* set, sx_seen_set_info* out);
+int  sx_seen_set_reset(sx_seen_set* set);
+void sx_seen_set_free(sx_seen_set* set);
+int  sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, uint32_t flags, sx_labels** out, sx_seen_info* info);
 
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);

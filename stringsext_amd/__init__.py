@@ -26,6 +26,7 @@ SX_SELECT_REGEX_MAX_POSITIONS, SX_SELECT_REGEX_MAX_STATES = 65536, 65536
 SX_TALLY_NEVER = (1 << 64) - 1   # sx_tally_set_read: first[k] of a keyword without a hit
 SX_LABEL_NEVER = (1 << 64) - 1   # sx_label_set_read: first[p] of a pattern without a finding
 SX_DISTINCT_FIRST, SX_DISTINCT_REPEATED, SX_DISTINCT_COUNT_SHIFT = 1, 2, 32   # sx_result_distinct_device (Result.distinct_device): a word's bits
+SX_DISTINCT_SEEN, SX_SEEN_LOOKUP_ONLY = 4, 0x100   # sx_result_seen_device (Result.seen_device): bit 2 of a word, and the call flag "mark, add nothing"
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -49,7 +50,8 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_result_extract_regex_device", "sx_tally_set_create", "sx_tally_set_info_get", "sx_tally_set_free", "sx_tally_set_reset",
            "sx_result_tally_device", "sx_tally_set_read", "sx_tally_set_counters_device",
            "sx_label_set_create", "sx_label_set_info_get", "sx_label_set_free", "sx_label_set_reset", "sx_label_set_read", "sx_label_set_counters_device",
-           "sx_result_label_device", "sx_labels_segment_device", "sx_labels_segments", "sx_labels_free", "sx_result_select_labels_device", "sx_result_distinct_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
+           "sx_result_label_device", "sx_labels_segment_device", "sx_labels_segments", "sx_labels_free", "sx_result_select_labels_device", "sx_result_distinct_device",
+           "sx_seen_set_create", "sx_seen_set_info_get", "sx_seen_set_reset", "sx_seen_set_free", "sx_result_seen_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
 
@@ -208,6 +210,16 @@ class DistinctInfo(C.Structure):   # sx_distinct_info
     _fields_ = [("findings", C.c_uint64), ("distinct", C.c_uint64), ("repeated", C.c_uint64), ("rounds", C.c_uint32), ("table_log2", C.c_uint32)]
 
 
+class SeenSetInfo(C.Structure):   # sx_seen_set_info
+    _fields_ = [("strings", C.c_uint64), ("bytes", C.c_uint64), ("capacity_strings", C.c_uint64), ("capacity_bytes", C.c_uint64),
+                ("table_log2", C.c_uint32), ("nocase", C.c_uint32), ("tag_bits", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SeenInfo(C.Structure):   # sx_seen_info
+    _fields_ = [("findings", C.c_uint64), ("distinct", C.c_uint64), ("repeated", C.c_uint64), ("seen_findings", C.c_uint64), ("seen_distinct", C.c_uint64),
+                ("added_strings", C.c_uint64), ("added_bytes", C.c_uint64), ("rounds", C.c_uint32), ("table_log2", C.c_uint32)]
+
+
 class Run(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("chars", C.c_uint64)]
 
@@ -312,6 +324,11 @@ def lib():
     L.sx_labels_free.argtypes, L.sx_labels_free.restype = [vp], None
     L.sx_result_select_labels_device.argtypes = [vp, vp, vp, u64, u64, u64, C.POINTER(vp)]
     L.sx_result_distinct_device.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(DistinctInfo)]
+    L.sx_seen_set_create.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(vp)]
+    L.sx_seen_set_info_get.argtypes = [vp, C.POINTER(SeenSetInfo)]
+    L.sx_seen_set_reset.argtypes = [vp]
+    L.sx_seen_set_free.argtypes, L.sx_seen_set_free.restype = [vp], None
+    L.sx_result_seen_device.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(SeenInfo)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -541,6 +558,25 @@ class Result:
         labels.info = {k: getattr(info, k) for k, _ in DistinctInfo._fields_}
         return labels
 
+    def seen_device(self, seen_set, add=True):
+        """sx_result_seen_device: the words of distinct_device() under the fold of `seen_set` (a SeenSet: Scanner.seen_set) plus bit 2
+        (SX_DISTINCT_SEEN): the set held an equal string when the call began.  select_device(labels, any=SX_DISTINCT_FIRST,
+        none=SX_DISTINCT_SEEN) is every string new to the stream, once; none=SX_DISTINCT_SEEN baseline subtraction; any=SX_DISTINCT_SEEN
+        intersection.  add: afterwards the set also holds this Result's strings, each once (False: SX_SEEN_LOOKUP_ONLY, the set is
+        only read).  The Labels' .info is sx_seen_info as a dict: findings, distinct, repeated, seen_findings, seen_distinct,
+        added_strings, added_bytes, rounds, table_log2.  This Result is read, not moved, and no selection ages.  Raises SxError:
+        SX_E_STATE wherever distinct_device() would refuse this Result, SX_E_NOMEM if what is new does not fit the set (which is then
+        as it was), SX_E_INVALID for a freed set."""
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        if not isinstance(seen_set, SeenSet) or not seen_set.h:
+            raise SxError(SX_E_INVALID, "the SeenSet has been freed" if isinstance(seen_set, SeenSet) else "seen_device takes a SeenSet")
+        out, info = C.c_void_p(), SeenInfo()
+        self._s._chk(lib().sx_result_seen_device(self._s.h, self.h, seen_set.h, 0 if add else SX_SEEN_LOOKUP_ONLY, C.byref(out), C.byref(info)))
+        labels = Labels(self._s, out)
+        labels.info = {k: getattr(info, k) for k, _ in SeenInfo._fields_}
+        return labels
+
     def free(self):
         if self.h:
             lib().sx_result_free(self.h)
@@ -708,13 +744,31 @@ class LabelSet(_DeviceHandle):
         return f.value, m.value
 
 
+class SeenSet(_DeviceHandle):
+    """Strings remembered in HBM from one Result to the next (sx_seen_set_create; Scanner.seen_set makes it): Result.seen_device() says
+    which findings' strings it held and adds the others, on result after result.  Its capacity is fixed.  It owns its device memory:
+    free() it before or after the Scanner's close()."""
+
+    _free, _info_get, _info_type = "sx_seen_set_free", "sx_seen_set_info_get", SeenSetInfo
+
+    def info(self):
+        """sx_seen_set_info as a dict: strings, bytes (what it holds), capacity_strings, capacity_bytes, table_log2, nocase, tag_bits"""
+        return self._info_dict()
+
+    def reset(self):
+        """the set is empty again; its capacity is kept"""
+        rc = lib().sx_seen_set_reset(self._handle())
+        if rc != SX_OK:
+            raise SxError(rc, "sx_seen_set_reset")
+
+
 class Labels(_DeviceHandle):
     """One Result's labels in HBM (sx_result_label_device; Result.label_device makes them — or sx_result_distinct_device,
     Result.distinct_device, which also sets .info —): a 64-bit word per finding, an array per segment of the Result.  Result.select_device() of the SAME Result takes them with the masks any, all, none.  They own their
     device memory: free() them before or after the Scanner's close()."""
 
     _free, _freed = "sx_labels_free", "the Labels have been freed"
-    info = None      # distinct_device(): sx_distinct_info as a dict
+    info = None      # distinct_device(): sx_distinct_info as a dict; seen_device(): sx_seen_info
 
     def __init__(self, scanner, handle):
         self._s, self.h = scanner, handle
@@ -816,6 +870,14 @@ class Scanner:
         out = C.c_void_p()
         self._chk(lib().sx_label_set_create(self.h, arr, n, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
         return LabelSet(out, n)
+
+    def seen_set(self, capacity_strings, capacity_bytes, ignore_case=False):
+        """sx_seen_set_create: an empty SeenSet for capacity_strings strings whose entries take capacity_bytes at most — a string of
+        n bytes takes 8 + n rounded up to a multiple of 8 —; ignore_case: the set folds 'A'..'Z' to 'a'..'z', and so does every
+        Result.seen_device() call that takes it."""
+        out = C.c_void_p()
+        self._chk(lib().sx_seen_set_create(self.h, capacity_strings, capacity_bytes, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        return SeenSet(out)
 
     def scan(self, data, file_id=-1, is_last=False):
         """sx_scan: replaces the loop src/main.rs:153-168 for one chunk held in host memory."""

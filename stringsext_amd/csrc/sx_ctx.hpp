@@ -210,7 +210,7 @@ struct sx_ctx {
     uint64_t select_calls = 0;
     uint8_t* d_select_scratch = nullptr; uint64_t d_select_scratch_cap = 0;
     uint8_t* d_select_scratch2 = nullptr; uint64_t d_select_scratch2_cap = 0;
-    // sx_result_distinct_device: the call's tables (the segments, the counters, rep, count, the slots), grown on demand and reused; no
+    // sx_result_distinct_device, and the distinct pass of sx_result_seen_device: the call's tables (the segments, the counters, rep, count, the slots), grown on demand and reused; no
     // result and no selection lies here
     uint8_t* d_distinct = nullptr; uint64_t d_distinct_cap = 0;
     bool merge_async = false;                           // device_merge returns with its last copies in flight; merge_drain() waits

@@ -324,6 +324,12 @@ hipError_t label_launch(const LabelParams& P, hipStream_t stream);
 struct DistinctParams;
 enum DistinctPhase { kDistinctClaim = 0, kDistinctResolve = 1, kDistinctFinalize = 2 };
 hipError_t distinct_launch(const DistinctParams& P, int phase, hipStream_t stream);
+// The seen set on the device (sx_seen_dev.hip, SeenParams: sx_seen_core.hpp), one pass of one segment per launch, behind distinct's
+// finalize: mark writes the segment's words and adds to the call's totals, and reads the set; add — behind every segment's mark, once
+// the host has seen that what is new fits — writes the set's entries, slots and cursors, and nothing else
+struct SeenParams;
+enum SeenPhase { kSeenMark = 0, kSeenAdd = 1 };
+hipError_t seen_launch(const SeenParams& P, int phase, hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
 hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit

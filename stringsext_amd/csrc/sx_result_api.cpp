@@ -1,5 +1,5 @@
 // sx_result_api.cpp — the C-ABI of include/stringsext_amd.h for a result that stays in HBM (SX_OPT_RESULT_ON_DEVICE): the print, the
-// selections, the extraction, the tally, the labels and the duplicate strings, and the compiled sets they take.  What the operations
+// selections, the extraction, the tally, the labels, the duplicate strings and the seen set, and the compiled sets they take.  What the operations
 // share is here once — the view of a segment, a set's upload, a handle's device and memory, the counters' reset, the two passes of
 // whatever writes a new result —; what tells them apart is in their lane functions (sx_*_core.hpp) and kernels (sx_*_dev.hip).
 #include "sx_ctx.hpp"
@@ -16,6 +16,7 @@
 #include "sx_label_build.hpp"
 #include "sx_label_core.hpp"
 #include "sx_distinct_core.hpp"
+#include "sx_seen_core.hpp"
 
 using namespace sx;
 
@@ -71,7 +72,16 @@ struct sx_labels : sx_device_handle {
     std::vector<Seg> segs;
 };
 
+// sx_seen_set_create: strings remembered from result to result; `mem` = [the cursors and a call's totals: kSeenHeadBytes][the slots]
+// [the entries], each 256-byte aligned.  info's strings and bytes are not kept here: the cursors say
+struct sx_seen_set : sx_device_handle {
+    SeenSet dev{};
+    sx_seen_set_info info{};
+};
+
 namespace {
+
+constexpr uint64_t kSeenHeadBytes = 256, kSeenMaxCapacity = (uint64_t)1 << 40;
 
 // A segment where it lies in HBM: what every kernel's parameters begin with
 struct SegRef {
@@ -315,6 +325,116 @@ int select_on_device(sx_ctx* ctx, const sx_result* r, TwoPass& pass, sx_result**
     *out = res.release();
     return SX_OK;
 }
+
+// The duplicate strings where the findings lie (sx_distinct_dev.hip): the source is checked as a whole, the words' memory is had as the
+// labels' is, then the call's own tables — [the segments][the counter and the totals][rep][count][the table], each 256-byte aligned, in
+// sx_ctx::d_distinct, which grows on demand and is no selection block —, then the rounds on the selections' stream: the table emptied,
+// every segment's claim, every segment's resolve, and one read of the counter, until it is 0; a round that does not lower it is an
+// error.  Then every segment's finalize and one read of the totals.  Only the words and the tables are written.
+// This is the body of sx_result_distinct_device and the first part of sx_result_seen_device, whose arguments are checked (what:
+// "distinct", "seen" — the call's name in the messages; nocase: 0 / 1).  *segs_out (may be NULL): the segments as the kernels took them.
+int distinct_on_device(sx_ctx* ctx, const sx_result* r, uint32_t nocase, const char* what, sx_labels** out, sx_distinct_info* info,
+                       std::vector<DistinctSeg>* segs_out) {
+    *out = nullptr;
+    if (host_only(ctx, what)) return SX_E_STATE;
+    { const int rc = result_on_device(ctx, r, "compare the strings on the host"); if (rc != SX_OK) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    const size_t n_segs = r->r.segs.size();
+    std::vector<DistinctSeg> segs;
+    uint64_t findings = 0, label_bytes = 0;
+    for (const MissionFindings& s : r->r.segs) {
+        const SegRef v = seg_ref(s);
+        if (v.n >> 32 || n_segs >> 31) { ctx->set_err(std::string(what) + ": a segment of 2^32 findings or more"); return SX_E_INVALID; }
+        segs.push_back(DistinctSeg{ v.recs, v.arena, v.n, v.packed, 0u, findings });
+        findings += v.n;
+        label_bytes += up256(v.n * sizeof(uint64_t));
+    }
+    uint32_t table_log2 = 1;
+    if (ctx->sw.distinct_table_log2 >= 0) table_log2 = (uint32_t)ctx->sw.distinct_table_log2;
+    else while (((uint64_t)1 << table_log2) < 2 * findings) table_log2++;
+    sx_labels* lab = new (std::nothrow) sx_labels;
+    if (!lab) return SX_E_NOMEM;
+    lab->device = ctx->device;
+    const uint64_t at_words = up256(n_segs * sizeof(DistinctSeg)), at_rep = at_words + 256, at_count = at_rep + up256(findings * sizeof(uint64_t)),
+                   at_table = at_count + up256(findings * sizeof(uint64_t)), table_bytes = sizeof(uint64_t) << table_log2;
+    // (the tables: grown on demand, SX_E_NOMEM leaves them empty; then the words)
+    bool room = at_table + table_bytes <= ctx->d_distinct_cap;
+    if (!room) {
+        if (ctx->d_distinct) (void)hipFree(ctx->d_distinct);
+        ctx->d_distinct = nullptr; ctx->d_distinct_cap = 0;
+        room = hipMalloc((void**)&ctx->d_distinct, at_table + table_bytes) == hipSuccess;
+        if (room) ctx->d_distinct_cap = at_table + table_bytes;
+        else ctx->d_distinct = nullptr;
+    }
+    if (!room || hipMalloc((void**)&lab->mem, label_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        lab->mem = nullptr;
+        ctx->set_err("device distinct: no memory for " + std::to_string(label_bytes) + " bytes of words and " + std::to_string(at_table + table_bytes) + " bytes of tables");
+        sx_labels_free(lab);
+        return SX_E_NOMEM;
+    }
+    uint8_t* const tab = ctx->d_distinct;
+    DistinctParams base;
+    memset(&base, 0, sizeof base);
+    base.segs = (const DistinctSeg*)tab; base.n_segs = (uint32_t)n_segs; base.nocase = nocase; base.table_log2 = table_log2;
+    base.unresolved = (uint64_t*)(tab + at_words); base.totals = base.unresolved + 1;
+    base.rep = (uint64_t*)(tab + at_rep); base.count = (uint64_t*)(tab + at_count); base.table = (uint64_t*)(tab + at_table);
+    uint64_t lab_at = 0;
+    for (const MissionFindings& s : r->r.segs) {
+        sx_labels::Seg seg;
+        seg.d = (const uint64_t*)(lab->mem + lab_at); seg.recs = s.dev_copy; seg.n = s.ext_nf; seg.epoch_ref = s.dev_epoch_ref; seg.epoch = s.dev_epoch;
+        lab->segs.push_back(seg);
+        lab_at += up256(s.ext_nf * sizeof(uint64_t));
+    }
+    // one phase over every segment, in order
+    auto phase = [&](int which, uint32_t round) {
+        for (size_t i = 0; i < n_segs; i++) {
+            DistinctParams p = base;
+            p.recs = segs[i].recs; p.arena = segs[i].arena; p.n = segs[i].n; p.packed = segs[i].packed; p.seg = (uint32_t)i; p.base = segs[i].base;
+            p.round = round; p.labels = (uint64_t*)lab->segs[i].d;
+            const hipError_t pe = distinct_launch(p, which, st);
+            if (pe != hipSuccess) return pe;
+        }
+        return hipSuccess;
+    };
+    hipError_t e = hipMemcpy(tab, segs.data(), n_segs * sizeof(DistinctSeg), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(tab + at_words, 0, 256, st);
+    if (e == hipSuccess) e = hipMemsetAsync(base.rep, 0xFF, findings * sizeof(uint64_t), st);          // (the top bit: no class yet)
+    if (e == hipSuccess) e = hipMemsetAsync(base.count, 0, findings * sizeof(uint64_t), st);
+    uint64_t left = findings, words[3] = { 0, 0, 0 };
+    uint32_t rounds = 0;
+    bool stuck = false;
+    while (e == hipSuccess && left != 0) {
+        const uint64_t before = left;
+        e = hipMemsetAsync(base.table, 0xFF, table_bytes, st);
+        if (e == hipSuccess) e = hipMemsetAsync(base.unresolved, 0, sizeof(uint64_t), st);
+        if (e == hipSuccess) e = phase(kDistinctClaim, rounds);
+        if (e == hipSuccess) e = phase(kDistinctResolve, rounds);
+        if (e == hipSuccess) e = hipMemcpyAsync(&left, base.unresolved, sizeof left, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+        rounds++;
+        if (ctx->sw.timing) fprintf(stderr, "[sx] distinct round %u: %llu of %llu findings left, 2^%u slots\n", rounds - 1, (unsigned long long)left, (unsigned long long)findings, table_log2);
+        if (left >= before) { stuck = true; break; }      // (every round resolves its winners' classes: this is an error, not a reason to go on)
+    }
+    if (e == hipSuccess && !stuck) e = phase(kDistinctFinalize, rounds);
+    if (e == hipSuccess && !stuck) e = hipMemcpyAsync(words, base.unresolved, sizeof words, hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess || stuck) {
+        (void)hipGetLastError();
+        sx_labels_free(lab);
+        ctx->set_err(stuck ? "device distinct: round " + std::to_string(rounds - 1) + " left " + std::to_string(left) + " findings without a class, no fewer than the round before"
+                           : std::string("device distinct: ") + hipGetErrorString(e));
+        return SX_E_HIP;
+    }
+    if (info) *info = sx_distinct_info{ findings, words[1], words[2], rounds, table_log2 };
+    if (segs_out) *segs_out = std::move(segs);
+    *out = lab;
+    return SX_OK;
+}
+
 
 }  // namespace
 
@@ -734,109 +854,117 @@ int sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_lab
     return select_on_device(ctx, r, sel, out);
 }
 
-// The duplicate strings where the findings lie (sx_distinct_dev.hip): the source is checked as a whole, the words' memory is had as the
-// labels' is, then the call's own tables — [the segments][the counter and the totals][rep][count][the table], each 256-byte aligned, in
-// sx_ctx::d_distinct, which grows on demand and is no selection block —, then the rounds on the selections' stream: the table emptied,
-// every segment's claim, every segment's resolve, and one read of the counter, until it is 0; a round that does not lower it is an
-// error.  Then every segment's finalize and one read of the totals.  Only the words and the tables are written.
 int sx_result_distinct_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_labels** out, sx_distinct_info* info) {
     if (out) *out = nullptr;
     if (!ctx || !r || !out) return SX_E_INVALID;
     if (flags & ~(uint32_t)SX_SELECT_ASCII_NOCASE) { ctx->set_err("distinct: flags other than SX_SELECT_ASCII_NOCASE"); return SX_E_INVALID; }
-    if (host_only(ctx, "distinct")) return SX_E_STATE;
-    { const int rc = result_on_device(ctx, r, "compare the strings on the host"); if (rc != SX_OK) return rc; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->post_stream;
-    const size_t n_segs = r->r.segs.size();
-    std::vector<DistinctSeg> segs;
-    uint64_t findings = 0, label_bytes = 0;
-    for (const MissionFindings& s : r->r.segs) {
-        const SegRef v = seg_ref(s);
-        if (v.n >> 32 || n_segs >> 31) { ctx->set_err("distinct: a segment of 2^32 findings or more"); return SX_E_INVALID; }
-        segs.push_back(DistinctSeg{ v.recs, v.arena, v.n, v.packed, 0u, findings });
-        findings += v.n;
-        label_bytes += up256(v.n * sizeof(uint64_t));
+    return distinct_on_device(ctx, r, flags & SX_SELECT_ASCII_NOCASE ? 1u : 0u, "distinct", out, info, nullptr);
+}
+
+int sx_seen_set_reset(sx_seen_set* set) {
+    if (!set) return SX_E_INVALID;
+    if (hipSetDevice(set->device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    hipError_t e = hipMemset(set->mem, 0, kSeenHeadBytes);                                  // the cursors (and the totals of a call)
+    if (e == hipSuccess) e = hipMemset(set->dev.slots, 0xFF, sizeof(uint64_t) << set->dev.table_log2);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (as reset_counters: the kernels run on a stream that does not wait for this one)
+    if (e != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    return SX_OK;
+}
+
+int sx_seen_set_create(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capacity_bytes, uint32_t flags, sx_seen_set** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out) return SX_E_INVALID;
+    if (flags & ~(uint32_t)SX_SELECT_ASCII_NOCASE) { ctx->set_err("seen set: flags other than SX_SELECT_ASCII_NOCASE"); return SX_E_INVALID; }
+    if (capacity_strings == 0 || capacity_strings > kSeenMaxCapacity || capacity_bytes > kSeenMaxCapacity) {
+        ctx->set_err("seen set: a capacity of " + std::to_string(capacity_strings) + " strings and " + std::to_string(capacity_bytes) + " bytes: at least one string, 2^40 of either at most");
+        return SX_E_INVALID;
     }
+    if (host_only(ctx, "for the seen set")) return SX_E_STATE;
     uint32_t table_log2 = 1;
-    if (ctx->sw.distinct_table_log2 >= 0) table_log2 = (uint32_t)ctx->sw.distinct_table_log2;
-    else while (((uint64_t)1 << table_log2) < 2 * findings) table_log2++;
-    sx_labels* lab = new (std::nothrow) sx_labels;
-    if (!lab) return SX_E_NOMEM;
-    lab->device = ctx->device;
-    const uint64_t at_words = up256(n_segs * sizeof(DistinctSeg)), at_rep = at_words + 256, at_count = at_rep + up256(findings * sizeof(uint64_t)),
-                   at_table = at_count + up256(findings * sizeof(uint64_t)), table_bytes = sizeof(uint64_t) << table_log2;
-    // (the tables: grown on demand, SX_E_NOMEM leaves them empty; then the words)
-    bool room = at_table + table_bytes <= ctx->d_distinct_cap;
-    if (!room) {
-        if (ctx->d_distinct) (void)hipFree(ctx->d_distinct);
-        ctx->d_distinct = nullptr; ctx->d_distinct_cap = 0;
-        room = hipMalloc((void**)&ctx->d_distinct, at_table + table_bytes) == hipSuccess;
-        if (room) ctx->d_distinct_cap = at_table + table_bytes;
-        else ctx->d_distinct = nullptr;
-    }
-    if (!room || hipMalloc((void**)&lab->mem, label_bytes) != hipSuccess) {
+    while (((uint64_t)1 << table_log2) < 2 * capacity_strings) table_log2++;
+    const uint64_t table_bytes = sizeof(uint64_t) << table_log2, at_arena = kSeenHeadBytes + up256(table_bytes), bytes = at_arena + up256(capacity_bytes ? capacity_bytes : 1);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint8_t* mem = nullptr;
+    if (hipMalloc((void**)&mem, bytes) != hipSuccess) {
         (void)hipGetLastError();
-        lab->mem = nullptr;
-        ctx->set_err("device distinct: no memory for " + std::to_string(label_bytes) + " bytes of words and " + std::to_string(at_table + table_bytes) + " bytes of tables");
-        sx_labels_free(lab);
+        ctx->set_err("seen set: no device memory for " + std::to_string(bytes) + " bytes of slots and entries");
         return SX_E_NOMEM;
     }
-    uint8_t* const tab = ctx->d_distinct;
-    DistinctParams base;
-    memset(&base, 0, sizeof base);
-    base.segs = (const DistinctSeg*)tab; base.n_segs = (uint32_t)n_segs; base.nocase = flags & SX_SELECT_ASCII_NOCASE ? 1u : 0u; base.table_log2 = table_log2;
-    base.unresolved = (uint64_t*)(tab + at_words); base.totals = base.unresolved + 1;
-    base.rep = (uint64_t*)(tab + at_rep); base.count = (uint64_t*)(tab + at_count); base.table = (uint64_t*)(tab + at_table);
-    uint64_t lab_at = 0;
-    for (const MissionFindings& s : r->r.segs) {
-        sx_labels::Seg seg;
-        seg.d = (const uint64_t*)(lab->mem + lab_at); seg.recs = s.dev_copy; seg.n = s.ext_nf; seg.epoch_ref = s.dev_epoch_ref; seg.epoch = s.dev_epoch;
-        lab->segs.push_back(seg);
-        lab_at += up256(s.ext_nf * sizeof(uint64_t));
-    }
-    // one phase over every segment, in order
-    auto phase = [&](int which, uint32_t round) {
-        for (size_t i = 0; i < n_segs; i++) {
-            DistinctParams p = base;
-            p.recs = segs[i].recs; p.arena = segs[i].arena; p.n = segs[i].n; p.packed = segs[i].packed; p.seg = (uint32_t)i; p.base = segs[i].base;
-            p.round = round; p.labels = (uint64_t*)lab->segs[i].d;
-            const hipError_t pe = distinct_launch(p, which, st);
+    sx_seen_set* set = new_handle<sx_seen_set>(ctx, mem);
+    if (!set) return SX_E_NOMEM;
+    set->dev = SeenSet{ (uint64_t*)(mem + kSeenHeadBytes), mem + at_arena, (uint64_t*)mem, table_log2, (uint32_t)ctx->sw.seen_tag_bits, flags & SX_SELECT_ASCII_NOCASE ? 1u : 0u, 0u };
+    set->info = sx_seen_set_info{ 0, 0, capacity_strings, capacity_bytes, table_log2, set->dev.nocase, set->dev.tag_bits, 0 };
+    if (sx_seen_set_reset(set) != SX_OK) { ctx->set_err("seen set: the slots could not be emptied"); sx_seen_set_free(set); return SX_E_HIP; }
+    *out = set;
+    return SX_OK;
+}
+
+// (strings and bytes are the cursors, read where they lie)
+int sx_seen_set_info_get(const sx_seen_set* set, sx_seen_set_info* out) {
+    if (!set || !out) return SX_E_INVALID;
+    uint64_t cursors[2];
+    { const int rc = read_counters(set->device, set->dev.cursors, cursors, 2); if (rc != SX_OK) return rc; }
+    *out = set->info;
+    out->strings = cursors[0]; out->bytes = cursors[1];
+    return SX_OK;
+}
+void sx_seen_set_free(sx_seen_set* set) { handle_free(set); }
+
+// The seen set where the findings lie (sx_seen_dev.hip): the distinct pass under the set's fold, as sx_result_distinct_device runs it;
+// then, on the selections' stream, the totals zeroed, every segment's mark, and ONE read — the set's cursors and the call's totals,
+// which lie side by side —; the host decides whether what is new fits; then every segment's add and one wait.  A refusal for capacity
+// comes before the add pass: the set is as it was.
+int sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, uint32_t flags, sx_labels** out, sx_seen_info* info) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !set || !out) return SX_E_INVALID;
+    if (flags & ~(uint32_t)SX_SEEN_LOOKUP_ONLY) { ctx->set_err("seen: flags other than SX_SEEN_LOOKUP_ONLY"); return SX_E_INVALID; }
+    if (host_only(ctx, "seen")) return SX_E_STATE;
+    if (on_another_device(ctx, *set, "the seen set lies")) return SX_E_INVALID;
+    sx_labels* lab = nullptr;
+    sx_distinct_info di{};
+    std::vector<DistinctSeg> segs;
+    { const int rc = distinct_on_device(ctx, r, set->dev.nocase, "seen", &lab, &di, &segs); if (rc != SX_OK) return rc; }
+    hipStream_t st = ctx->post_stream;
+    uint64_t* const totals = set->dev.cursors + 2;
+    auto pass = [&](int which) {
+        for (size_t i = 0; i < segs.size(); i++) {
+            SeenParams p;
+            memset(&p, 0, sizeof p);
+            p.recs = segs[i].recs; p.arena = segs[i].arena; p.n = segs[i].n; p.packed = segs[i].packed;
+            p.labels = (uint64_t*)lab->segs[i].d; p.totals = totals; p.set = set->dev;
+            const hipError_t pe = seen_launch(p, which, st);
             if (pe != hipSuccess) return pe;
         }
         return hipSuccess;
     };
-    hipError_t e = hipMemcpy(tab, segs.data(), n_segs * sizeof(DistinctSeg), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(tab + at_words, 0, 256, st);
-    if (e == hipSuccess) e = hipMemsetAsync(base.rep, 0xFF, findings * sizeof(uint64_t), st);          // (the top bit: no class yet)
-    if (e == hipSuccess) e = hipMemsetAsync(base.count, 0, findings * sizeof(uint64_t), st);
-    uint64_t left = findings, words[3] = { 0, 0, 0 };
-    uint32_t rounds = 0;
-    bool stuck = false;
-    while (e == hipSuccess && left != 0) {
-        const uint64_t before = left;
-        e = hipMemsetAsync(base.table, 0xFF, table_bytes, st);
-        if (e == hipSuccess) e = hipMemsetAsync(base.unresolved, 0, sizeof(uint64_t), st);
-        if (e == hipSuccess) e = phase(kDistinctClaim, rounds);
-        if (e == hipSuccess) e = phase(kDistinctResolve, rounds);
-        if (e == hipSuccess) e = hipMemcpyAsync(&left, base.unresolved, sizeof left, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) break;
-        rounds++;
-        if (ctx->sw.timing) fprintf(stderr, "[sx] distinct round %u: %llu of %llu findings left, 2^%u slots\n", rounds - 1, (unsigned long long)left, (unsigned long long)findings, table_log2);
-        if (left >= before) { stuck = true; break; }      // (every round resolves its winners' classes: this is an error, not a reason to go on)
+    uint64_t words[2 + kSeenTotals] = { 0 };      // the cursors, the totals
+    hipError_t e = hipMemsetAsync(totals, 0, kSeenTotals * sizeof(uint64_t), st);
+    if (e == hipSuccess) e = pass(kSeenMark);
+    if (e == hipSuccess) e = hipMemcpyAsync(words, set->dev.cursors, sizeof words, hipMemcpyDeviceToHost, st);
+    { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
+    const uint64_t* const tot = words + 2;
+    const bool lost = e == hipSuccess && tot[kSeenError] != 0;
+    const bool add = !(flags & SX_SEEN_LOOKUP_ONLY);
+    const bool full = e == hipSuccess && !lost && add
+                      && (words[0] + tot[kSeenNewClasses] > set->info.capacity_strings || words[1] + tot[kSeenNewBytes] > set->info.capacity_bytes);
+    if (e == hipSuccess && !lost && !full && add && tot[kSeenNewClasses]) {
+        e = pass(kSeenAdd);
+        const hipError_t e2 = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = e2;
     }
-    if (e == hipSuccess && !stuck) e = phase(kDistinctFinalize, rounds);
-    if (e == hipSuccess && !stuck) e = hipMemcpyAsync(words, base.unresolved, sizeof words, hipMemcpyDeviceToHost, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess || stuck) {
+    if (e != hipSuccess || lost || full) {
         (void)hipGetLastError();
         sx_labels_free(lab);
-        ctx->set_err(stuck ? "device distinct: round " + std::to_string(rounds - 1) + " left " + std::to_string(left) + " findings without a class, no fewer than the round before"
-                           : std::string("device distinct: ") + hipGetErrorString(e));
-        return SX_E_HIP;
+        if (full)
+            ctx->set_err("seen set: " + std::to_string(words[0]) + " + " + std::to_string(tot[kSeenNewClasses]) + " strings of " + std::to_string(set->info.capacity_strings) + ", "
+                         + std::to_string(words[1]) + " + " + std::to_string(tot[kSeenNewBytes]) + " bytes of " + std::to_string(set->info.capacity_bytes) + ": the set is as it was, create a larger one");
+        else
+            ctx->set_err(lost ? std::string("device seen: a probe walked every slot of the set and met no empty one") : std::string("device seen: ") + hipGetErrorString(e));
+        return full ? SX_E_NOMEM : SX_E_HIP;
     }
-    if (info) *info = sx_distinct_info{ findings, words[1], words[2], rounds, table_log2 };
+    if (info)
+        *info = sx_seen_info{ di.findings, di.distinct, di.repeated, tot[kSeenFindings], tot[kSeenClasses], add ? tot[kSeenNewClasses] : 0u, add ? tot[kSeenNewBytes] : 0u,
+                              di.rounds, di.table_log2 };
     *out = lab;
     return SX_OK;
 }

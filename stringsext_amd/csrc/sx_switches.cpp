@@ -80,6 +80,7 @@ Switches Switches::from_env() {
     if (const char* e = getenv("SX_WAVE_REPAIR")) s.wave_repair = atoi(e) ? std::max(1, atoi(e)) : 0;
     s.wave_same = on_unless_0("SX_WAVE_SAME");
     s.distinct_table_log2 = clamped_or("SX_DISTINCT_TABLE_LOG2", 0, 40, s.distinct_table_log2);
+    s.seen_tag_bits = clamped_or("SX_SEEN_TAG_BITS", 0, 24, s.seen_tag_bits);
     if (const char* e = getenv("SX_SCAN_STREAM_MIB")) s.scan_stream_mib = (uint64_t)atoll(e);
     s.ingest_mmap = present("SX_INGEST_MMAP");
     return s;

@@ -89,6 +89,7 @@ struct Switches {
     bool wave_same = true;             // SX_WAVE_SAME on / off: -r inside the wave kernels, Mission::wave_same (tests)
     // ---- device-resident results (sx_result_api.cpp)
     int distinct_table_log2 = -1;      // SX_DISTINCT_TABLE_LOG2=n (0 .. 40): sx_result_distinct_device's table has 2^n slots, 0 = one slot and a round per distinct string; -1 unset: the power of two >= 2 x findings (tests)
+    int seen_tag_bits = 24;            // SX_SEEN_TAG_BITS=n (0 .. 24): the tag bits of a slot of a seen set made by this context (sx_seen_set_create), 0 = every occupied slot on a probe's way is compared byte for byte (tests)
     // ---- ingest (sx_ingest.cpp)
     uint64_t scan_stream_mib = 0;      // SX_SCAN_STREAM_MIB=n: sx_scan of >= 2n MiB goes through the chunked ingest pipeline; 0: never (tests)
     bool ingest_mmap = false;          // SX_INGEST_MMAP presence: sx_scan_file maps the file instead of reading it (tests)

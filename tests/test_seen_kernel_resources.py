@@ -1,0 +1,11 @@
+"""sx_result_seen_device, what the compiler made of stringsext_amd/csrc/sx_seen_dev.hip (no GPU needed): the per-kernel resource
+remarks the Makefile keeps next to the object."""
+from test_kernel_resources import remarks
+
+
+def test_the_two_seen_kernels_are_there_with_no_scratch_no_spills_and_no_lds():
+    rows = remarks("sx_seen_dev")
+    assert sorted(rows) == ["seen_add_kernel", "seen_mark_kernel"], sorted(rows)
+    for k, v in rows.items():
+        assert v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (k, v)
+        assert v["LDS Size [bytes/block]"] == 0, (k, v)                          # kSeenGroupsPerCu rests on it

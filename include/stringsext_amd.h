@@ -841,7 +841,7 @@ int  sx_result_distinct_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, 
  * the set, both 0 for a lookup-only call.
  * CAPACITY is fixed.  If strings + added_strings > capacity_strings or bytes + added_bytes > capacity_bytes the call returns
  * SX_E_NOMEM, sx_last_error names both sums, *out = NULL and THE SET IS UNCHANGED: the host decides it from the lookup's totals before
- * anything is added.  A lookup-only call never fails for capacity.  Growth is not built: create a larger set.
+ * anything is added.  A lookup-only call never fails for capacity.  sx_seen_set_grow (below) gives the set room and keeps what it holds.
  * THE METHOD (csrc/sx_seen_core.hpp): behind the distinct pass a lookup pass — a lane per finding hashes its string, walks from its
  * home slot, and compares with an entry only where the slot's tag equals its hash's — and, behind one read of its totals, an add pass
  * in which only the first finding of a class the set did not hold acts: a wavefront takes its entries' room with one add, a lane
@@ -850,8 +850,8 @@ int  sx_result_distinct_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, 
  * Sources, refusals and lifetime are exactly sx_result_distinct_device's — SX_E_STATE where that refuses —: r is read and never moved,
  * no result or selection block is written, no selection ages.  SX_E_INVALID also: a NULL set, flags other than 0 or
  * SX_SEEN_LOOKUP_ONLY, a set on another device.  Not thread-safe: one call per set at a time, and no reset or info during it.
- * Not built: growth, removing strings, a count per stored string over the stream, dumping or loading a set, Unicode folding, sharded
- * entry points, a host-memory source. */
+ * Not built: removing strings, a count per stored string over the stream, Unicode folding, sharded entry points.  (Growth, saving
+ * and loading a set, and a list of strings as the source: below.) */
 typedef struct sx_seen_set sx_seen_set;         /* the slots, the entries and their cursors, in HBM */
 enum { SX_DISTINCT_SEEN = 4u };                 /* bit 2 of a word made by sx_result_seen_device */
 #define SX_SEEN_LOOKUP_ONLY 0x100u              /* call flag: mark, add nothing */
@@ -871,6 +871,55 @@ int  sx_seen_set_info_get(const sx_seen_set* set, sx_seen_set_info* out);
 int  sx_seen_set_reset(sx_seen_set* set);
 void sx_seen_set_free(sx_seen_set* set);
 int  sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, uint32_t flags, sx_labels** out, sx_seen_info* info);
+
+/* A SEEN SET THAT OUTLIVES A CALL: merged with another, grown, saved and loaded, and fed from a list of strings.  All of it is one
+ * mechanism (csrc/sx_seen_merge_core.hpp, csrc/sx_seen_merge_dev.hip): a SOURCE of entries that already are a set — pairwise
+ * different, folded under the destination's fold — goes into a destination in two passes, a lane per source entry: a lookup pass
+ * that says per entry whether the destination held it and counts what is new, and, behind one read of the cursors and the counts, an
+ * add pass that copies the new entries and claims their slots.  Entries are hashed, compared and copied eight bytes at a time.  The
+ * source is another set's slot table as it lies (merge, grow) or a list the host built and uploaded (import, add_strings).
+ * sx_seen_set_merge: dst = dst united with src.  flags: 0, or SX_SEEN_LOOKUP_ONLY — count, add nothing: already_held is then the size
+ * of the intersection.  *info (may be NULL): source_strings = what src holds, already_held = those dst held when the call began,
+ * added_strings / added_bytes = what the call put into dst (0 for a lookup-only call).  SX_E_INVALID: a NULL pointer, other flags,
+ * sets of different folds, dst == src, a set on another device than the context's.  SX_E_NOMEM: strings + new > capacity_strings or
+ * bytes + new bytes > capacity_bytes — sx_last_error names both sums, and DST IS UNCHANGED —, or no device memory for the call's
+ * scratch (a bit per slot of src).  src is only read.
+ * sx_seen_set_grow: THE SAME HANDLE gets new capacities: new memory is allocated, the set's contents are merged into it — every entry
+ * is hashed again for the new table_log2 —, the handle takes the new memory and the old is freed.  The capacities may be smaller than
+ * they were as long as they hold what the set holds; otherwise, or with capacity_strings == 0 or either above 2^40, SX_E_INVALID
+ * before anything is allocated.  SX_E_NOMEM: no device memory for the new set; the set is as it was.  tag_bits stay the set's.
+ * THE BLOB: sx_seen_set_export_size says how many bytes sx_seen_set_export writes: a 64-byte little-endian header — the magic
+ * "SXSEEN\0\0", u32 version = 1, u32 nocase, u64 strings, u64 bytes, u64 FNV-1a-64 over the entry area, the rest 0 — and then the
+ * set's first `bytes` bytes of entries as they lie: [u32 len][u32 0][the (folded) bytes, zero-padded to 8] each.  cap < that size:
+ * SX_E_INVALID, nothing written.  Where entries lie depends on the order of the adds: two exports of equal sets may differ, the
+ * contract is the set of strings; two exports of a set that was not written in between are byte-identical.
+ * sx_seen_blob_info_get checks a blob completely, on the host and without a device or a context, and says what it holds.  It
+ * refuses (SX_E_INVALID) a wrong magic or version, len != 64 + bytes, bytes not a multiple of 8, nocase other than 0 / 1, an entry
+ * that overruns the area, a second u32 or padding that is not 0, an entry count other than `strings`, a checksum that does not match,
+ * two equal entries, and with nocase a byte 'A'..'Z': what the kernels rely on is checked before they run.
+ * sx_seen_set_import: a new set that holds the blob's strings, under the blob's fold and the CONTEXT's tag bits (SX_SEEN_TAG_BITS).
+ * A capacity of 0 = what the blob holds (at least one string); one smaller than the blob holds: SX_E_INVALID.  A blob that
+ * sx_seen_blob_info_get refuses: SX_E_INVALID, sx_last_error says why, nothing is allocated.  *out = NULL on every error.
+ * sx_seen_set_add_strings: n byte strings, string i = bytes[offsets[i], offsets[i + 1]), as a source.  The host folds them under the
+ * set's fold and keeps the first of every group of equal ones; source_strings counts those.  held_out (n bytes, may be NULL):
+ * held_out[i] = 1 iff the set held string i WHEN THE CALL BEGAN, per input string, duplicates alike.  With SX_SEEN_LOOKUP_ONLY this
+ * is `contains` for a list.  A string may be longer than a finding can be.  SX_E_INVALID also: n or offsets[n] above 2^32 - 1,
+ * offsets that decrease.  Capacity as sx_seen_set_merge.
+ * All of them but the two host-only blob calls refuse a host-only context (SX_E_STATE), age no selection and write no result or
+ * selection block; like every call on a set they are not thread-safe per set.
+ * Not built: removing strings, a count per stored string, canonical (sorted) blobs, Unicode folding, sharded entry points. */
+typedef struct sx_seen_merge_info { uint64_t source_strings, already_held, added_strings, added_bytes; } sx_seen_merge_info;
+typedef struct sx_seen_blob_info  { uint64_t strings, bytes; uint32_t nocase, version; } sx_seen_blob_info;
+#define SX_SEEN_BLOB_HEADER_BYTES 64u
+#define SX_SEEN_BLOB_VERSION 1u
+int  sx_seen_set_merge(sx_ctx* ctx, sx_seen_set* dst, const sx_seen_set* src, uint32_t flags, sx_seen_merge_info* info);
+int  sx_seen_set_grow(sx_ctx* ctx, sx_seen_set* set, uint64_t capacity_strings, uint64_t capacity_bytes);
+int  sx_seen_set_export_size(const sx_seen_set* set, uint64_t* bytes);
+int  sx_seen_set_export(const sx_seen_set* set, void* buf, uint64_t cap, uint64_t* written);
+int  sx_seen_blob_info_get(const void* blob, uint64_t len, sx_seen_blob_info* out);
+int  sx_seen_set_import(sx_ctx* ctx, const void* blob, uint64_t len, uint64_t capacity_strings, uint64_t capacity_bytes, sx_seen_set** out);
+int  sx_seen_set_add_strings(sx_ctx* ctx, sx_seen_set* set, const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
+                             uint32_t flags, uint8_t* held_out, sx_seen_merge_info* info);
 
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);

@@ -27,6 +27,7 @@ SX_TALLY_NEVER = (1 << 64) - 1   # sx_tally_set_read: first[k] of a keyword with
 SX_LABEL_NEVER = (1 << 64) - 1   # sx_label_set_read: first[p] of a pattern without a finding
 SX_DISTINCT_FIRST, SX_DISTINCT_REPEATED, SX_DISTINCT_COUNT_SHIFT = 1, 2, 32   # sx_result_distinct_device (Result.distinct_device): a word's bits
 SX_DISTINCT_SEEN, SX_SEEN_LOOKUP_ONLY = 4, 0x100   # sx_result_seen_device (Result.seen_device): bit 2 of a word, and the call flag "mark, add nothing"
+SX_SEEN_BLOB_HEADER_BYTES, SX_SEEN_BLOB_VERSION = 64, 1   # sx_seen_set_export (SeenSet.export): the header of a saved set
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -51,7 +52,9 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_result_tally_device", "sx_tally_set_read", "sx_tally_set_counters_device",
            "sx_label_set_create", "sx_label_set_info_get", "sx_label_set_free", "sx_label_set_reset", "sx_label_set_read", "sx_label_set_counters_device",
            "sx_result_label_device", "sx_labels_segment_device", "sx_labels_segments", "sx_labels_free", "sx_result_select_labels_device", "sx_result_distinct_device",
-           "sx_seen_set_create", "sx_seen_set_info_get", "sx_seen_set_reset", "sx_seen_set_free", "sx_result_seen_device", "sx_get_stats", "sx_free", "sx_fill_background_device",
+           "sx_seen_set_create", "sx_seen_set_info_get", "sx_seen_set_reset", "sx_seen_set_free", "sx_result_seen_device",
+           "sx_seen_set_merge", "sx_seen_set_grow", "sx_seen_set_export_size", "sx_seen_set_export", "sx_seen_blob_info_get", "sx_seen_set_import", "sx_seen_set_add_strings",
+           "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
 
@@ -220,6 +223,14 @@ class SeenInfo(C.Structure):   # sx_seen_info
                 ("added_strings", C.c_uint64), ("added_bytes", C.c_uint64), ("rounds", C.c_uint32), ("table_log2", C.c_uint32)]
 
 
+class SeenMergeInfo(C.Structure):   # sx_seen_merge_info
+    _fields_ = [("source_strings", C.c_uint64), ("already_held", C.c_uint64), ("added_strings", C.c_uint64), ("added_bytes", C.c_uint64)]
+
+
+class SeenBlobInfo(C.Structure):   # sx_seen_blob_info
+    _fields_ = [("strings", C.c_uint64), ("bytes", C.c_uint64), ("nocase", C.c_uint32), ("version", C.c_uint32)]
+
+
 class Run(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("chars", C.c_uint64)]
 
@@ -329,6 +340,13 @@ def lib():
     L.sx_seen_set_reset.argtypes = [vp]
     L.sx_seen_set_free.argtypes, L.sx_seen_set_free.restype = [vp], None
     L.sx_result_seen_device.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(SeenInfo)]
+    L.sx_seen_set_merge.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SeenMergeInfo)]
+    L.sx_seen_set_grow.argtypes = [vp, vp, C.c_uint64, C.c_uint64]
+    L.sx_seen_set_export_size.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.sx_seen_set_export.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.sx_seen_blob_info_get.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(SeenBlobInfo)]
+    L.sx_seen_set_import.argtypes = [vp, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp)]
+    L.sx_seen_set_add_strings.argtypes = [vp, vp, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.c_char_p, C.POINTER(SeenMergeInfo)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -625,6 +643,23 @@ class _DeviceHandle:
             pass
 
 
+def _blob_bytes(blob_or_path):
+    if isinstance(blob_or_path, (bytes, bytearray, memoryview)):
+        return bytes(blob_or_path)
+    with open(blob_or_path, "rb") as f:
+        return f.read()
+
+
+def seen_blob_info(blob):
+    """sx_seen_blob_info_get: a saved SeenSet (bytes, or the path of a file) checked completely, on the host and without a device;
+    sx_seen_blob_info as a dict: strings, bytes, nocase, version.  SxError SX_E_INVALID: it is not a blob a set can be loaded from."""
+    blob, info = _blob_bytes(blob), SeenBlobInfo()
+    rc = lib().sx_seen_blob_info_get(blob, len(blob), C.byref(info))
+    if rc != SX_OK:
+        raise SxError(rc, "sx_seen_blob_info_get")
+    return {k: getattr(info, k) for k, _ in SeenBlobInfo._fields_}
+
+
 def _pattern_array(patterns):
     """(an array of sx_pattern, its length) for a list of bytes-like patterns; the array keeps the bytes alive"""
     pats = [bytes(p) for p in patterns]
@@ -751,6 +786,9 @@ class SeenSet(_DeviceHandle):
 
     _free, _info_get, _info_type = "sx_seen_set_free", "sx_seen_set_info_get", SeenSetInfo
 
+    def __init__(self, handle, scanner=None):
+        self.h, self._s = handle, scanner
+
     def info(self):
         """sx_seen_set_info as a dict: strings, bytes (what it holds), capacity_strings, capacity_bytes, table_log2, nocase, tag_bits"""
         return self._info_dict()
@@ -760,6 +798,78 @@ class SeenSet(_DeviceHandle):
         rc = lib().sx_seen_set_reset(self._handle())
         if rc != SX_OK:
             raise SxError(rc, "sx_seen_set_reset")
+
+    def _scanner(self, scanner):
+        """the context of a call that needs one: `scanner`, or the Scanner that made the set (any on the set's device will do)"""
+        s = scanner or self._s
+        if s is None or not s.h:
+            raise SxError(SX_E_STATE, "the Scanner that made the SeenSet is closed: pass scanner=")
+        return s
+
+    def merge(self, other, add=True, scanner=None):
+        """sx_seen_set_merge: this set united with `other` (a SeenSet of the same fold, which is only read).  add=False
+        (SX_SEEN_LOOKUP_ONLY) counts and adds nothing.  sx_seen_merge_info as a dict: source_strings (what `other` holds),
+        already_held (of those, what this set held: the intersection), added_strings, added_bytes.  SxError SX_E_NOMEM: what is new
+        does not fit, and the set is as it was — grow() it."""
+        if not isinstance(other, SeenSet) or not other.h:
+            raise SxError(SX_E_INVALID, "the SeenSet has been freed" if isinstance(other, SeenSet) else "merge takes a SeenSet")
+        s, info = self._scanner(scanner), SeenMergeInfo()
+        s._chk(lib().sx_seen_set_merge(s.h, self._handle(), other.h, 0 if add else SX_SEEN_LOOKUP_ONLY, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in SeenMergeInfo._fields_}
+
+    def grow(self, capacity_strings, capacity_bytes, scanner=None):
+        """sx_seen_set_grow: this same set with new capacities (smaller ones too, as long as they hold what it holds); every string
+        it holds stays"""
+        s = self._scanner(scanner)
+        s._chk(lib().sx_seen_set_grow(s.h, self._handle(), capacity_strings, capacity_bytes))
+
+    def export(self):
+        """sx_seen_set_export: the set as bytes — a 64-byte header and its entries as they lie (include/stringsext_amd.h) —, for
+        Scanner.seen_set_from() in this or another process"""
+        n, written = C.c_uint64(), C.c_uint64()
+        rc = lib().sx_seen_set_export_size(self._handle(), C.byref(n))
+        if rc != SX_OK:
+            raise SxError(rc, "sx_seen_set_export_size")
+        buf = C.create_string_buffer(n.value)
+        rc = lib().sx_seen_set_export(self.h, buf, n.value, C.byref(written))
+        if rc != SX_OK:
+            raise SxError(rc, "sx_seen_set_export")
+        return buf.raw[:written.value]
+
+    def save(self, path):
+        """export() into a file"""
+        with open(path, "wb") as f:
+            f.write(self.export())
+
+    def strings(self):
+        """the strings the set holds — folded, if it folds — in the order of their entries: parsed from export()"""
+        blob, out, at = self.export(), [], SX_SEEN_BLOB_HEADER_BYTES
+        while at < len(blob):
+            n = int.from_bytes(blob[at:at + 4], "little")
+            out.append(blob[at + 8:at + 8 + n])
+            at += 8 + (n + 7) // 8 * 8
+        return out
+
+    def add_strings(self, strings, add=True, scanner=None, _held=None):
+        """sx_seen_set_add_strings: a list of bytes objects put into the set (add=False: only looked up).  sx_seen_merge_info as a
+        dict: source_strings = the distinct ones among them under the set's fold, already_held, added_strings, added_bytes.  SxError
+        SX_E_NOMEM: what is new does not fit, and the set is as it was."""
+        strings = [bytes(x) for x in strings]
+        offsets = (C.c_uint64 * (len(strings) + 1))()
+        at = 0
+        for i, x in enumerate(strings):
+            at += len(x)
+            offsets[i + 1] = at
+        s, info = self._scanner(scanner), SeenMergeInfo()
+        s._chk(lib().sx_seen_set_add_strings(s.h, self._handle(), b"".join(strings), offsets, len(strings), 0 if add else SX_SEEN_LOOKUP_ONLY, _held, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in SeenMergeInfo._fields_}
+
+    def contains(self, strings, scanner=None):
+        """per string of the list whether the set holds it (under the set's fold): add_strings(add=False) with its held_out"""
+        strings = list(strings)
+        held = C.create_string_buffer(max(1, len(strings)))
+        self.add_strings(strings, add=False, scanner=scanner, _held=held)
+        return [b != 0 for b in held.raw[:len(strings)]]
 
 
 class Labels(_DeviceHandle):
@@ -877,7 +987,16 @@ class Scanner:
         Result.seen_device() call that takes it."""
         out = C.c_void_p()
         self._chk(lib().sx_seen_set_create(self.h, capacity_strings, capacity_bytes, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
-        return SeenSet(out)
+        return SeenSet(out, self)
+
+    def seen_set_from(self, blob_or_path, capacity_strings=0, capacity_bytes=0):
+        """sx_seen_set_import: a new SeenSet that holds what SeenSet.export() / save() wrote (bytes, or the path of a file), under the
+        blob's fold and this Scanner's SX_SEEN_TAG_BITS.  A capacity of 0: what the blob holds; a smaller one, or a blob that
+        seen_blob_info() refuses: SxError SX_E_INVALID."""
+        blob = _blob_bytes(blob_or_path)
+        out = C.c_void_p()
+        self._chk(lib().sx_seen_set_import(self.h, blob, len(blob), capacity_strings, capacity_bytes, C.byref(out)))
+        return SeenSet(out, self)
 
     def scan(self, data, file_id=-1, is_last=False):
         """sx_scan: replaces the loop src/main.rs:153-168 for one chunk held in host memory."""

@@ -330,6 +330,11 @@ hipError_t distinct_launch(const DistinctParams& P, int phase, hipStream_t strea
 struct SeenParams;
 enum SeenPhase { kSeenMark = 0, kSeenAdd = 1 };
 hipError_t seen_launch(const SeenParams& P, int phase, hipStream_t stream);
+// A set's entries into a seen set (sx_seen_merge_dev.hip, SeenMergeParams: sx_seen_merge_core.hpp), one pass over one source per
+// launch (phase: SeenPhase): mark writes held[] and adds to the call's totals, and reads the destination; add — once the host has seen
+// that what is new fits — writes the destination's entries, slots and cursors, and the error total
+struct SeenMergeParams;
+hipError_t seen_merge_launch(const SeenMergeParams& P, int phase, hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
 hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit

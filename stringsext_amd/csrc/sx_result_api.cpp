@@ -1,5 +1,6 @@
 // sx_result_api.cpp — the C-ABI of include/stringsext_amd.h for a result that stays in HBM (SX_OPT_RESULT_ON_DEVICE): the print, the
-// selections, the extraction, the tally, the labels, the duplicate strings and the seen set, and the compiled sets they take.  What the operations
+// selections, the extraction, the tally, the labels, the duplicate strings and the seen set — with its merge, growth, blob and string
+// lists —, and the compiled sets they take.  What the operations
 // share is here once — the view of a segment, a set's upload, a handle's device and memory, the counters' reset, the two passes of
 // whatever writes a new result —; what tells them apart is in their lane functions (sx_*_core.hpp) and kernels (sx_*_dev.hip).
 #include "sx_ctx.hpp"
@@ -17,6 +18,8 @@
 #include "sx_label_core.hpp"
 #include "sx_distinct_core.hpp"
 #include "sx_seen_core.hpp"
+#include "sx_seen_merge_core.hpp"
+#include "sx_seen_blob.hpp"
 
 using namespace sx;
 
@@ -326,6 +329,17 @@ int select_on_device(sx_ctx* ctx, const sx_result* r, TwoPass& pass, sx_result**
     return SX_OK;
 }
 
+// sx_ctx::d_distinct — the tables of a distinct pass, the scratch of a seen set's merge — holds `bytes`: grown on demand, and empty
+// where that fails (false)
+bool distinct_room(sx_ctx* ctx, uint64_t bytes) {
+    if (bytes <= ctx->d_distinct_cap) return true;
+    if (ctx->d_distinct) (void)hipFree(ctx->d_distinct);
+    ctx->d_distinct = nullptr; ctx->d_distinct_cap = 0;
+    if (hipMalloc((void**)&ctx->d_distinct, bytes) != hipSuccess) { ctx->d_distinct = nullptr; return false; }
+    ctx->d_distinct_cap = bytes;
+    return true;
+}
+
 // The duplicate strings where the findings lie (sx_distinct_dev.hip): the source is checked as a whole, the words' memory is had as the
 // labels' is, then the call's own tables — [the segments][the counter and the totals][rep][count][the table], each 256-byte aligned, in
 // sx_ctx::d_distinct, which grows on demand and is no selection block —, then the rounds on the selections' stream: the table emptied,
@@ -359,15 +373,7 @@ int distinct_on_device(sx_ctx* ctx, const sx_result* r, uint32_t nocase, const c
     const uint64_t at_words = up256(n_segs * sizeof(DistinctSeg)), at_rep = at_words + 256, at_count = at_rep + up256(findings * sizeof(uint64_t)),
                    at_table = at_count + up256(findings * sizeof(uint64_t)), table_bytes = sizeof(uint64_t) << table_log2;
     // (the tables: grown on demand, SX_E_NOMEM leaves them empty; then the words)
-    bool room = at_table + table_bytes <= ctx->d_distinct_cap;
-    if (!room) {
-        if (ctx->d_distinct) (void)hipFree(ctx->d_distinct);
-        ctx->d_distinct = nullptr; ctx->d_distinct_cap = 0;
-        room = hipMalloc((void**)&ctx->d_distinct, at_table + table_bytes) == hipSuccess;
-        if (room) ctx->d_distinct_cap = at_table + table_bytes;
-        else ctx->d_distinct = nullptr;
-    }
-    if (!room || hipMalloc((void**)&lab->mem, label_bytes) != hipSuccess) {
+    if (!distinct_room(ctx, at_table + table_bytes) || hipMalloc((void**)&lab->mem, label_bytes) != hipSuccess) {
         (void)hipGetLastError();
         lab->mem = nullptr;
         ctx->set_err("device distinct: no memory for " + std::to_string(label_bytes) + " bytes of words and " + std::to_string(at_table + table_bytes) + " bytes of tables");
@@ -871,15 +877,15 @@ int sx_seen_set_reset(sx_seen_set* set) {
     return SX_OK;
 }
 
-int sx_seen_set_create(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capacity_bytes, uint32_t flags, sx_seen_set** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !out) return SX_E_INVALID;
-    if (flags & ~(uint32_t)SX_SELECT_ASCII_NOCASE) { ctx->set_err("seen set: flags other than SX_SELECT_ASCII_NOCASE"); return SX_E_INVALID; }
-    if (capacity_strings == 0 || capacity_strings > kSeenMaxCapacity || capacity_bytes > kSeenMaxCapacity) {
-        ctx->set_err("seen set: a capacity of " + std::to_string(capacity_strings) + " strings and " + std::to_string(capacity_bytes) + " bytes: at least one string, 2^40 of either at most");
-        return SX_E_INVALID;
-    }
-    if (host_only(ctx, "for the seen set")) return SX_E_STATE;
+// (what sx_seen_set_create, _grow and _import ask of a set's capacities)
+static bool seen_capacity_refused(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capacity_bytes) {
+    if (capacity_strings != 0 && capacity_strings <= kSeenMaxCapacity && capacity_bytes <= kSeenMaxCapacity) return false;
+    ctx->set_err("seen set: a capacity of " + std::to_string(capacity_strings) + " strings and " + std::to_string(capacity_bytes) + " bytes: at least one string, 2^40 of either at most");
+    return true;
+}
+
+// An empty set of checked capacities on the context's device (nocase: 0 / 1)
+static int seen_set_make(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capacity_bytes, uint32_t nocase, uint32_t tag_bits, sx_seen_set** out) {
     uint32_t table_log2 = 1;
     while (((uint64_t)1 << table_log2) < 2 * capacity_strings) table_log2++;
     const uint64_t table_bytes = sizeof(uint64_t) << table_log2, at_arena = kSeenHeadBytes + up256(table_bytes), bytes = at_arena + up256(capacity_bytes ? capacity_bytes : 1);
@@ -892,11 +898,20 @@ int sx_seen_set_create(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capacity
     }
     sx_seen_set* set = new_handle<sx_seen_set>(ctx, mem);
     if (!set) return SX_E_NOMEM;
-    set->dev = SeenSet{ (uint64_t*)(mem + kSeenHeadBytes), mem + at_arena, (uint64_t*)mem, table_log2, (uint32_t)ctx->sw.seen_tag_bits, flags & SX_SELECT_ASCII_NOCASE ? 1u : 0u, 0u };
+    set->dev = SeenSet{ (uint64_t*)(mem + kSeenHeadBytes), mem + at_arena, (uint64_t*)mem, table_log2, tag_bits, nocase, 0u };
     set->info = sx_seen_set_info{ 0, 0, capacity_strings, capacity_bytes, table_log2, set->dev.nocase, set->dev.tag_bits, 0 };
     if (sx_seen_set_reset(set) != SX_OK) { ctx->set_err("seen set: the slots could not be emptied"); sx_seen_set_free(set); return SX_E_HIP; }
     *out = set;
     return SX_OK;
+}
+
+int sx_seen_set_create(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capacity_bytes, uint32_t flags, sx_seen_set** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out) return SX_E_INVALID;
+    if (flags & ~(uint32_t)SX_SELECT_ASCII_NOCASE) { ctx->set_err("seen set: flags other than SX_SELECT_ASCII_NOCASE"); return SX_E_INVALID; }
+    if (seen_capacity_refused(ctx, capacity_strings, capacity_bytes)) return SX_E_INVALID;
+    if (host_only(ctx, "for the seen set")) return SX_E_STATE;
+    return seen_set_make(ctx, capacity_strings, capacity_bytes, flags & SX_SELECT_ASCII_NOCASE ? 1u : 0u, (uint32_t)ctx->sw.seen_tag_bits, out);
 }
 
 // (strings and bytes are the cursors, read where they lie)
@@ -957,7 +972,7 @@ int sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, uin
         sx_labels_free(lab);
         if (full)
             ctx->set_err("seen set: " + std::to_string(words[0]) + " + " + std::to_string(tot[kSeenNewClasses]) + " strings of " + std::to_string(set->info.capacity_strings) + ", "
-                         + std::to_string(words[1]) + " + " + std::to_string(tot[kSeenNewBytes]) + " bytes of " + std::to_string(set->info.capacity_bytes) + ": the set is as it was, create a larger one");
+                         + std::to_string(words[1]) + " + " + std::to_string(tot[kSeenNewBytes]) + " bytes of " + std::to_string(set->info.capacity_bytes) + ": the set is as it was, sx_seen_set_grow gives it room");
         else
             ctx->set_err(lost ? std::string("device seen: a probe walked every slot of the set and met no empty one") : std::string("device seen: ") + hipGetErrorString(e));
         return full ? SX_E_NOMEM : SX_E_HIP;
@@ -966,6 +981,194 @@ int sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, uin
         *info = sx_seen_info{ di.findings, di.distinct, di.repeated, tot[kSeenFindings], tot[kSeenClasses], add ? tot[kSeenNewClasses] : 0u, add ? tot[kSeenNewBytes] : 0u,
                               di.rounds, di.table_log2 };
     *out = lab;
+    return SX_OK;
+}
+
+// A source of the merge kernels where it lies in HBM (sx_seen_merge_core.hpp)
+struct SeenSource {
+    const uint64_t* words;
+    const uint8_t* arena;
+    uint64_t n;
+};
+
+// A source into a set (sx_seen_merge_dev.hip), on the selections' stream: the totals zeroed, mark, and ONE read — the destination's
+// cursors and the call's totals, which lie side by side —; the host decides whether what is new fits; then add, and the same read
+// again for the error total.  A refusal for capacity comes before the add pass: the destination is as it was.  dst, capacity_*: the
+// destination; d_held: ceil(src.n / 64) words of scratch; what: the call's name in the messages; held (may be NULL): held[] as mark left it.
+static int seen_merge_run(sx_ctx* ctx, const char* what, const SeenSet& dst, uint64_t capacity_strings, uint64_t capacity_bytes, const SeenSource& src,
+                          uint64_t* d_held, bool add, sx_seen_merge_info* info, std::vector<uint64_t>* held) {
+    hipStream_t st = ctx->post_stream;
+    SeenMergeParams p;
+    memset(&p, 0, sizeof p);
+    p.words = src.words; p.src_arena = src.arena; p.n = src.n; p.held = d_held; p.totals = dst.cursors + 2; p.set = dst;
+    uint64_t words[2 + kSeenMergeTotals] = { 0 };      // the cursors, the totals
+    const uint64_t* const tot = words + 2;
+    const uint64_t waves = (src.n + kSelectRecs - 1) / kSelectRecs;
+    if (held) held->assign(waves, 0);
+    hipError_t e = hipMemsetAsync(p.totals, 0, kSeenMergeTotals * sizeof(uint64_t), st);
+    if (e == hipSuccess) e = seen_merge_launch(p, kSeenMark, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(words, dst.cursors, sizeof words, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && held && waves) e = hipMemcpyAsync(held->data(), d_held, waves * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+    { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
+    bool lost = e == hipSuccess && tot[kSeenMergeError] != 0;
+    const uint64_t had[2] = { words[0], words[1] }, fresh = tot[kSeenMergeNew], fresh_bytes = tot[kSeenMergeNewBytes];
+    const bool full = e == hipSuccess && !lost && add && (had[0] + fresh > capacity_strings || had[1] + fresh_bytes > capacity_bytes);
+    if (info) *info = sx_seen_merge_info{ tot[kSeenMergeOccupied], tot[kSeenMergeHeld], add ? fresh : 0u, add ? fresh_bytes : 0u };
+    if (e == hipSuccess && !lost && !full && add && fresh) {
+        e = seen_merge_launch(p, kSeenAdd, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(words, dst.cursors, sizeof words, hipMemcpyDeviceToHost, st);
+        const hipError_t e2 = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = e2;
+        lost = e == hipSuccess && (tot[kSeenMergeError] != 0 || words[0] != had[0] + fresh || words[1] != had[1] + fresh_bytes);
+    }
+    if (e == hipSuccess && !lost && !full) return SX_OK;
+    (void)hipGetLastError();
+    if (full)
+        ctx->set_err(std::string("seen set ") + what + ": " + std::to_string(had[0]) + " + " + std::to_string(fresh) + " strings of " + std::to_string(capacity_strings) + ", "
+                     + std::to_string(had[1]) + " + " + std::to_string(fresh_bytes) + " bytes of " + std::to_string(capacity_bytes) + ": the set is as it was, sx_seen_set_grow gives it room");
+    else
+        ctx->set_err(std::string("seen set ") + what + (lost ? ": a probe walked every slot of the set and met no empty one, or the cursors are not the sums" : std::string(": ") + hipGetErrorString(e)));
+    return full ? SX_E_NOMEM : SX_E_HIP;
+}
+
+// (the scratch of a merge: `bytes` of sx_ctx::d_distinct, which is no selection block)
+static int seen_merge_room(sx_ctx* ctx, const char* what, uint64_t bytes) {
+    if (distinct_room(ctx, bytes)) return SX_OK;
+    (void)hipGetLastError();
+    ctx->set_err(std::string("seen set ") + what + ": no device memory for " + std::to_string(bytes) + " bytes of scratch");
+    return SX_E_NOMEM;
+}
+
+// A source the host built — n words, and the arena_bytes of entries they point into — uploaded behind held[] and put into `set`
+static int seen_merge_list(sx_ctx* ctx, const char* what, sx_seen_set* set, const uint64_t* words, uint64_t n, const uint8_t* arena, uint64_t arena_bytes,
+                           bool add, sx_seen_merge_info* info, std::vector<uint64_t>* held) {
+    if (info) *info = sx_seen_merge_info{ 0, 0, 0, 0 };
+    if (held) held->clear();
+    if (n == 0) return SX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t at_words = up256((n + kSelectRecs - 1) / kSelectRecs * sizeof(uint64_t)), at_arena = at_words + up256(n * sizeof(uint64_t));
+    { const int rc = seen_merge_room(ctx, what, at_arena + up256(arena_bytes)); if (rc != SX_OK) return rc; }
+    uint8_t* const d = ctx->d_distinct;
+    HIP_TRY(ctx, hipMemcpy(d + at_words, words, n * sizeof(uint64_t), hipMemcpyHostToDevice));      // (done when they return: the kernels' stream need not wait)
+    HIP_TRY(ctx, hipMemcpy(d + at_arena, arena, arena_bytes, hipMemcpyHostToDevice));
+    return seen_merge_run(ctx, what, set->dev, set->info.capacity_strings, set->info.capacity_bytes, SeenSource{ (const uint64_t*)(d + at_words), d + at_arena, n },
+                          (uint64_t*)d, add, info, held);
+}
+
+// A set's slot table as the source
+static int seen_merge_set(sx_ctx* ctx, const char* what, const SeenSet& dst, uint64_t capacity_strings, uint64_t capacity_bytes, const sx_seen_set* src, bool add,
+                          sx_seen_merge_info* info) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = (uint64_t)1 << src->dev.table_log2;
+    { const int rc = seen_merge_room(ctx, what, up256((n + kSelectRecs - 1) / kSelectRecs * sizeof(uint64_t))); if (rc != SX_OK) return rc; }
+    return seen_merge_run(ctx, what, dst, capacity_strings, capacity_bytes, SeenSource{ src->dev.slots, src->dev.arena, n }, (uint64_t*)ctx->d_distinct, add, info, nullptr);
+}
+
+int sx_seen_set_merge(sx_ctx* ctx, sx_seen_set* dst, const sx_seen_set* src, uint32_t flags, sx_seen_merge_info* info) {
+    if (!ctx || !dst || !src) return SX_E_INVALID;
+    if (flags & ~(uint32_t)SX_SEEN_LOOKUP_ONLY) { ctx->set_err("seen set merge: flags other than SX_SEEN_LOOKUP_ONLY"); return SX_E_INVALID; }
+    if (dst == src) { ctx->set_err("seen set merge: a set into itself"); return SX_E_INVALID; }
+    if (dst->dev.nocase != src->dev.nocase) { ctx->set_err("seen set merge: the sets fold differently"); return SX_E_INVALID; }
+    if (host_only(ctx, "for a seen set's merge")) return SX_E_STATE;
+    if (on_another_device(ctx, *dst, "the seen set lies") || on_another_device(ctx, *src, "the source set lies")) return SX_E_INVALID;
+    return seen_merge_set(ctx, "merge", dst->dev, dst->info.capacity_strings, dst->info.capacity_bytes, src, !(flags & SX_SEEN_LOOKUP_ONLY), info);
+}
+
+int sx_seen_set_grow(sx_ctx* ctx, sx_seen_set* set, uint64_t capacity_strings, uint64_t capacity_bytes) {
+    if (!ctx || !set) return SX_E_INVALID;
+    if (seen_capacity_refused(ctx, capacity_strings, capacity_bytes)) return SX_E_INVALID;
+    if (host_only(ctx, "for a seen set's growth")) return SX_E_STATE;
+    if (on_another_device(ctx, *set, "the seen set lies")) return SX_E_INVALID;
+    uint64_t cursors[2];
+    { const int rc = read_counters(set->device, set->dev.cursors, cursors, 2); if (rc != SX_OK) { ctx->set_err("seen set grow: the cursors could not be read"); return rc; } }
+    if (cursors[0] > capacity_strings || cursors[1] > capacity_bytes) {
+        ctx->set_err("seen set grow: the set holds " + std::to_string(cursors[0]) + " strings and " + std::to_string(cursors[1]) + " bytes, more than the new capacity of "
+                     + std::to_string(capacity_strings) + " and " + std::to_string(capacity_bytes));
+        return SX_E_INVALID;
+    }
+    sx_seen_set* fresh = nullptr;
+    { const int rc = seen_set_make(ctx, capacity_strings, capacity_bytes, set->dev.nocase, set->dev.tag_bits, &fresh); if (rc != SX_OK) return rc; }
+    sx_seen_merge_info mi{};
+    int rc = seen_merge_set(ctx, "grow", fresh->dev, capacity_strings, capacity_bytes, set, true, &mi);
+    if (rc == SX_OK && (mi.source_strings != cursors[0] || mi.added_strings != cursors[0] || mi.added_bytes != cursors[1])) {
+        ctx->set_err("seen set grow: the set's table holds " + std::to_string(mi.source_strings) + " entries, its cursors say " + std::to_string(cursors[0]));
+        rc = SX_E_HIP;
+    }
+    if (rc != SX_OK) { sx_seen_set_free(fresh); return rc; }
+    std::swap(set->mem, fresh->mem);
+    set->dev = fresh->dev; set->info = fresh->info;
+    sx_seen_set_free(fresh);       // (the old memory)
+    return SX_OK;
+}
+
+int sx_seen_set_export_size(const sx_seen_set* set, uint64_t* bytes) {
+    if (!set || !bytes) return SX_E_INVALID;
+    uint64_t cursors[2];
+    { const int rc = read_counters(set->device, set->dev.cursors, cursors, 2); if (rc != SX_OK) return rc; }
+    *bytes = kSeenBlobHeaderBytes + cursors[1];
+    return SX_OK;
+}
+
+int sx_seen_set_export(const sx_seen_set* set, void* buf, uint64_t cap, uint64_t* written) {
+    if (written) *written = 0;
+    if (!set || !buf || !written) return SX_E_INVALID;
+    uint64_t cursors[2];
+    { const int rc = read_counters(set->device, set->dev.cursors, cursors, 2); if (rc != SX_OK) return rc; }
+    if (cap < kSeenBlobHeaderBytes + cursors[1]) return SX_E_INVALID;
+    uint8_t* const area = (uint8_t*)buf + kSeenBlobHeaderBytes;
+    if (cursors[1] && hipMemcpy(area, set->dev.arena, cursors[1], hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+    seen_blob_header((uint8_t*)buf, set->dev.nocase, cursors[0], area, cursors[1]);
+    *written = kSeenBlobHeaderBytes + cursors[1];
+    return SX_OK;
+}
+
+int sx_seen_blob_info_get(const void* blob, uint64_t len, sx_seen_blob_info* out) {
+    if (!blob || !out) return SX_E_INVALID;
+    std::string why;
+    return seen_blob_check(blob, len, out, nullptr, &why);
+}
+
+int sx_seen_set_import(sx_ctx* ctx, const void* blob, uint64_t len, uint64_t capacity_strings, uint64_t capacity_bytes, sx_seen_set** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !blob || !out) return SX_E_INVALID;
+    if (host_only(ctx, "for the seen set")) return SX_E_STATE;
+    sx_seen_blob_info bi{};
+    std::vector<uint64_t> words;
+    std::string why;
+    { const int rc = seen_blob_check(blob, len, &bi, &words, &why); if (rc != SX_OK) { ctx->set_err("seen set import: " + why); return rc; } }
+    if (capacity_strings == 0) capacity_strings = bi.strings ? bi.strings : 1;
+    if (capacity_bytes == 0) capacity_bytes = bi.bytes;
+    if (capacity_strings < bi.strings || capacity_bytes < bi.bytes) {
+        ctx->set_err("seen set import: the blob holds " + std::to_string(bi.strings) + " strings and " + std::to_string(bi.bytes) + " bytes, more than the capacity of "
+                     + std::to_string(capacity_strings) + " and " + std::to_string(capacity_bytes));
+        return SX_E_INVALID;
+    }
+    if (seen_capacity_refused(ctx, capacity_strings, capacity_bytes)) return SX_E_INVALID;
+    sx_seen_set* set = nullptr;
+    { const int rc = seen_set_make(ctx, capacity_strings, capacity_bytes, bi.nocase, (uint32_t)ctx->sw.seen_tag_bits, &set); if (rc != SX_OK) return rc; }
+    sx_seen_merge_info mi{};
+    int rc = seen_merge_list(ctx, "import", set, words.data(), words.size(), (const uint8_t*)blob + kSeenBlobHeaderBytes, bi.bytes, true, &mi, nullptr);
+    if (rc == SX_OK && (mi.added_strings != bi.strings || mi.added_bytes != bi.bytes)) { ctx->set_err("seen set import: not every entry of the blob was added"); rc = SX_E_HIP; }
+    if (rc != SX_OK) { sx_seen_set_free(set); return rc; }
+    *out = set;
+    return SX_OK;
+}
+
+int sx_seen_set_add_strings(sx_ctx* ctx, sx_seen_set* set, const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint32_t flags, uint8_t* held_out,
+                            sx_seen_merge_info* info) {
+    if (!ctx || !set) return SX_E_INVALID;
+    if (flags & ~(uint32_t)SX_SEEN_LOOKUP_ONLY) { ctx->set_err("seen set add_strings: flags other than SX_SEEN_LOOKUP_ONLY"); return SX_E_INVALID; }
+    if (host_only(ctx, "for a seen set's strings")) return SX_E_STATE;
+    if (on_another_device(ctx, *set, "the seen set lies")) return SX_E_INVALID;
+    std::vector<uint8_t> arena;
+    std::vector<uint64_t> words, held;
+    std::vector<uint32_t> kept_of;
+    std::string why;
+    { const int rc = seen_entries_build(bytes, offsets, n, set->dev.nocase, &arena, &words, &kept_of, &why); if (rc != SX_OK) { ctx->set_err("seen set add_strings: " + why); return rc; } }
+    const int rc = seen_merge_list(ctx, "add_strings", set, words.data(), words.size(), arena.data(), arena.size(), !(flags & SX_SEEN_LOOKUP_ONLY), info, held_out ? &held : nullptr);
+    if (rc != SX_OK) return rc;
+    if (held_out)
+        for (uint64_t i = 0; i < n; i++) held_out[i] = (uint8_t)((held[kept_of[i] / kSelectRecs] >> (kept_of[i] % kSelectRecs)) & 1u);
     return SX_OK;
 }
 

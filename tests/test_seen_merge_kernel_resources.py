@@ -1,0 +1,11 @@
+"""A seen set's merge, what the compiler made of stringsext_amd/csrc/sx_seen_merge_dev.hip (no GPU needed): the per-kernel resource
+remarks the Makefile keeps next to the object."""
+from test_kernel_resources import remarks
+
+
+def test_the_two_merge_kernels_are_there_with_no_scratch_no_spills_and_no_lds():
+    rows = remarks("sx_seen_merge_dev")
+    assert sorted(rows) == ["seen_merge_add_kernel", "seen_merge_mark_kernel"], sorted(rows)
+    for k, v in rows.items():
+        assert v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (k, v)
+        assert v["LDS Size [bytes/block]"] == 0, (k, v)                          # kSeenMergeGroupsPerCu rests on it

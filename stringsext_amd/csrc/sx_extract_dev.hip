@@ -37,9 +37,8 @@ __global__ __launch_bounds__(64 * kRowsWaves) void extract_count_kernel(ExtractP
             }
         const uint64_t i = w * kSelectRecs + lane;
         if (i < P.n) P.rcount[i] = count;
-        uint64_t sum = count;
-#pragma unroll
-        for (int d = 32; d; d >>= 1) { sum += __shfl_xor(sum, d, 64); bytes += __shfl_xor(bytes, d, 64); }
+        const uint64_t sum = wave_sum(count);
+        bytes = wave_sum(bytes);
         if (lane == 0) { P.wcount[w] = sum; P.wbytes[w] = bytes; }
     }
 }
@@ -54,12 +53,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void extract_place_kernel(ExtractP
         const uint64_t i = w * kSelectRecs + lane;
         // the lane's base: the wavefront's, plus the matches of the wavefront's earlier records
         const uint32_t own = i < P.n ? P.rcount[i] : 0u;
-        uint64_t before = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t v = __shfl_up(before, d, 64);
-            if (lane >= (uint32_t)d) before += v;
-        }
+        const uint64_t before = wave_prefix(own, lane);
         uint64_t rank = P.wbase[w] + before - own;
         const uint64_t rank_end = rank + own;
         ExtractLane L = extract_begin_lane(P, w, lane);

@@ -8,6 +8,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "sx_device.hpp"
+#include "sx_rows_dev.hpp"
 
 #define SXD __device__ __forceinline__
 #include "sx_print_core.hpp"
@@ -19,9 +20,7 @@ constexpr uint32_t kPrintWaves = 4;   // wavefronts per workgroup, each with its
 // wsum[w] for w in [0, waves]: the last one (behind the last record) is 0, so that the scan's last word is the segment's text bytes
 __global__ __launch_bounds__(64 * kPrintWaves) void print_len_kernel(PrintParams P, uint64_t* wsum, uint64_t waves) {
     const uint64_t i = (uint64_t)blockIdx.x * (64 * kPrintWaves) + threadIdx.x;
-    uint64_t len = print_line_len(P, i);
-#pragma unroll
-    for (int d = 32; d; d >>= 1) len += __shfl_xor(len, d, 64);
+    const uint64_t len = wave_sum(print_line_len(P, i));
     if ((threadIdx.x & 63u) == 0 && i / kPrintRecs <= waves) wsum[i / kPrintRecs] = len;
 }
 

@@ -1,8 +1,9 @@
 // sx_result_api.cpp — the C-ABI of include/stringsext_amd.h for a result that stays in HBM (SX_OPT_RESULT_ON_DEVICE): the print, the
 // selections, the extraction, the tally, the labels, the duplicate strings and the seen set — with its merge, growth, blob and string
-// lists —, and the compiled sets they take.  What the operations
-// share is here once — the view of a segment, a set's upload, a handle's device and memory, the counters' reset, the two passes of
-// whatever writes a new result —; what tells them apart is in their lane functions (sx_*_core.hpp) and kernels (sx_*_dev.hip).
+// lists —, and the compiled sets they take.  What the operations share is here once — the view of a segment, a set's upload, a
+// handle's device and memory, the counters' reset, a buffer that grows, a result's labels, the two passes of whatever writes a new
+// result, the mark and add passes of whatever goes into a seen set —; what tells them apart is in their lane functions
+// (sx_*_core.hpp) and kernels (sx_*_dev.hip).
 #include "sx_ctx.hpp"
 #include "sx_print_core.hpp"
 #include "sx_select_core.hpp"
@@ -194,19 +195,40 @@ int result_on_device(sx_ctx* ctx, const sx_result* r, const char* host_call) {
     return SX_OK;
 }
 
-// (a grow-only device buffer of the selection: SX_E_NOMEM leaves it empty)
-int grow_device(sx_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t bytes, const char* what) {
-    if (bytes <= *cap) return SX_OK;
+// A grow-only device buffer of the context holds `bytes`.  false: the allocation failed and the buffer is empty; the caller says so in
+// its own words
+bool device_room(uint8_t** p, uint64_t* cap, uint64_t bytes) {
+    if (bytes <= *cap) return true;
     if (*p) (void)hipFree(*p);
     *p = nullptr; *cap = 0;
-    if (hipMalloc((void**)p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        ctx->set_err(std::string("device select: no memory for ") + std::to_string(bytes) + " bytes of " + what);
-        return SX_E_NOMEM;
-    }
+    if (hipMalloc((void**)p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
     *cap = bytes;
-    return SX_OK;
+    return true;
+}
+// (a buffer of the selection)
+int grow_device(sx_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t bytes, const char* what) {
+    if (device_room(p, cap, bytes)) return SX_OK;
+    ctx->set_err(std::string("device select: no memory for ") + std::to_string(bytes) + " bytes of " + what);
+    return SX_E_NOMEM;
+}
+
+// The labels of a result whose segments lie in HBM: the handle, an array of a word per record for every segment — each 256-byte aligned
+// in ONE allocation of *bytes bytes, not written here — and per segment what tells the source apart.  NULL: no memory for them
+sx_labels* labels_of(const sx_ctx* ctx, const sx_result* r, uint64_t* bytes) {
+    *bytes = 0;
+    for (const MissionFindings& s : r->r.segs) *bytes += up256(s.ext_nf * sizeof(uint64_t));
+    uint8_t* mem = nullptr;
+    if (hipMalloc((void**)&mem, *bytes ? *bytes : 256) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    sx_labels* lab = new_handle<sx_labels>(ctx, mem);
+    uint64_t at = 0;
+    for (size_t i = 0; lab && i < r->r.segs.size(); i++) {
+        const MissionFindings& s = r->r.segs[i];
+        sx_labels::Seg seg;
+        seg.d = (const uint64_t*)(mem + at); seg.recs = s.dev_copy; seg.n = s.ext_nf; seg.epoch_ref = s.dev_epoch_ref; seg.epoch = s.dev_epoch;
+        lab->segs.push_back(seg);
+        at += up256(s.ext_nf * sizeof(uint64_t));
+    }
+    return lab;
 }
 
 // The two passes of an operation that writes a new result, a segment at a time, as select_on_device drives them.  measure: pass 1
@@ -329,17 +351,6 @@ int select_on_device(sx_ctx* ctx, const sx_result* r, TwoPass& pass, sx_result**
     return SX_OK;
 }
 
-// sx_ctx::d_distinct — the tables of a distinct pass, the scratch of a seen set's merge — holds `bytes`: grown on demand, and empty
-// where that fails (false)
-bool distinct_room(sx_ctx* ctx, uint64_t bytes) {
-    if (bytes <= ctx->d_distinct_cap) return true;
-    if (ctx->d_distinct) (void)hipFree(ctx->d_distinct);
-    ctx->d_distinct = nullptr; ctx->d_distinct_cap = 0;
-    if (hipMalloc((void**)&ctx->d_distinct, bytes) != hipSuccess) { ctx->d_distinct = nullptr; return false; }
-    ctx->d_distinct_cap = bytes;
-    return true;
-}
-
 // The duplicate strings where the findings lie (sx_distinct_dev.hip): the source is checked as a whole, the words' memory is had as the
 // labels' is, then the call's own tables — [the segments][the counter and the totals][rep][count][the table], each 256-byte aligned, in
 // sx_ctx::d_distinct, which grows on demand and is no selection block —, then the rounds on the selections' stream: the table emptied,
@@ -362,20 +373,15 @@ int distinct_on_device(sx_ctx* ctx, const sx_result* r, uint32_t nocase, const c
         if (v.n >> 32 || n_segs >> 31) { ctx->set_err(std::string(what) + ": a segment of 2^32 findings or more"); return SX_E_INVALID; }
         segs.push_back(DistinctSeg{ v.recs, v.arena, v.n, v.packed, 0u, findings });
         findings += v.n;
-        label_bytes += up256(v.n * sizeof(uint64_t));
     }
     uint32_t table_log2 = 1;
     if (ctx->sw.distinct_table_log2 >= 0) table_log2 = (uint32_t)ctx->sw.distinct_table_log2;
     else while (((uint64_t)1 << table_log2) < 2 * findings) table_log2++;
-    sx_labels* lab = new (std::nothrow) sx_labels;
-    if (!lab) return SX_E_NOMEM;
-    lab->device = ctx->device;
     const uint64_t at_words = up256(n_segs * sizeof(DistinctSeg)), at_rep = at_words + 256, at_count = at_rep + up256(findings * sizeof(uint64_t)),
                    at_table = at_count + up256(findings * sizeof(uint64_t)), table_bytes = sizeof(uint64_t) << table_log2;
-    // (the tables: grown on demand, SX_E_NOMEM leaves them empty; then the words)
-    if (!distinct_room(ctx, at_table + table_bytes) || hipMalloc((void**)&lab->mem, label_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        lab->mem = nullptr;
+    // (the words; then the tables: grown on demand, SX_E_NOMEM leaves them empty)
+    sx_labels* lab = labels_of(ctx, r, &label_bytes);
+    if (!lab || !device_room(&ctx->d_distinct, &ctx->d_distinct_cap, at_table + table_bytes)) {
         ctx->set_err("device distinct: no memory for " + std::to_string(label_bytes) + " bytes of words and " + std::to_string(at_table + table_bytes) + " bytes of tables");
         sx_labels_free(lab);
         return SX_E_NOMEM;
@@ -386,13 +392,6 @@ int distinct_on_device(sx_ctx* ctx, const sx_result* r, uint32_t nocase, const c
     base.segs = (const DistinctSeg*)tab; base.n_segs = (uint32_t)n_segs; base.nocase = nocase; base.table_log2 = table_log2;
     base.unresolved = (uint64_t*)(tab + at_words); base.totals = base.unresolved + 1;
     base.rep = (uint64_t*)(tab + at_rep); base.count = (uint64_t*)(tab + at_count); base.table = (uint64_t*)(tab + at_table);
-    uint64_t lab_at = 0;
-    for (const MissionFindings& s : r->r.segs) {
-        sx_labels::Seg seg;
-        seg.d = (const uint64_t*)(lab->mem + lab_at); seg.recs = s.dev_copy; seg.n = s.ext_nf; seg.epoch_ref = s.dev_epoch_ref; seg.epoch = s.dev_epoch;
-        lab->segs.push_back(seg);
-        lab_at += up256(s.ext_nf * sizeof(uint64_t));
-    }
     // one phase over every segment, in order
     auto phase = [&](int which, uint32_t round) {
         for (size_t i = 0; i < n_segs; i++) {
@@ -441,6 +440,48 @@ int distinct_on_device(sx_ctx* ctx, const sx_result* r, uint32_t nocase, const c
     return SX_OK;
 }
 
+// THE mark/add protocol of a seen set, for a result's records (sx_seen_dev.hip) and for a source of entries (sx_seen_merge_dev.hip),
+// on the selections' stream: the totals zeroed; the caller's mark launches; ONE read — the set's cursors and the call's totals, which
+// lie side by side, and in the same wait held[] where the caller wants it (d_held -> *held, sized by the caller) —; the host decides
+// `lost` (a lookup walked every slot), then `full` (what is new does not fit: SX_E_NOMEM BEFORE the add pass, the set is as it was);
+// the caller's add launches, only if adding and something is new; the same read again behind them: the error total — an adder that
+// found no slot — and the cursors, which have to be the sums.  launch(phase): the caller's launches of one pass, kSeenMark / kSeenAdd.
+// what: the call's name in a refusal ("seen set", "seen set merge"), err_what: in an error.  tot: the totals as mark left them.
+template <class Launch>
+int seen_mark_add(sx_ctx* ctx, const std::string& what, const std::string& err_what, const SeenSet& dst, uint64_t capacity_strings, uint64_t capacity_bytes,
+                  bool add, Launch launch, uint64_t tot[kSeenTotals], const uint64_t* d_held, std::vector<uint64_t>* held) {
+    hipStream_t st = ctx->post_stream;
+    uint64_t words[2 + kSeenTotals] = { 0 };      // the cursors, the totals
+    auto read_back = [&] { return hipMemcpyAsync(words, dst.cursors, sizeof words, hipMemcpyDeviceToHost, st); };
+    hipError_t e = hipMemsetAsync(dst.cursors + 2, 0, kSeenTotals * sizeof(uint64_t), st);
+    if (e == hipSuccess) e = launch(kSeenMark);
+    if (e == hipSuccess) e = read_back();
+    if (e == hipSuccess && held && !held->empty()) e = hipMemcpyAsync(held->data(), d_held, held->size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+    { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
+    memcpy(tot, words + 2, kSeenTotals * sizeof(uint64_t));
+    const uint64_t had[2] = { words[0], words[1] }, fresh = tot[kSeenNewClasses], fresh_bytes = tot[kSeenNewBytes];
+    bool lost = e == hipSuccess && tot[kSeenError] != 0, added = false;
+    const bool full = e == hipSuccess && !lost && add && (had[0] + fresh > capacity_strings || had[1] + fresh_bytes > capacity_bytes);
+    if (e == hipSuccess && !lost && !full && add && fresh) {
+        added = true;
+        e = launch(kSeenAdd);
+        if (e == hipSuccess) e = read_back();
+        const hipError_t e2 = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = e2;
+        lost = e == hipSuccess && (words[2 + kSeenError] != 0 || words[0] != had[0] + fresh || words[1] != had[1] + fresh_bytes);
+    }
+    if (e == hipSuccess && !lost && !full) return SX_OK;
+    (void)hipGetLastError();
+    if (full)
+        ctx->set_err(what + ": " + std::to_string(had[0]) + " + " + std::to_string(fresh) + " strings of " + std::to_string(capacity_strings) + ", "
+                     + std::to_string(had[1]) + " + " + std::to_string(fresh_bytes) + " bytes of " + std::to_string(capacity_bytes) + ": the set is as it was, sx_seen_set_grow gives it room");
+    else if (lost)
+        ctx->set_err(err_what + (added ? ": an adder walked every slot of the set and met no empty one, or the cursors are not the sums"
+                                       : ": a probe walked every slot of the set and met no empty one"));
+    else
+        ctx->set_err(err_what + ": " + hipGetErrorString(e));
+    return full ? SX_E_NOMEM : SX_E_HIP;
+}
 
 }  // namespace
 
@@ -497,12 +538,7 @@ int sx_print_findings_device(sx_ctx* ctx, const sx_result* r, int n_inputs, int 
     const size_t ns = r->r.segs.size();
     uint64_t scratch = 0;
     for (const MissionFindings& s : r->r.segs) scratch += print_scratch_bytes(s.ext_nf);
-    if (scratch > ctx->d_print_scratch_cap) {
-        if (ctx->d_print_scratch) (void)hipFree(ctx->d_print_scratch);
-        ctx->d_print_scratch = nullptr; ctx->d_print_scratch_cap = 0;
-        if (hipMalloc((void**)&ctx->d_print_scratch, scratch) != hipSuccess) { (void)hipGetLastError(); ctx->d_print_scratch = nullptr; ctx->set_err("device print: no memory for the offsets"); return SX_E_NOMEM; }
-        ctx->d_print_scratch_cap = scratch;
-    }
+    if (!device_room(&ctx->d_print_scratch, &ctx->d_print_scratch_cap, scratch)) { ctx->set_err("device print: no memory for the offsets"); return SX_E_NOMEM; }
     std::vector<PrintParams> P(ns);
     std::vector<const uint64_t*> d_total(ns);
     uint64_t at = 0;
@@ -525,17 +561,7 @@ int sx_print_findings_device(sx_ctx* ctx, const sx_result* r, int n_inputs, int 
         P[i].base = total;
         total += t;
     }
-    if (total > ctx->d_text_cap) {
-        if (ctx->d_text) (void)hipFree(ctx->d_text);
-        ctx->d_text = nullptr; ctx->d_text_cap = 0;
-        if (hipMalloc((void**)&ctx->d_text, total) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->d_text = nullptr;
-            ctx->set_err("device print: no memory for " + std::to_string(total) + " bytes of text");
-            return SX_E_NOMEM;
-        }
-        ctx->d_text_cap = total;
-    }
+    if (!device_room(&ctx->d_text, &ctx->d_text_cap, total)) { ctx->set_err("device print: no memory for " + std::to_string(total) + " bytes of text"); return SX_E_NOMEM; }
     for (size_t i = 0; i < ns; i++) {
         P[i].text = ctx->d_text;
         HIP_TRY(ctx, print_write(P[i], st));
@@ -789,31 +815,21 @@ int sx_result_label_device(sx_ctx* ctx, const sx_result* r, sx_label_set* set, u
     { const int rc = result_on_device(ctx, r, "label on the host"); if (rc != SX_OK) return rc; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->post_stream;
-    sx_labels* lab = new (std::nothrow) sx_labels;
-    if (!lab) return SX_E_NOMEM;
-    lab->device = ctx->device;
     uint64_t bytes = 0;
-    for (const MissionFindings& s : r->r.segs) bytes += up256(s.ext_nf * sizeof(uint64_t));
-    if (hipMalloc((void**)&lab->mem, bytes ? bytes : 256) != hipSuccess) {
-        (void)hipGetLastError();
-        delete lab;
+    sx_labels* lab = labels_of(ctx, r, &bytes);
+    if (!lab) {
         ctx->set_err("device labels: no memory for " + std::to_string(bytes) + " bytes of labels");
         return SX_E_NOMEM;
     }
-    uint64_t walked = 0, at = 0;
+    uint64_t walked = 0;
     hipError_t e = hipSuccess;
-    for (const MissionFindings& s : r->r.segs) {
-        sx_labels::Seg seg;
-        seg.d = (const uint64_t*)(lab->mem + at); seg.recs = s.dev_copy; seg.n = s.ext_nf; seg.epoch_ref = s.dev_epoch_ref; seg.epoch = s.dev_epoch;
-        lab->segs.push_back(seg);
-        LabelParams p = params_of<LabelParams>(seg_ref(s));
+    for (size_t i = 0; e == hipSuccess && i < lab->segs.size(); i++) {
+        LabelParams p = params_of<LabelParams>(seg_ref(r->r.segs[i]));
         p.ordinal = ordinal_base + walked;
-        p.labels = (uint64_t*)(lab->mem + at);
+        p.labels = (uint64_t*)lab->segs[i].d;
         p.set = set->dev;
         e = label_launch(p, st);
-        if (e != hipSuccess) break;
-        walked += s.ext_nf;
-        at += up256(s.ext_nf * sizeof(uint64_t));
+        walked += lab->segs[i].n;
     }
     const hipError_t e2 = hipStreamSynchronize(st);
     if (e == hipSuccess) e = e2;
@@ -925,10 +941,8 @@ int sx_seen_set_info_get(const sx_seen_set* set, sx_seen_set_info* out) {
 }
 void sx_seen_set_free(sx_seen_set* set) { handle_free(set); }
 
-// The seen set where the findings lie (sx_seen_dev.hip): the distinct pass under the set's fold, as sx_result_distinct_device runs it;
-// then, on the selections' stream, the totals zeroed, every segment's mark, and ONE read — the set's cursors and the call's totals,
-// which lie side by side —; the host decides whether what is new fits; then every segment's add and one wait.  A refusal for capacity
-// comes before the add pass: the set is as it was.
+// The seen set where the findings lie: the distinct pass under the set's fold, as sx_result_distinct_device runs it; then seen_mark_add
+// with every segment's mark and every segment's add.  On any refusal or error the labels are freed.
 int sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, uint32_t flags, sx_labels** out, sx_seen_info* info) {
     if (out) *out = nullptr;
     if (!ctx || !r || !set || !out) return SX_E_INVALID;
@@ -939,44 +953,21 @@ int sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, uin
     sx_distinct_info di{};
     std::vector<DistinctSeg> segs;
     { const int rc = distinct_on_device(ctx, r, set->dev.nocase, "seen", &lab, &di, &segs); if (rc != SX_OK) return rc; }
-    hipStream_t st = ctx->post_stream;
-    uint64_t* const totals = set->dev.cursors + 2;
     auto pass = [&](int which) {
         for (size_t i = 0; i < segs.size(); i++) {
             SeenParams p;
             memset(&p, 0, sizeof p);
             p.recs = segs[i].recs; p.arena = segs[i].arena; p.n = segs[i].n; p.packed = segs[i].packed;
-            p.labels = (uint64_t*)lab->segs[i].d; p.totals = totals; p.set = set->dev;
-            const hipError_t pe = seen_launch(p, which, st);
+            p.labels = (uint64_t*)lab->segs[i].d; p.totals = set->dev.cursors + 2; p.set = set->dev;
+            const hipError_t pe = seen_launch(p, which, ctx->post_stream);
             if (pe != hipSuccess) return pe;
         }
         return hipSuccess;
     };
-    uint64_t words[2 + kSeenTotals] = { 0 };      // the cursors, the totals
-    hipError_t e = hipMemsetAsync(totals, 0, kSeenTotals * sizeof(uint64_t), st);
-    if (e == hipSuccess) e = pass(kSeenMark);
-    if (e == hipSuccess) e = hipMemcpyAsync(words, set->dev.cursors, sizeof words, hipMemcpyDeviceToHost, st);
-    { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
-    const uint64_t* const tot = words + 2;
-    const bool lost = e == hipSuccess && tot[kSeenError] != 0;
     const bool add = !(flags & SX_SEEN_LOOKUP_ONLY);
-    const bool full = e == hipSuccess && !lost && add
-                      && (words[0] + tot[kSeenNewClasses] > set->info.capacity_strings || words[1] + tot[kSeenNewBytes] > set->info.capacity_bytes);
-    if (e == hipSuccess && !lost && !full && add && tot[kSeenNewClasses]) {
-        e = pass(kSeenAdd);
-        const hipError_t e2 = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = e2;
-    }
-    if (e != hipSuccess || lost || full) {
-        (void)hipGetLastError();
-        sx_labels_free(lab);
-        if (full)
-            ctx->set_err("seen set: " + std::to_string(words[0]) + " + " + std::to_string(tot[kSeenNewClasses]) + " strings of " + std::to_string(set->info.capacity_strings) + ", "
-                         + std::to_string(words[1]) + " + " + std::to_string(tot[kSeenNewBytes]) + " bytes of " + std::to_string(set->info.capacity_bytes) + ": the set is as it was, sx_seen_set_grow gives it room");
-        else
-            ctx->set_err(lost ? std::string("device seen: a probe walked every slot of the set and met no empty one") : std::string("device seen: ") + hipGetErrorString(e));
-        return full ? SX_E_NOMEM : SX_E_HIP;
-    }
+    uint64_t tot[kSeenTotals];
+    const int rc = seen_mark_add(ctx, "seen set", "device seen", set->dev, set->info.capacity_strings, set->info.capacity_bytes, add, pass, tot, nullptr, nullptr);
+    if (rc != SX_OK) { sx_labels_free(lab); return rc; }
     if (info)
         *info = sx_seen_info{ di.findings, di.distinct, di.repeated, tot[kSeenFindings], tot[kSeenClasses], add ? tot[kSeenNewClasses] : 0u, add ? tot[kSeenNewBytes] : 0u,
                               di.rounds, di.table_log2 };
@@ -991,50 +982,25 @@ struct SeenSource {
     uint64_t n;
 };
 
-// A source into a set (sx_seen_merge_dev.hip), on the selections' stream: the totals zeroed, mark, and ONE read — the destination's
-// cursors and the call's totals, which lie side by side —; the host decides whether what is new fits; then add, and the same read
-// again for the error total.  A refusal for capacity comes before the add pass: the destination is as it was.  dst, capacity_*: the
-// destination; d_held: ceil(src.n / 64) words of scratch; what: the call's name in the messages; held (may be NULL): held[] as mark left it.
+// A source into a set: seen_mark_add with the source's one mark launch and one add launch.  dst, capacity_*: the destination; d_held:
+// ceil(src.n / 64) words of scratch; what: the call's name in the messages; held (may be NULL): held[] as mark left it.  *info is
+// written for a refused call too: what would have been added.
 static int seen_merge_run(sx_ctx* ctx, const char* what, const SeenSet& dst, uint64_t capacity_strings, uint64_t capacity_bytes, const SeenSource& src,
                           uint64_t* d_held, bool add, sx_seen_merge_info* info, std::vector<uint64_t>* held) {
-    hipStream_t st = ctx->post_stream;
     SeenMergeParams p;
     memset(&p, 0, sizeof p);
     p.words = src.words; p.src_arena = src.arena; p.n = src.n; p.held = d_held; p.totals = dst.cursors + 2; p.set = dst;
-    uint64_t words[2 + kSeenMergeTotals] = { 0 };      // the cursors, the totals
-    const uint64_t* const tot = words + 2;
-    const uint64_t waves = (src.n + kSelectRecs - 1) / kSelectRecs;
-    if (held) held->assign(waves, 0);
-    hipError_t e = hipMemsetAsync(p.totals, 0, kSeenMergeTotals * sizeof(uint64_t), st);
-    if (e == hipSuccess) e = seen_merge_launch(p, kSeenMark, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(words, dst.cursors, sizeof words, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && held && waves) e = hipMemcpyAsync(held->data(), d_held, waves * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
-    { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
-    bool lost = e == hipSuccess && tot[kSeenMergeError] != 0;
-    const uint64_t had[2] = { words[0], words[1] }, fresh = tot[kSeenMergeNew], fresh_bytes = tot[kSeenMergeNewBytes];
-    const bool full = e == hipSuccess && !lost && add && (had[0] + fresh > capacity_strings || had[1] + fresh_bytes > capacity_bytes);
-    if (info) *info = sx_seen_merge_info{ tot[kSeenMergeOccupied], tot[kSeenMergeHeld], add ? fresh : 0u, add ? fresh_bytes : 0u };
-    if (e == hipSuccess && !lost && !full && add && fresh) {
-        e = seen_merge_launch(p, kSeenAdd, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(words, dst.cursors, sizeof words, hipMemcpyDeviceToHost, st);
-        const hipError_t e2 = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = e2;
-        lost = e == hipSuccess && (tot[kSeenMergeError] != 0 || words[0] != had[0] + fresh || words[1] != had[1] + fresh_bytes);
-    }
-    if (e == hipSuccess && !lost && !full) return SX_OK;
-    (void)hipGetLastError();
-    if (full)
-        ctx->set_err(std::string("seen set ") + what + ": " + std::to_string(had[0]) + " + " + std::to_string(fresh) + " strings of " + std::to_string(capacity_strings) + ", "
-                     + std::to_string(had[1]) + " + " + std::to_string(fresh_bytes) + " bytes of " + std::to_string(capacity_bytes) + ": the set is as it was, sx_seen_set_grow gives it room");
-    else
-        ctx->set_err(std::string("seen set ") + what + (lost ? ": a probe walked every slot of the set and met no empty one, or the cursors are not the sums" : std::string(": ") + hipGetErrorString(e)));
-    return full ? SX_E_NOMEM : SX_E_HIP;
+    if (held) held->assign((src.n + kSelectRecs - 1) / kSelectRecs, 0);
+    uint64_t tot[kSeenTotals];
+    const std::string name = std::string("seen set ") + what;
+    const int rc = seen_mark_add(ctx, name, name, dst, capacity_strings, capacity_bytes, add, [&](int which) { return seen_merge_launch(p, which, ctx->post_stream); }, tot, d_held, held);
+    if (info) *info = sx_seen_merge_info{ tot[kSeenMergeOccupied], tot[kSeenMergeHeld], add ? tot[kSeenNewClasses] : 0u, add ? tot[kSeenNewBytes] : 0u };
+    return rc;
 }
 
 // (the scratch of a merge: `bytes` of sx_ctx::d_distinct, which is no selection block)
 static int seen_merge_room(sx_ctx* ctx, const char* what, uint64_t bytes) {
-    if (distinct_room(ctx, bytes)) return SX_OK;
-    (void)hipGetLastError();
+    if (device_room(&ctx->d_distinct, &ctx->d_distinct_cap, bytes)) return SX_OK;
     ctx->set_err(std::string("seen set ") + what + ": no device memory for " + std::to_string(bytes) + " bytes of scratch");
     return SX_E_NOMEM;
 }

@@ -1,7 +1,7 @@
 // sx_rows_dev.hpp — what the kernels that walk a table over a segment's records share (sx_selset_dev.hip, sx_selre_dev.hip,
-// sx_extract_dev.hip, sx_seltally_dev.hip, sx_label_dev.hip; sx_select_dev.hip for the epilogue): the workgroup's shape, the class
-// map and the first rows into LDS, the grid that strides over the segment, the words a pass 1 of the selection leaves per wavefront,
-// and the table checks.  Device-only: included behind <hip/hip_runtime.h> and sx_device.hpp.  The walks themselves are the kernels'.
+// sx_extract_dev.hip, sx_seltally_dev.hip, sx_label_dev.hip; sx_select_dev.hip for the epilogue; sx_seen_dev.hip, sx_seen_merge_dev.hip
+// and sx_print_dev.hip for the wavefront's sum, prefix and reserve): the workgroup's shape, the class map and the first rows into
+// LDS, the grid that strides over the segment, the words a pass 1 of the selection leaves per wavefront, and the table checks.  Device-only: included behind <hip/hip_runtime.h> and sx_device.hpp.  The walks themselves are the kernels'.
 #pragma once
 
 namespace sx {
@@ -21,13 +21,35 @@ __device__ __forceinline__ void rows_load(const uint8_t* map_src, const void* ne
     __syncthreads();
 }
 
+// The wavefront's helpers; every lane of the wavefront calls them.  wave_sum: every lane gets the sum over the 64 lanes
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+// the sum over the lanes up to and including this one; lane 63 holds the wavefront's
+__device__ __forceinline__ uint64_t wave_prefix(uint64_t v, uint32_t lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t left = __shfl_up(v, d, 64);
+        if (lane >= (uint32_t)d) v += left;
+    }
+    return v;
+}
+// Room for every lane's `bytes` behind *cursor, one address for the whole grid, with ONE add by lane 0: where this lane's bytes
+// begin, the lanes' rooms one behind the other in lane order
+__device__ __forceinline__ uint64_t wave_reserve(uint64_t* cursor, uint64_t bytes, uint32_t lane) {
+    const uint64_t upto = wave_prefix(bytes, lane), all = __shfl(upto, 63, 64);
+    uint64_t base = 0;
+    if (lane == 0) base = atomicAdd((unsigned long long*)cursor, (unsigned long long)all);
+    return __shfl(base, 0, 64) + upto - bytes;
+}
+
 // What pass 1 of a selection leaves of wavefront w: the mask of its selected records, their number, their strings' bytes
 // (sel, len: the lane's record; every lane of the wavefront calls)
 __device__ __forceinline__ void wave_store_selected(uint64_t* wmask, uint32_t* wcount, uint64_t* wbytes, uint64_t w, bool sel, uint32_t len) {
     const uint64_t mask = __ballot(sel ? 1 : 0);
-    uint64_t bytes = sel ? len : 0u;
-#pragma unroll
-    for (int d = 32; d; d >>= 1) bytes += __shfl_xor(bytes, d, 64);
+    const uint64_t bytes = wave_sum(sel ? len : 0u);
     if (threadIdx.x % 64u == 0) { wmask[w] = mask; wcount[w] = (uint32_t)__popcll(mask); wbytes[w] = bytes; }
 }
 

@@ -1,7 +1,9 @@
-// sx_seen_core.hpp — the seen set (sx_seen_set, sx_result_seen_device): strings remembered in HBM from one result to the next.  What
-// ONE lane does for its record, written as lane functions.  Included by sx_seen_dev.hip with SXD = `__device__ __forceinline__`; the
-// test-only harness tests/native/seen_core_host.cpp includes it with SXD = `inline`, so the very same code is checked against a Python
-// set carried across calls on a machine without GPU (tests/test_seen_core.py).
+// sx_seen_core.hpp — the seen set (sx_seen_set, sx_result_seen_device): strings remembered in HBM from one result to the next.  This
+// file owns THE SET — its slot words (seen_entry_at), its bounded walk for lookups (seen_lookup) and for inserts (seen_claim), its
+// call totals (SeenTotal) and its validity (seen_set_ok) — and what ONE lane does for a RECORD of a result, written as lane functions;
+// sx_seen_merge_core.hpp puts entries that are already a set's through the same two walks.  Included by sx_seen_dev.hip with SXD =
+// `__device__ __forceinline__`; the test-only harness tests/native/seen_core_host.cpp includes it with SXD = `inline`, so the very same
+// code is checked against a Python set carried across calls on a machine without GPU (tests/test_seen_core.py).
 //
 // The set: 2^table_log2 slots — the power of two >= 2 x capacity_strings, so a probe always meets an empty slot — and one arena of
 // capacity_bytes.  A slot is kSeenEmpty or tag << 40 | entry_offset / 8; an entry is [u32 len][u32 0][the (folded) bytes, zero-padded
@@ -18,8 +20,9 @@
 //   add   (behind every segment's mark, and behind the host's look at the totals: what is new fits) only FIRST && !SEEN records act.
 //         They are pairwise different and different from everything the set holds, so no inserter reads another's entry.  A
 //         wavefront takes its entries' room with ONE add to the byte cursor — the lanes share it by an exclusive prefix of their
-//         entry sizes — and counts them with one add to the string cursor; a lane writes its entry and then walks from its home slot
-//         with a 64-bit compare-and-swap kSeenEmpty -> its word until one succeeds.  It compares no string.
+//         entry sizes (wave_reserve, sx_rows_dev.hpp) — and counts them with one add to the string cursor; a lane writes its entry
+//         and then walks from its home slot with a 64-bit compare-and-swap kSeenEmpty -> its word until one succeeds.  It compares no
+//         string.  A lane whose walk tried every slot says so, and the wavefront adds that to the error word.
 // No lane waits for another: every dependency is a kernel boundary.  Words, totals and cursors are sums: deterministic.  WHERE an
 // entry lies depends on the order of the adds, and is no part of the contract.  A lane reads the bytes [str_off, str_off + str_len)
 // of its own record and the bytes of entries of the set, and no other byte of any arena.
@@ -34,7 +37,12 @@ constexpr uint64_t kSeenEmpty = ~(uint64_t)0;                  // a slot without
 constexpr uint32_t kSeenOffsetBits = 40;                       // a slot's low bits: entry_offset / 8
 constexpr uint32_t kSeenMaxTagBits = 24;
 constexpr uint32_t kSeenSeed = 0x5EE25E70u;                    // the set's own seed: distinct_hash's `round`, unlike any round of a tournament
-enum SeenTotal : uint32_t { kSeenFindings = 0, kSeenClasses = 1, kSeenNewClasses = 2, kSeenNewBytes = 3, kSeenError = 4, kSeenTotals = 5 };
+// A call's totals.  Words 0 and 1 are, for a result, the seen findings and the seen classes; for a source of entries (sx_seen_merge_core.hpp),
+// the occupied words and those the destination held.  What is new, its entry bytes and the error — a lookup that walked every slot, an
+// adder that found none — are the same words for both.
+enum SeenTotal : uint32_t { kSeenFindings = 0, kSeenClasses = 1, kSeenNewClasses = 2, kSeenNewBytes = 3, kSeenError = 4, kSeenTotals = 5,
+                            // (the same words, as a source of entries names them)
+                            kSeenMergeOccupied = 0, kSeenMergeHeld = 1, kSeenMergeNew = 2, kSeenMergeNewBytes = 3, kSeenMergeError = 4, kSeenMergeTotals = 5 };
 
 // the set where it lies (device pointers; in the harness: the test's)
 struct SeenSet {
@@ -43,6 +51,10 @@ struct SeenSet {
     uint64_t* cursors;       // [0] the strings the set holds, [1] their entries' bytes: where the next entry begins
     uint32_t table_log2, tag_bits, nocase, reserved;
 };
+// (a set the kernels can walk: what both launchers ask)
+inline bool seen_set_ok(const SeenSet& S) {
+    return S.slots && S.arena && S.cursors && S.table_log2 >= 1 && S.table_log2 <= 41 && S.tag_bits <= kSeenMaxTagBits;
+}
 
 struct SeenParams {
     const void* recs;        // the segment this launch walks, as SelectParams
@@ -50,11 +62,11 @@ struct SeenParams {
     uint64_t n;
     uint32_t packed, reserved;
     uint64_t* labels;        // the segment's n words, as distinct's finalize wrote them; mark ORs SX_DISTINCT_SEEN
-    uint64_t* totals;        // kSeenTotals words, mark adds
+    uint64_t* totals;        // kSeenTotals words: mark adds; add adds to the error alone
     SeenSet set;
 };
 
-// (the harness runs the lanes one after the other)
+// (the harness runs the lanes one after the other; on the device the add to the byte cursor is wave_reserve's)
 SXD uint64_t seen_fetch_add64(uint64_t* word, uint64_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return atomicAdd((unsigned long long*)word, (unsigned long long)v);
@@ -76,23 +88,42 @@ SXD bool seen_claim_slot(uint64_t* slot, uint64_t word) {
 
 SXD uint64_t seen_entry_bytes(uint32_t len) { return SX_SEEN_ENTRY_BYTES(len); }
 SXD uint64_t seen_tag(const SeenSet& S, uint64_t hash) { return hash & (((uint64_t)1 << S.tag_bits) - 1u); }
+// The entry an occupied slot's (or source's) word points to; the bits above the offset are not read
+SXD const uint8_t* seen_entry_at(const uint8_t* arena, uint64_t word) { return arena + (word & (((uint64_t)1 << kSeenOffsetBits) - 1u)) * 8u; }
 
-// Does the set hold the (folded) string s[0, len)?  *exhausted: every slot was looked at and none was empty
-SXD bool seen_find(const SeenSet& S, const uint8_t* s, uint32_t len, bool* exhausted) {
-    const uint64_t hash = distinct_hash(s, len, S.nocase, kSeenSeed), mask = ((uint64_t)1 << S.table_log2) - 1u, tag = seen_tag(S, hash);
+// THE walk of a lookup.  Does the set hold the string whose hash is `hash`?  From the home slot on: empty = no; another tag = next
+// slot; the same tag = same(entry) decides, the caller's comparison, inlined.  *exhausted: every slot was looked at and none was empty
+template <class Same>
+SXD bool seen_lookup(const SeenSet& S, uint64_t hash, Same same, bool* exhausted) {
+    const uint64_t mask = ((uint64_t)1 << S.table_log2) - 1u, tag = seen_tag(S, hash);
     uint64_t slot = distinct_slot(hash, S.table_log2);
     for (uint64_t walked = 0; walked <= mask; walked++, slot = (slot + 1u) & mask) {
         const uint64_t word = S.slots[slot];
         if (word == kSeenEmpty) return false;
-        if (word >> kSeenOffsetBits != tag) continue;
-        const uint8_t* entry = S.arena + (word & (((uint64_t)1 << kSeenOffsetBits) - 1u)) * 8u;
-        if (*(const uint32_t*)entry != len) continue;
-        uint32_t j = 0;
-        while (j < len && entry[8u + j] == select_fold(S.nocase, s[j])) j++;
-        if (j == len) return true;
+        if (word >> kSeenOffsetBits == tag && same(seen_entry_at(S.arena, word))) return true;
     }
     *exhausted = true;
     return false;
+}
+
+// THE walk of an insert: the entry at arena offset `at`, whose hash is `hash`, takes the first empty slot from its home slot on.
+// false: every slot was tried (the host has checked strings <= slots / 2, so it is an error of the table's, not a full set)
+SXD bool seen_claim(const SeenSet& S, uint64_t hash, uint64_t at) {
+    const uint64_t mask = ((uint64_t)1 << S.table_log2) - 1u, word = seen_tag(S, hash) << kSeenOffsetBits | at / 8u;
+    uint64_t slot = distinct_slot(hash, S.table_log2);
+    for (uint64_t walked = 0; walked <= mask; walked++, slot = (slot + 1u) & mask)
+        if (seen_claim_slot(S.slots + slot, word)) return true;
+    return false;
+}
+
+// Does the set hold the (folded) string s[0, len)?  Byte for byte: a record's string is neither aligned nor padded
+SXD bool seen_find(const SeenSet& S, const uint8_t* s, uint32_t len, bool* exhausted) {
+    return seen_lookup(S, distinct_hash(s, len, S.nocase, kSeenSeed), [&](const uint8_t* entry) {
+        if (*(const uint32_t*)entry != len) return false;
+        uint32_t j = 0;
+        while (j < len && entry[8u + j] == select_fold(S.nocase, s[j])) j++;
+        return j == len;
+    }, exhausted);
 }
 
 // mark, lane `lane` of wavefront `w`: its record's word gets SX_DISTINCT_SEEN if the set holds its string.  *seen = it does; *first =
@@ -123,9 +154,9 @@ SXD uint64_t seen_add_size_lane(const SeenParams& P, uint64_t w, uint32_t lane) 
 }
 
 // add, step 2, a lane whose step 1 gave bytes: `at` = where its entry begins — what the wavefront's one add to the byte cursor gave
-// back, plus the entry bytes of the lanes in front of it.  The entry is written, folded, 8 bytes at a time; then the first empty slot
-// from the home slot on takes its word.
-SXD void seen_add_lane(const SeenParams& P, uint64_t w, uint32_t lane, uint64_t at) {
+// back, plus the entry bytes of the lanes in front of it.  The entry is written, folded, 8 bytes at a time; then seen_claim.  false:
+// it found no slot (the wavefront adds that to the error total)
+SXD bool seen_add_lane(const SeenParams& P, uint64_t w, uint32_t lane, uint64_t at) {
     const SeenSet& S = P.set;
     uint64_t off; uint32_t len;
     select_string(P, w * kSelectRecs + lane, &off, &len);
@@ -137,11 +168,7 @@ SXD void seen_add_lane(const SeenParams& P, uint64_t w, uint32_t lane, uint64_t 
         for (uint32_t k = 0; k < 8 && j + k < len; k++) v |= (uint64_t)select_fold(S.nocase, s[j + k]) << (8u * k);
         entry[1u + j / 8u] = v;
     }
-    const uint64_t hash = distinct_hash(s, len, S.nocase, kSeenSeed), mask = ((uint64_t)1 << S.table_log2) - 1u;
-    const uint64_t word = seen_tag(S, hash) << kSeenOffsetBits | at / 8u;
-    uint64_t slot = distinct_slot(hash, S.table_log2);
-    for (uint64_t walked = 0; walked <= mask; walked++, slot = (slot + 1u) & mask)      // (the host has checked: strings <= slots / 2)
-        if (seen_claim_slot(S.slots + slot, word)) return;
+    return seen_claim(S, distinct_hash(s, len, S.nocase, kSeenSeed), at);
 }
 
 }  // namespace sx

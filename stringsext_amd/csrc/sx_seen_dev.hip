@@ -3,8 +3,9 @@
 // device holds at once and striding over the segment.  seen_mark_kernel looks every record's string up in the set, ORs
 // SX_DISTINCT_SEEN into its word and sums the ballots, one add per wavefront and total; seen_add_kernel — behind every segment's mark
 // and the host's look at the totals — puts the first record of every class the set does not hold into it: one add per wavefront to
-// each cursor, the entry written by its lane, and a compare-and-swap into the first empty slot.  No LDS, no barrier, and no lane waits
-// for another.
+// each cursor (wave_reserve, sx_rows_dev.hpp), the entry written by its lane, and a compare-and-swap into the first empty slot; an
+// adder that found none is added to the error total.  No LDS, no barrier, and no lane waits for another.  The set, its walks and the
+// lane functions are sx_seen_core.hpp's; this file owns the two kernels and their launcher.
 #include <hip/hip_runtime.h>
 
 #include "sx_device.hpp"
@@ -16,13 +17,6 @@
 namespace sx {
 
 constexpr uint32_t kSeenGroupsPerCu = 4;      // 4 x kRowsWaves = 32 wavefronts per CU: the kernels hold nothing in LDS
-
-// (every lane gets the sum over the wavefront)
-__device__ __forceinline__ uint64_t seen_wave_sum(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 // wavefronts [0, waves): waves = ceil(n / 64)
 __global__ __launch_bounds__(64 * kRowsWaves) void seen_mark_kernel(SeenParams P, uint64_t waves) {
@@ -37,7 +31,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void seen_mark_kernel(SeenParams P
         fresh += (uint64_t)__popcll(__ballot(first && !seen ? 1 : 0));
         fresh_bytes += bytes;
     }
-    fresh_bytes = seen_wave_sum(fresh_bytes);
+    fresh_bytes = wave_sum(fresh_bytes);
     if (lane == 0 && findings) seltally_add64(P.totals + kSeenFindings, findings);
     if (lane == 0 && classes) seltally_add64(P.totals + kSeenClasses, classes);
     if (lane == 0 && fresh) seltally_add64(P.totals + kSeenNewClasses, fresh);
@@ -46,32 +40,22 @@ __global__ __launch_bounds__(64 * kRowsWaves) void seen_mark_kernel(SeenParams P
 
 __global__ __launch_bounds__(64 * kRowsWaves) void seen_add_kernel(SeenParams P, uint64_t waves) {
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    uint64_t lost = 0;                                                    // (this lane's)
     for (uint64_t w = (uint64_t)blockIdx.x * kRowsWaves + wv; w < waves; w += (uint64_t)gridDim.x * kRowsWaves) {
         const uint64_t bytes = seen_add_size_lane(P, w, lane);
         const uint64_t adders = __ballot(bytes ? 1 : 0);
         if (!adders) continue;                                            // (the same in every lane)
-        // the entry bytes of the lanes up to and including this one; lane 63 holds the wavefront's
-        uint64_t upto = bytes;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t left = __shfl_up(upto, d, 64);
-            if (lane >= (uint32_t)d) upto += left;
-        }
-        const uint64_t all = __shfl(upto, 63, 64);
-        uint64_t base = 0;
-        if (lane == 0) {
-            base = seen_fetch_add64(P.set.cursors + 1, all);
-            seltally_add64(P.set.cursors, (uint64_t)__popcll(adders));
-        }
-        base = __shfl(base, 0, 64);
-        if (bytes) seen_add_lane(P, w, lane, base + upto - bytes);
+        const uint64_t at = wave_reserve(P.set.cursors + 1, bytes, lane);
+        if (lane == 0) seltally_add64(P.set.cursors, (uint64_t)__popcll(adders));
+        if (bytes && !seen_add_lane(P, w, lane, at)) lost++;
     }
+    lost = wave_sum(lost);
+    if (lane == 0 && lost) seltally_add64(P.totals + kSeenError, lost);
 }
 
 // One pass of one segment: P = the segment, its words, the call's totals and the set (phase: SeenPhase)
 hipError_t seen_launch(const SeenParams& P, int phase, hipStream_t stream) {
-    const SeenSet& S = P.set;
-    if (!S.slots || !S.arena || !S.cursors || S.table_log2 < 1 || S.table_log2 > 41 || S.tag_bits > kSeenMaxTagBits || !P.totals) return hipErrorInvalidValue;
+    if (!seen_set_ok(P.set) || !P.totals) return hipErrorInvalidValue;
     if (P.n == 0) return hipSuccess;
     if (!P.recs || !P.arena || !P.labels) return hipErrorInvalidValue;
     const uint64_t waves = (P.n + kSelectRecs - 1) / kSelectRecs;

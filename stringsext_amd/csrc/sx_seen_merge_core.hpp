@@ -1,5 +1,6 @@
 // sx_seen_merge_core.hpp — entries that are ALREADY a set, put into a seen set (sx_seen_set_merge, _grow, _import, _add_strings): what
-// ONE lane does for its source word, written as lane functions.  Included by sx_seen_merge_dev.hip with SXD = `__device__
+// ONE lane does for its source word, written as lane functions.  The set itself — its slot words, the walk of a lookup, the walk of an
+// insert, the totals — is sx_seen_core.hpp's; this file owns the source, the hash of an entry and the word-wise comparison.  Included by sx_seen_merge_dev.hip with SXD = `__device__
 // __forceinline__`; the test-only harness tests/native/seen_merge_host.cpp includes it with SXD = `inline`, so the very same code is
 // checked against Python sets on a machine without GPU (tests/test_seen_merge_core.py).
 //
@@ -13,8 +14,8 @@
 //         entries' bytes, error (a probe that walked every slot).  The destination is read; only held[] and the totals are written.
 //   add   (behind mark, and behind the host's look at the cursors and the totals: what is new fits) only occupied lanes whose bit of
 //         held[w] is clear act.  They are pairwise different and different from everything the destination holds, so no inserter
-//         reads another's entry.  Room is taken as seen_add takes it — an exclusive prefix of the lanes' entry sizes, then one add
-//         to the byte cursor — but for kSeenMergeAddChunks chunks of 64 words at once, a word of every chunk per lane, whose entries
+//         reads another's entry.  Room is taken as seen_add takes it — wave_reserve: an exclusive prefix of the lanes' entry sizes,
+//         then one add to the byte cursor — but for kSeenMergeAddChunks chunks of 64 words at once, a word of every chunk per lane, whose entries
 //         then lie one behind the other; the string cursor gets one add per wavefront, behind its last trip.  A lane copies an
 //         entry, then walks from the home slot with a compare-and-swap.
 // ENTRIES ARE MOVED AND COMPARED EIGHT BYTES AT A TIME.  Both sides are 8-byte aligned and zero-padded and their second u32 is 0, so
@@ -35,14 +36,12 @@ namespace sx {
 // table of 2^26 slots, whatever it held.
 constexpr uint32_t kSeenMergeAddChunks = 8;
 
-enum SeenMergeTotal : uint32_t { kSeenMergeOccupied = 0, kSeenMergeHeld = 1, kSeenMergeNew = 2, kSeenMergeNewBytes = 3, kSeenMergeError = 4, kSeenMergeTotals = 5 };
-
 struct SeenMergeParams {
     const uint64_t* words;       // the source's n words
     const uint8_t* src_arena;    // where their entries lie, 8-byte aligned
     uint64_t n;
     uint64_t* held;              // ceil(n / 64) words: mark writes, add reads
-    uint64_t* totals;            // kSeenMergeTotals words: mark adds; add adds to the error alone
+    uint64_t* totals;            // kSeenMergeTotals words (occupied, held, new, new bytes, error): mark adds; add adds to the error alone
     SeenSet set;                 // the destination
 };
 
@@ -51,7 +50,7 @@ SXD const uint64_t* seen_merge_entry(const SeenMergeParams& P, uint64_t i) {
     if (i >= P.n) return nullptr;
     const uint64_t word = P.words[i];
     if (word == kSeenEmpty) return nullptr;
-    return (const uint64_t*)(P.src_arena + (word & (((uint64_t)1 << kSeenOffsetBits) - 1u)) * 8u);
+    return (const uint64_t*)seen_entry_at(P.src_arena, word);
 }
 
 // distinct_hash(the entry's bytes, len, nocase, kSeenSeed), a word of the entry at a time: begin, every word with the bytes it holds
@@ -72,19 +71,13 @@ SXD uint64_t seen_merge_hash(const uint64_t* entry, uint32_t nocase) {
 // Does the set hold `entry` (whose hash is `hash`)?  Word for word, the length first: a comparison ends at the first word that
 // differs, so it never leaves the shorter entry.  *exhausted: every slot was looked at and none was empty
 SXD bool seen_merge_find(const SeenSet& S, const uint64_t* entry, uint64_t hash, bool* exhausted) {
-    const uint64_t mask = ((uint64_t)1 << S.table_log2) - 1u, tag = seen_tag(S, hash), words = 1u + ((entry[0] & 0xFFFFFFFFu) + 7u) / 8u;
-    uint64_t slot = distinct_slot(hash, S.table_log2);
-    for (uint64_t walked = 0; walked <= mask; walked++, slot = (slot + 1u) & mask) {
-        const uint64_t word = S.slots[slot];
-        if (word == kSeenEmpty) return false;
-        if (word >> kSeenOffsetBits != tag) continue;
-        const uint64_t* have = (const uint64_t*)(S.arena + (word & (((uint64_t)1 << kSeenOffsetBits) - 1u)) * 8u);
+    const uint64_t words = 1u + ((entry[0] & 0xFFFFFFFFu) + 7u) / 8u;
+    return seen_lookup(S, hash, [&](const uint8_t* at) {
+        const uint64_t* have = (const uint64_t*)at;
         uint64_t j = 0;
         while (j < words && have[j] == entry[j]) j++;
-        if (j == words) return true;
-    }
-    *exhausted = true;
-    return false;
+        return j == words;
+    }, exhausted);
 }
 
 // mark, lane `lane` of wavefront `w`.  *occupied = its source word has an entry; *held = the destination holds it; *bytes = the entry
@@ -107,8 +100,7 @@ SXD uint64_t seen_merge_add_size_lane(const SeenMergeParams& P, uint64_t w, uint
 }
 
 // add, step 2, a lane whose step 1 gave bytes: `at` = where its entry begins, as seen_add_lane's.  The entry is copied word for word
-// and hashed on the way; then the first empty slot from the home slot on takes its word.  false: every slot was tried (the wavefront
-// adds that to the error total; the host has checked strings <= slots / 2, so it is an error of the table's, not a full set).
+// and hashed on the way; then seen_claim.  false: it found no slot (the wavefront adds that to the error total)
 SXD bool seen_merge_add_lane(const SeenMergeParams& P, uint64_t w, uint32_t lane, uint64_t at) {
     const SeenSet& S = P.set;
     const uint64_t* entry = seen_merge_entry(P, w * kSelectRecs + lane);
@@ -121,12 +113,7 @@ SXD bool seen_merge_add_lane(const SeenMergeParams& P, uint64_t w, uint32_t lane
         to[k] = v;
         h = seen_merge_hash_word(h, v, len - j < 8u ? (uint32_t)(len - j) : 8u, S.nocase);
     }
-    const uint64_t hash = seen_merge_hash_end(h, len), mask = ((uint64_t)1 << S.table_log2) - 1u;
-    const uint64_t word = seen_tag(S, hash) << kSeenOffsetBits | at / 8u;
-    uint64_t slot = distinct_slot(hash, S.table_log2);
-    for (uint64_t walked = 0; walked <= mask; walked++, slot = (slot + 1u) & mask)
-        if (seen_claim_slot(S.slots + slot, word)) return true;
-    return false;
+    return seen_claim(S, seen_merge_hash_end(h, len), at);
 }
 
 }  // namespace sx

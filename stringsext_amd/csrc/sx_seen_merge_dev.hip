@@ -4,7 +4,9 @@
 // ballot "held" per wavefront and sums five totals, one add per wavefront and total; seen_merge_add_kernel — behind the host's look at
 // the cursors and the totals — copies the entries the destination did not hold into it: one add to the byte cursor per wavefront and
 // trip, a trip being kSeenMergeAddChunks chunks of 64 words, the entry copied by its lane eight bytes at a time, and a compare-and-swap
-// into the first empty slot.  No LDS, no barrier, and no lane waits for another.
+// into the first empty slot.  No LDS, no barrier, and no lane waits for another.  The set and its walks are sx_seen_core.hpp's, the
+// lane functions sx_seen_merge_core.hpp's, the wavefront's sum and reserve sx_rows_dev.hpp's; this file owns the two kernels and
+// their launcher.
 #include <hip/hip_runtime.h>
 
 #include "sx_device.hpp"
@@ -32,8 +34,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void seen_merge_mark_kernel(SeenMe
         lost += (uint64_t)__popcll(__ballot(gone ? 1 : 0));
         fresh_bytes += bytes;
     }
-#pragma unroll
-    for (int d = 32; d; d >>= 1) fresh_bytes += __shfl_xor(fresh_bytes, d, 64);
+    fresh_bytes = wave_sum(fresh_bytes);
     if (lane != 0) return;
     if (occupied) seltally_add64(P.totals + kSeenMergeOccupied, occupied);
     if (held) seltally_add64(P.totals + kSeenMergeHeld, held);
@@ -53,17 +54,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void seen_merge_add_kernel(SeenMer
 #pragma unroll
         for (uint32_t k = 0; k < kSeenMergeAddChunks; k++) bytes += seen_merge_add_size_lane(P, b * kSeenMergeAddChunks + k, lane);
         if (!__ballot(bytes ? 1 : 0)) continue;                           // (the same in every lane)
-        // the entry bytes of the lanes up to and including this one; lane 63 holds the wavefront's
-        uint64_t upto = bytes;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t left = __shfl_up(upto, d, 64);
-            if (lane >= (uint32_t)d) upto += left;
-        }
-        const uint64_t all = __shfl(upto, 63, 64);
-        uint64_t base = 0;
-        if (lane == 0) base = seen_fetch_add64(P.set.cursors + 1, all);
-        uint64_t at = __shfl(base, 0, 64) + upto - bytes;                 // this lane's entries lie one behind the other
+        uint64_t at = wave_reserve(P.set.cursors + 1, bytes, lane);       // this lane's entries lie one behind the other
         for (uint32_t k = 0; k < kSeenMergeAddChunks; k++) {
             const uint64_t w = b * kSeenMergeAddChunks + k, size = seen_merge_add_size_lane(P, w, lane);
             if (!size) continue;
@@ -71,16 +62,14 @@ __global__ __launch_bounds__(64 * kRowsWaves) void seen_merge_add_kernel(SeenMer
             at += size; added++;
         }
     }
-#pragma unroll
-    for (int d = 32; d; d >>= 1) { added += __shfl_xor(added, d, 64); lost += __shfl_xor(lost, d, 64); }
+    added = wave_sum(added); lost = wave_sum(lost);
     if (lane == 0 && added) seltally_add64(P.set.cursors, added);
     if (lane == 0 && lost) seltally_add64(P.totals + kSeenMergeError, lost);
 }
 
 // One pass over one source: P = the source, held[], the call's totals and the destination (phase: SeenPhase)
 hipError_t seen_merge_launch(const SeenMergeParams& P, int phase, hipStream_t stream) {
-    const SeenSet& S = P.set;
-    if (!S.slots || !S.arena || !S.cursors || S.table_log2 < 1 || S.table_log2 > 41 || S.tag_bits > kSeenMaxTagBits || !P.totals) return hipErrorInvalidValue;
+    if (!seen_set_ok(P.set) || !P.totals) return hipErrorInvalidValue;
     if (P.n == 0) return hipSuccess;
     if (!P.words || !P.src_arena || !P.held || ((uintptr_t)P.src_arena & 7u)) return hipErrorInvalidValue;
     if (phase != kSeenMark && phase != kSeenAdd) return hipErrorInvalidValue;

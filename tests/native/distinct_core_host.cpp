@@ -4,13 +4,10 @@
 // the ballot's popcount added per wavefront and one add to a winner's count per run of neighbouring lanes that found it, until the
 // counter is 0 (a round that does not lower it ends the call with -1), then finalize over every segment with the two totals summed per
 // wavefront.
-#include <stdint.h>
-#include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 #include <vector>
 #define SXD inline
 #include "../../stringsext_amd/csrc/sx_distinct_core.hpp"
+#include "seen_set_host.hpp"      // (sxs_guarded, sxs_unmap: the arenas end where a page without access begins)
 
 constexpr uint32_t kWaves = 8;      // wavefronts per workgroup, as kRowsWaves
 
@@ -100,13 +97,3 @@ extern "C" int sxs_distinct_host(uint32_t n_segs, const void* const* recs, const
 extern "C" uint64_t sxs_distinct_slot(const uint8_t* s, uint32_t len, uint32_t nocase, uint32_t round, uint32_t table_log2) {
     return sx::distinct_slot(sx::distinct_hash(s, len, nocase, round), table_log2);
 }
-
-// `bytes` bytes that end where a page without access begins: a read behind the arena faults
-extern "C" void* sxs_guarded(uint64_t bytes, void** region, uint64_t* region_bytes) {
-    const uint64_t page = (uint64_t)sysconf(_SC_PAGESIZE), body = (bytes + page - 1) / page * page;
-    uint8_t* p = (uint8_t*)mmap(nullptr, body + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (p == MAP_FAILED || mprotect(p + body, page, PROT_NONE) != 0) return nullptr;
-    *region = p; *region_bytes = body + page;
-    return p + body - bytes;
-}
-extern "C" void sxs_unmap(void* region, uint64_t region_bytes) { munmap(region, region_bytes); }

@@ -4,63 +4,8 @@
 // workgroups of 8 wavefronts that strides over the segment, every lane of a wavefront, the totals added per wavefront —, then the
 // host's look at the totals — what is new has to fit, else the call ends with 1 and the set is as it was —, then add over every
 // segment: per wavefront the exclusive prefix of the lanes' entry sizes, one add to each cursor, and the lanes that add.
-// The set takes table_log2 and tag_bits directly: tiny tables make long probe chains, few tag bits make the tags collide.  Its arena
-// ends where a page without access begins, as the sources' arenas do.
+// The set is seen_set_host.hpp's, which distinct_core_host.cpp includes.
 #include "distinct_core_host.cpp"
-
-#include "../../stringsext_amd/csrc/sx_seen_core.hpp"
-
-struct SxsSeen {
-    sx::SeenSet dev;
-    std::vector<uint64_t> slots;
-    uint64_t cursors[2];
-    uint64_t capacity_strings, capacity_bytes;
-    void* region;
-    uint64_t region_bytes;
-};
-
-extern "C" void sxs_seen_reset(SxsSeen* S) {
-    for (uint64_t& slot : S->slots) slot = sx::kSeenEmpty;
-    S->cursors[0] = S->cursors[1] = 0;
-}
-
-// table_log2 < 0: the power of two >= 2 x capacity_strings, at least 2 slots
-extern "C" SxsSeen* sxs_seen_new(int32_t table_log2, uint32_t tag_bits, uint32_t nocase, uint64_t capacity_strings, uint64_t capacity_bytes) {
-    SxsSeen* S = new SxsSeen;
-    uint32_t log2 = 1;
-    if (table_log2 >= 0) log2 = (uint32_t)table_log2;
-    else while (((uint64_t)1 << log2) < 2 * capacity_strings) log2++;
-    S->slots.resize((size_t)1 << log2);
-    S->capacity_strings = capacity_strings; S->capacity_bytes = capacity_bytes;
-    uint8_t* arena = (uint8_t*)sxs_guarded(capacity_bytes ? capacity_bytes : 8, &S->region, &S->region_bytes);
-    if (!arena) { delete S; return nullptr; }
-    S->dev = sx::SeenSet{ S->slots.data(), arena, S->cursors, log2, tag_bits, nocase, 0u };
-    sxs_seen_reset(S);
-    return S;
-}
-extern "C" void sxs_seen_free(SxsSeen* S) { sxs_unmap(S->region, S->region_bytes); delete S; }
-
-// out: strings, bytes, capacity_strings, capacity_bytes, table_log2, tag_bits
-extern "C" void sxs_seen_state(const SxsSeen* S, uint64_t* out) {
-    out[0] = S->cursors[0]; out[1] = S->cursors[1]; out[2] = S->capacity_strings; out[3] = S->capacity_bytes; out[4] = S->dev.table_log2; out[5] = S->dev.tag_bits;
-}
-
-// The stored strings, by a walk over the table: per occupied slot its index, its word, its entry's length, and the entry's bytes (all
-// of them, the padding too) appended to `bytes`.  Returns the number of occupied slots, or ~0 if something does not fit.
-extern "C" uint64_t sxs_seen_dump(const SxsSeen* S, uint64_t* slot_of, uint64_t* word_of, uint64_t* len_of, uint64_t cap, uint8_t* bytes, uint64_t bytes_cap) {
-    uint64_t k = 0, at = 0;
-    for (size_t s = 0; s < S->slots.size(); s++) {
-        const uint64_t word = S->slots[s];
-        if (word == sx::kSeenEmpty) continue;
-        const uint8_t* entry = S->dev.arena + (word & (((uint64_t)1 << sx::kSeenOffsetBits) - 1u)) * 8u;
-        const uint64_t len = *(const uint32_t*)entry, padded = (len + 7u) & ~(uint64_t)7u;
-        if (k >= cap || at + padded > bytes_cap || ((const uint32_t*)entry)[1] != 0) return ~(uint64_t)0;
-        slot_of[k] = s; word_of[k] = word; len_of[k] = len;
-        memcpy(bytes + at, entry + 8, padded);
-        at += padded; k++;
-    }
-    return k;
-}
 
 // the home slot and the tag of one string, for the tests that plant strings at the end of the table
 extern "C" uint64_t sxs_seen_home(const uint8_t* s, uint32_t len, uint32_t nocase, uint32_t table_log2) {
@@ -75,7 +20,7 @@ extern "C" uint64_t sxs_seen_tag(const uint8_t* s, uint32_t len, uint32_t nocase
 // One call.  The segments as sxs_distinct_host takes them; distinct_log2: its table; groups: the grid of every pass.  labels[s]: ns[s]
 // words.  info: findings, distinct, repeated, seen_findings, seen_distinct, added_strings, added_bytes, rounds, table_log2 (the distinct
 // pass's).  Returns 0; 1 what is new does not fit (nothing was added; info holds what the mark pass counted, added_* = what would have
-// been); -1, -2 as sxs_distinct_host; -3 a probe walked every slot; -4 a lane behind the last record was seen, first or adding.
+// been); -1, -2 as sxs_distinct_host; -3 a probe walked every slot, or an adder found no slot; -4 a lane behind the last record was seen, first or adding.
 extern "C" int sxs_seen_call(SxsSeen* S, uint32_t n_segs, const void* const* recs, const uint8_t* const* arenas, const uint64_t* ns, const int32_t* packed,
                              int32_t distinct_log2, uint32_t groups, uint32_t lookup_only, uint64_t* const* labels, uint64_t* info) {
     uint64_t dinfo[5], left[1];
@@ -94,7 +39,7 @@ extern "C" int sxs_seen_call(SxsSeen* S, uint32_t n_segs, const void* const* rec
         const uint64_t waves = (P.n + sx::kSelectRecs - 1) / sx::kSelectRecs;
         for (uint32_t g = 0; g < groups; g++)
             for (uint32_t wv = 0; wv < kWaves; wv++) {
-                uint64_t findings = 0, classes = 0, fresh = 0, fresh_bytes = 0;
+                uint64_t findings = 0, classes = 0, fresh = 0, fresh_bytes = 0, lost = 0;
                 for (uint64_t w = (uint64_t)g * kWaves + wv; w < waves; w += (uint64_t)groups * kWaves) {
                     if (kernel == 0) {
                         for (uint32_t lane = 0; lane < sx::kSelectRecs; lane++) {
@@ -113,10 +58,10 @@ extern "C" int sxs_seen_call(SxsSeen* S, uint32_t n_segs, const void* const* rec
                         all += bytes[lane]; adders += bytes[lane] != 0;
                     }
                     if (!adders) continue;
-                    uint64_t at = sx::seen_fetch_add64(P.set.cursors + 1, all);      // (lane 0's two adds)
+                    uint64_t at = sx::seen_fetch_add64(P.set.cursors + 1, all);      // (wave_reserve: lane 0's add; and its add to the string cursor)
                     sx::seltally_add64(P.set.cursors, adders);
                     for (uint32_t lane = 0; lane < sx::kSelectRecs; lane++) {
-                        if (bytes[lane]) sx::seen_add_lane(P, w, lane, at);
+                        if (bytes[lane] && !sx::seen_add_lane(P, w, lane, at)) lost++;
                         at += bytes[lane];
                     }
                 }
@@ -124,6 +69,7 @@ extern "C" int sxs_seen_call(SxsSeen* S, uint32_t n_segs, const void* const* rec
                 if (classes) sx::seltally_add64(P.totals + sx::kSeenClasses, classes);
                 if (fresh) sx::seltally_add64(P.totals + sx::kSeenNewClasses, fresh);
                 if (fresh_bytes) sx::seltally_add64(P.totals + sx::kSeenNewBytes, fresh_bytes);
+                if (lost) sx::seltally_add64(P.totals + sx::kSeenError, lost);
             }
     };
     for (uint32_t s = 0; s < n_segs; s++) launch(0, of(s));
@@ -137,5 +83,6 @@ extern "C" int sxs_seen_call(SxsSeen* S, uint32_t n_segs, const void* const* rec
     if (S->cursors[0] + totals[sx::kSeenNewClasses] > S->capacity_strings || S->cursors[1] + totals[sx::kSeenNewBytes] > S->capacity_bytes) return 1;
     if (totals[sx::kSeenNewClasses])
         for (uint32_t s = 0; s < n_segs; s++) launch(1, of(s));
+    if (totals[sx::kSeenError]) return -3;
     return bad ? -4 : 0;
 }

@@ -194,12 +194,17 @@ def trip_words():
     return cus * constant("kSeenMergeGroupsPerCu") * constant("kRowsWaves") * 64
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 129])
+ADD_TRIP = constant("kSeenMergeAddChunks") * constant("kSelectRecs")      # the source words of one trip of seen_merge_add_kernel's wavefront: 512
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 129, ADD_TRIP - 1, ADD_TRIP, ADD_TRIP + 1])
 def test_list_sources_around_a_wavefront(scans, n):
     s1, _ = scans
     a = held_of(s1)
     new = [b"list string %d" % k + b"." * (k % 9) for k in range(n)]
-    ss = s1.sc.seen_set(len(a) + 200, size_of(a)["bytes"] + 200 * 40)
+    room = max(200, n)                                                    # (an entry of these strings has 40 bytes at most)
+    assert max(entry_bytes(len(s)) for s in new) <= 40
+    ss = s1.sc.seen_set(len(a) + room, size_of(a)["bytes"] + room * 40)
     try:
         s1.res.seen_device(ss).free()
         held = {new[0], new[n // 2], new[-1]}

@@ -19,7 +19,7 @@ from test_select_core import lay_out, records, text
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE = os.path.join(ROOT, "tests", "native")
 CSRC = os.path.join(ROOT, "stringsext_amd", "csrc")
-DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h"), os.path.join(NATIVE, "distinct_core_host.cpp")] + [os.path.join(CSRC, f) for f in (
+DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h"), os.path.join(NATIVE, "distinct_core_host.cpp"), os.path.join(NATIVE, "seen_set_host.hpp")] + [os.path.join(CSRC, f) for f in (
     "sx_seen_core.hpp", "sx_distinct_core.hpp", "sx_select_core.hpp", "sx_seltally_core.hpp")]
 FIRST, REPEATED, SEEN, SHIFT = sx.SX_DISTINCT_FIRST, sx.SX_DISTINCT_REPEATED, sx.SX_DISTINCT_SEEN, sx.SX_DISTINCT_COUNT_SHIFT
 INFO = ("findings", "distinct", "repeated", "seen_findings", "seen_distinct", "added_strings", "added_bytes", "rounds", "table_log2")
@@ -238,6 +238,22 @@ def test_tables_of_two_and_of_four_slots(core, tag_bits):
             assert [s for _, _, s in dump] == [a]
             _, _, dump = run_sequence(core, four, (3, 256), 2, tag_bits, packed=packed, layout=layout, n_segs=n_segs)
             assert sorted(s for _, _, s in dump) == sorted([a, b, c]) and len({slot for slot, _, _ in dump}) == 3
+
+
+@pytest.mark.parametrize("tag_bits", TAGS)
+def test_an_adder_that_finds_no_slot_is_an_error(core, tag_bits):
+    """Three pairwise different new strings in ONE call into an empty set whose table was given 2 slots, with room for 3 strings: the mark
+    pass meets only empty slots, so the call reaches the add pass, whose third claim walks both slots and finds none.  The call answers
+    -3, as a merge does; it used to answer 0 over cursors that said 3 strings and a table that held 2."""
+    hs = HostSet(core, 3, 256, 1, tag_bits)
+    try:
+        rc, words, info = hs.call([[b"alpha", b"beta", b"gamma gamma"]])
+        st = hs.state()
+        print("rc", rc, "cursor strings", st["strings"], "occupied slots", len(hs.dump()))
+        assert rc == -3
+        assert (info["seen_findings"], info["added_strings"]) == (0, 3)      # mark saw nothing and counted three new classes
+    finally:
+        hs.free()
 
 
 def test_a_probe_that_wraps_around_the_end_of_the_table(core):

@@ -9,3 +9,4 @@ def test_the_two_seen_kernels_are_there_with_no_scratch_no_spills_and_no_lds():
     for k, v in rows.items():
         assert v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (k, v)
         assert v["LDS Size [bytes/block]"] == 0, (k, v)                          # kSeenGroupsPerCu rests on it
+        assert v["Occupancy [waves/SIMD]"] >= 8, (k, v)                          # 8 x 4 SIMDs: the 32 wavefronts per CU of the grid

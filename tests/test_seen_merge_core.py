@@ -13,10 +13,13 @@ import subprocess
 
 import pytest
 
+import test_seen_core
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE = os.path.join(ROOT, "tests", "native")
 CSRC = os.path.join(ROOT, "stringsext_amd", "csrc")
-DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h")] + [os.path.join(CSRC, f) for f in (
+DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h")] + [os.path.join(NATIVE, f) for f in (
+    "seen_core_host.cpp", "distinct_core_host.cpp", "seen_set_host.hpp")] + [os.path.join(CSRC, f) for f in (
     "sx_seen_merge_core.hpp", "sx_seen_core.hpp", "sx_distinct_core.hpp", "sx_select_core.hpp", "sx_seltally_core.hpp")]
 EMPTY = (1 << 64) - 1             # kSeenEmpty
 OFFSET_BITS = 40                  # kSeenOffsetBits
@@ -92,17 +95,23 @@ def core():
         os.replace(tmp, out)
     L = C.CDLL(out)
     u64p, vp = C.POINTER(C.c_uint64), C.c_void_p
-    L.sxm_set_new.restype, L.sxm_set_new.argtypes = vp, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]
-    L.sxm_set_free.restype, L.sxm_set_free.argtypes = None, [vp]
-    L.sxm_set_state.restype, L.sxm_set_state.argtypes = None, [vp, u64p]
-    L.sxm_set_raw.restype, L.sxm_set_raw.argtypes = None, [vp, u64p, C.c_char_p]
-    L.sxm_set_dump.restype, L.sxm_set_dump.argtypes = C.c_uint64, [vp, u64p, u64p, u64p, C.c_uint64, C.c_char_p, C.c_uint64]
+    L.sxs_seen_new.restype, L.sxs_seen_new.argtypes = vp, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]
+    L.sxs_seen_free.restype, L.sxs_seen_free.argtypes = None, [vp]
+    L.sxs_seen_state.restype, L.sxs_seen_state.argtypes = None, [vp, u64p]
+    L.sxs_seen_raw.restype, L.sxs_seen_raw.argtypes = None, [vp, u64p, C.c_char_p]
+    L.sxs_seen_dump.restype, L.sxs_seen_dump.argtypes = C.c_uint64, [vp, u64p, u64p, u64p, C.c_uint64, C.c_char_p, C.c_uint64]
     L.sxm_list_new.restype, L.sxm_list_new.argtypes = vp, [u64p, C.c_uint64, C.c_char_p, C.c_uint64]
     L.sxm_list_free.restype, L.sxm_list_free.argtypes = None, [vp]
     L.sxm_hash_bytes.restype, L.sxm_hash_bytes.argtypes = C.c_uint64, [C.c_char_p, C.c_uint32, C.c_uint32]
     L.sxm_hash_entry.restype, L.sxm_hash_entry.argtypes = C.c_uint64, [C.c_char_p, C.c_uint32, C.c_uint32]
     L.sxm_merge_list.restype, L.sxm_merge_list.argtypes = C.c_int, [vp, vp, C.c_uint32, C.c_uint32, u64p, u64p]
     L.sxm_merge_set.restype, L.sxm_merge_set.argtypes = C.c_int, [vp, vp, C.c_uint32, C.c_uint32, u64p, u64p]
+    # the result path's call on the same set (seen_core_host.cpp is in this library)
+    vpp = C.POINTER(C.c_void_p)
+    L.sxs_seen_call.restype = C.c_int
+    L.sxs_seen_call.argtypes = [vp, C.c_uint32, vpp, vpp, u64p, C.POINTER(C.c_int32), C.c_int32, C.c_uint32, C.c_uint32, vpp, u64p]
+    L.sxs_guarded.restype, L.sxs_guarded.argtypes = C.c_void_p, [C.c_uint64, C.POINTER(C.c_void_p), u64p]
+    L.sxs_unmap.restype, L.sxs_unmap.argtypes = None, [C.c_void_p, C.c_uint64]
     return L
 
 
@@ -111,22 +120,22 @@ class HostSet:
 
     def __init__(self, L, capacity_strings, capacity_bytes, table_log2=-1, tag_bits=24, nocase=False):
         self.L, self.nocase = L, nocase
-        self.h = L.sxm_set_new(table_log2, tag_bits, int(nocase), capacity_strings, capacity_bytes)
+        self.h = L.sxs_seen_new(table_log2, tag_bits, int(nocase), capacity_strings, capacity_bytes)
         assert self.h
 
     def free(self):
-        self.L.sxm_set_free(self.h)
+        self.L.sxs_seen_free(self.h)
 
     def state(self):
         out = (C.c_uint64 * 6)()
-        self.L.sxm_set_state(self.h, out)
+        self.L.sxs_seen_state(self.h, out)
         return dict(zip(("strings", "bytes", "capacity_strings", "capacity_bytes", "table_log2", "tag_bits"), out))
 
     def raw(self):
         """the set's memory as it lies: (cursors, slots, arena)"""
         st = self.state()
         slots, arena = (C.c_uint64 * (1 << st["table_log2"]))(), C.create_string_buffer(max(1, st["capacity_bytes"]))
-        self.L.sxm_set_raw(self.h, slots, arena)
+        self.L.sxs_seen_raw(self.h, slots, arena)
         return (st["strings"], st["bytes"]), list(slots), arena.raw[:st["capacity_bytes"]]
 
     def dump(self):
@@ -135,7 +144,7 @@ class HostSet:
         cap = 1 << st["table_log2"]
         slot, word, ln = (C.c_uint64 * cap)(), (C.c_uint64 * cap)(), (C.c_uint64 * cap)()
         buf = C.create_string_buffer(st["bytes"] + 8)
-        n = self.L.sxm_set_dump(self.h, slot, word, ln, cap, buf, st["bytes"] + 8)
+        n = self.L.sxs_seen_dump(self.h, slot, word, ln, cap, buf, st["bytes"] + 8)
         assert n <= cap, "an entry that does not fit what the cursor says, or whose second word is not 0"
         out, at = [], 0
         for k in range(n):
@@ -144,6 +153,8 @@ class HostSet:
             out.append((slot[k], word[k], buf.raw[at:at + ln[k]]))
             at += padded
         return out
+
+    call = test_seen_core.HostSet.call      # the result path's call (distinct, mark, add) on this very set: (code, words, info)
 
     def merge(self, src, add=True, groups=2):
         """src: a HostSet (its slot table is the source) or (words, arena); (the harness's code, info as a dict, held per source word)"""
@@ -246,6 +257,54 @@ def test_merges_against_python_sets(core, table_log2, tag_bits, nocase):
     assert ("identical", False, True) in seen_cases and ("empty destination", True, False) in seen_cases
     if room >= 2:
         assert ("disjoint", True, False) in seen_cases and ("overlap", True, True) in seen_cases and ("subset", False, True) in seen_cases
+
+
+@pytest.mark.parametrize("nocase", [False, True])
+@pytest.mark.parametrize("tag_bits", TAGS)
+@pytest.mark.parametrize("table_log2", [1, 2, None])
+def test_the_result_path_and_the_merge_path_agree_about_one_set(core, table_log2, tag_bits, nocase):
+    """What the result path's add put into a set, the merge path's lookup finds — held[] bit for bit over a list source of POOL —, and
+    what the merge path's add put into a set, a following result call marks SX_DISTINCT_SEEN: exactly the model's strings, the model
+    being a Python set."""
+    rng = random.Random(300 + tag_bits)
+    key = fold if nocase else (lambda s: s)
+    pool = sorted({key(s) for s in POOL})                                    # what a source may hold: pairwise different, folded
+    room = len(pool) - 4 if table_log2 is None else (1 << table_log2) - 1     # (some of POOL stay outside: held[] and SEEN have both values)
+    findings = list(POOL) + rng.sample(POOL, 9)                              # a result: every string, some twice, unfolded
+    rng.shuffle(findings)
+    put, model = [], set()                                                   # the findings a result call adds: `room` classes
+    for s in findings:
+        if key(s) in model or len(model) < room:
+            put.append(s)
+            model.add(key(s))
+    assert len(model) == room
+    cap_b = sum(entry_bytes(len(s)) for s in model)
+    log2 = legal_log2(room) if table_log2 is None else table_log2
+    # the result path fills, the merge path looks up
+    hs = HostSet(core, room, cap_b, log2, tag_bits, nocase)
+    try:
+        rc, _, info = hs.call([put], rng=rng)
+        assert rc == 0 and info["added_strings"] == room, (rc, info)
+        check(hs, model)
+        merge_and_check(hs, model, pool, add=False, rng=rng)                 # held[] per source word against the model, info, nothing written
+        merge_and_check(hs, model, pool, add=False, rng=rng, empties=2, high_bits=True, groups=3)
+    finally:
+        hs.free()
+    # the merge path fills, the result path looks up
+    hs = HostSet(core, room, cap_b, log2, tag_bits, nocase)
+    try:
+        merge_and_check(hs, set(), model, rng=rng)
+        m = test_seen_core.Model(nocase)
+        m.held = set(model)
+        want, want_info = m.call(findings, add=False)
+        rc, got, info = hs.call([findings], add=False, rng=rng)
+        assert rc == 0 and got == want, [(s, hex(g), hex(w)) for s, g, w in zip(findings, got, want) if g != w][:5]
+        assert {f: info[f] for f in want_info} == want_info
+        assert [bool(w & test_seen_core.SEEN) for w in got] == [key(s) in model for s in findings]
+        assert any(key(s) in model for s in findings) and any(key(s) not in model for s in findings)
+        check(hs, model)
+    finally:
+        hs.free()
 
 
 @pytest.mark.parametrize("nocase", [False, True])

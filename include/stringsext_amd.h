@@ -850,15 +850,16 @@ int  sx_result_distinct_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, 
  * Sources, refusals and lifetime are exactly sx_result_distinct_device's — SX_E_STATE where that refuses —: r is read and never moved,
  * no result or selection block is written, no selection ages.  SX_E_INVALID also: a NULL set, flags other than 0 or
  * SX_SEEN_LOOKUP_ONLY, a set on another device.  Not thread-safe: one call per set at a time, and no reset or info during it.
- * Not built: removing strings, a count per stored string over the stream, Unicode folding, sharded entry points.  (Growth, saving
- * and loading a set, and a list of strings as the source: below.) */
+ * Not built: removing strings, Unicode folding, sharded entry points.  (Growth, saving and loading a set, and a list of strings as
+ * the source: below.  A count per stored string over the stream: SX_SEEN_COUNTED, further below.) */
 typedef struct sx_seen_set sx_seen_set;         /* the slots, the entries and their cursors, in HBM */
 enum { SX_DISTINCT_SEEN = 4u };                 /* bit 2 of a word made by sx_result_seen_device */
 #define SX_SEEN_LOOKUP_ONLY 0x100u              /* call flag: mark, add nothing */
 #define SX_SEEN_ENTRY_BYTES(len) (8u + (((uint64_t)(len) + 7u) & ~(uint64_t)7u))
 typedef struct sx_seen_set_info {
     uint64_t strings, bytes, capacity_strings, capacity_bytes;
-    uint32_t table_log2, nocase, tag_bits, reserved;
+    uint32_t table_log2, nocase, tag_bits;
+    uint32_t counted;                           /* 1: the set was made with SX_SEEN_COUNTED (below), else 0 */
 } sx_seen_set_info;
 typedef struct sx_seen_info {
     uint64_t findings, distinct, repeated;      /* as sx_distinct_info */
@@ -907,7 +908,7 @@ int  sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, ui
  * offsets that decrease.  Capacity as sx_seen_set_merge.
  * All of them but the two host-only blob calls refuse a host-only context (SX_E_STATE), age no selection and write no result or
  * selection block; like every call on a set they are not thread-safe per set.
- * Not built: removing strings, a count per stored string, canonical (sorted) blobs, Unicode folding, sharded entry points. */
+ * Not built: removing strings, canonical (sorted) blobs, Unicode folding, sharded entry points. */
 typedef struct sx_seen_merge_info { uint64_t source_strings, already_held, added_strings, added_bytes; } sx_seen_merge_info;
 typedef struct sx_seen_blob_info  { uint64_t strings, bytes; uint32_t nocase, version; } sx_seen_blob_info;
 #define SX_SEEN_BLOB_HEADER_BYTES 64u
@@ -920,6 +921,55 @@ int  sx_seen_blob_info_get(const void* blob, uint64_t len, sx_seen_blob_info* ou
 int  sx_seen_set_import(sx_ctx* ctx, const void* blob, uint64_t len, uint64_t capacity_strings, uint64_t capacity_bytes, sx_seen_set** out);
 int  sx_seen_set_add_strings(sx_ctx* ctx, sx_seen_set* set, const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
                              uint32_t flags, uint8_t* held_out, sx_seen_merge_info* info);
+
+/* A SEEN SET THAT COUNTS: how many results held each string, and how often — which strings occur in at least k of the N files
+ * scanned so far, which occur in this file and in no more than one other, `sort | uniq -c` over a stream (csrc/sx_seen_count_core.hpp,
+ * csrc/sx_seen_count_dev.hip).
+ * sx_seen_set_create with SX_SEEN_COUNTED (ORed with SX_SELECT_ASCII_NOCASE or not) makes a set that owns one more array in HBM: a
+ * 64-bit COUNT WORD per slot of its table —
+ *   bits 0..31   (word >> SX_SEEN_RESULTS_SHIFT)  & 0xFFFFFFFF   results:  the calls that held the string
+ *   bits 32..63  (word >> SX_SEEN_FINDINGS_SHIFT) & 0xFFFFFFFF   findings: the findings (or list members) equal to it over those calls
+ * — both saturating at 2^32 - 1, each on its own.  sx_seen_set_info.counted says which kind a set is.  A set made without the flag
+ * behaves bit for bit as before and runs no kernel it did not run before.  What each call does to a counted set:
+ *   sx_result_seen_device, adding   for every class C of r under the set's fold, whether the set held it or not: results += 1,
+ *                                   findings += |C| (the class size in the word's high half).  Words and *info are what they are for a
+ *                                   plain set.  SX_SEEN_LOOKUP_ONLY and SX_E_NOMEM leave the counts as they were.
+ *   sx_seen_set_reset               zeroes the counts.
+ *   sx_seen_set_merge(dst, src)     dst counted: for every string of src, dst's counts grow by src's counts, or by (1, 1) if src is
+ *                                   plain; lookup-only leaves them.  dst plain: as before, whatever src is.
+ *   sx_seen_set_grow                keeps the counts.
+ *   sx_seen_set_add_strings         the list is one result: per distinct folded string results += 1, findings += the number of input
+ *                                   strings equal to it.
+ *   sx_seen_set_export              BLOB VERSION 2: the header with version = 2, the entry area as in version 1, then `strings` 64-bit
+ *                                   count words, little-endian, in the order the entries lie in the area; the checksum covers the entry
+ *                                   area followed by the count words; the blob has 64 + bytes + 8 x strings bytes.  A plain set's export
+ *                                   stays version 1, byte for byte.
+ *   sx_seen_blob_info_get           takes both versions (sx_seen_blob_info.version says which); the length rule is the version's, and in
+ *                                   version 2 a count word with results == 0 or findings < results is refused.
+ *   sx_seen_set_import              a version-2 blob gives a counted set with those counts, a version-1 blob a plain set.
+ * The method: behind the add pass one more pass in which the first finding of every class (every entry of a source) looks its string
+ * up — every string of the call is held by then —, gets its slot and adds to the slot's word with a plain load and store: no two lanes
+ * of a call have the same string.  The pass also runs when nothing is new but some class was seen.
+ * sx_result_seen_counts_device: READ THE COUNTS WHERE THE FINDINGS LIE.  *out (sx_labels_free) holds one word per finding of r, laid
+ * out as every other labels object: the count word of the finding's string under the set's fold, or 0 if the set does not hold it.
+ * Lookup-only, no distinct pass.  A plain set: SX_E_INVALID.  Sources, refusals and lifetime are sx_result_seen_device's; no result or
+ * selection block is written and no selection ages.
+ * sx_result_select_labels_range_device: SELECTION BY A FIELD OF A LABEL WORD.  Finding i of r is selected iff
+ *   lo <= ((label_i >> shift) & mask(bits)) <= hi
+ * with 1 <= bits <= 64 and shift + bits <= 64 (else SX_E_INVALID); lo > hi selects nothing.  In everything else the contract of
+ * sx_result_select_labels_device, word for word: the labels' binding to r, the epochs, the output layout, the empty result.  It reads
+ * 8 bytes per record and the records, no string byte.  It takes any labels: on distinct words shift = 32, bits = 32, lo = 5 gives the
+ * strings that occur at least five times in r; on count words shift = SX_SEEN_RESULTS_SHIFT, bits = 32, lo = k the strings at least
+ * k results held.
+ * Not built: removing strings, counts per Mission, canonical (sorted) blobs, Unicode folding, sharded entry points, an accessor to
+ * the raw count table for hosts that stay on the GPU. */
+#define SX_SEEN_COUNTED 0x200u                  /* sx_seen_set_create flag: the set counts */
+#define SX_SEEN_RESULTS_SHIFT 0
+#define SX_SEEN_FINDINGS_SHIFT 32
+#define SX_SEEN_BLOB_VERSION_COUNTED 2u
+int  sx_result_seen_counts_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, sx_labels** out);
+int  sx_result_select_labels_range_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels, uint32_t shift, uint32_t bits,
+                                          uint64_t lo, uint64_t hi, sx_result** out);
 
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);

@@ -28,6 +28,8 @@ SX_LABEL_NEVER = (1 << 64) - 1   # sx_label_set_read: first[p] of a pattern with
 SX_DISTINCT_FIRST, SX_DISTINCT_REPEATED, SX_DISTINCT_COUNT_SHIFT = 1, 2, 32   # sx_result_distinct_device (Result.distinct_device): a word's bits
 SX_DISTINCT_SEEN, SX_SEEN_LOOKUP_ONLY = 4, 0x100   # sx_result_seen_device (Result.seen_device): bit 2 of a word, and the call flag "mark, add nothing"
 SX_SEEN_BLOB_HEADER_BYTES, SX_SEEN_BLOB_VERSION = 64, 1   # sx_seen_set_export (SeenSet.export): the header of a saved set
+# a set that counts (Scanner.seen_set(counted=True)): the create flag, the two halves of a count word, and its blob's version
+SX_SEEN_COUNTED, SX_SEEN_RESULTS_SHIFT, SX_SEEN_FINDINGS_SHIFT, SX_SEEN_BLOB_VERSION_COUNTED = 0x200, 0, 32, 2
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -54,6 +56,7 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_result_label_device", "sx_labels_segment_device", "sx_labels_segments", "sx_labels_free", "sx_result_select_labels_device", "sx_result_distinct_device",
            "sx_seen_set_create", "sx_seen_set_info_get", "sx_seen_set_reset", "sx_seen_set_free", "sx_result_seen_device",
            "sx_seen_set_merge", "sx_seen_set_grow", "sx_seen_set_export_size", "sx_seen_set_export", "sx_seen_blob_info_get", "sx_seen_set_import", "sx_seen_set_add_strings",
+           "sx_result_seen_counts_device", "sx_result_select_labels_range_device",
            "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
@@ -215,7 +218,7 @@ class DistinctInfo(C.Structure):   # sx_distinct_info
 
 class SeenSetInfo(C.Structure):   # sx_seen_set_info
     _fields_ = [("strings", C.c_uint64), ("bytes", C.c_uint64), ("capacity_strings", C.c_uint64), ("capacity_bytes", C.c_uint64),
-                ("table_log2", C.c_uint32), ("nocase", C.c_uint32), ("tag_bits", C.c_uint32), ("reserved", C.c_uint32)]
+                ("table_log2", C.c_uint32), ("nocase", C.c_uint32), ("tag_bits", C.c_uint32), ("counted", C.c_uint32)]
 
 
 class SeenInfo(C.Structure):   # sx_seen_info
@@ -347,6 +350,8 @@ def lib():
     L.sx_seen_blob_info_get.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(SeenBlobInfo)]
     L.sx_seen_set_import.argtypes = [vp, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp)]
     L.sx_seen_set_add_strings.argtypes = [vp, vp, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.c_char_p, C.POINTER(SeenMergeInfo)]
+    L.sx_result_seen_counts_device.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.sx_result_select_labels_range_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(vp)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -595,6 +600,36 @@ class Result:
         labels.info = {k: getattr(info, k) for k, _ in SeenInfo._fields_}
         return labels
 
+    def seen_counts_device(self, seen_set):
+        """sx_result_seen_counts_device: for every finding of this Result the count word of its string in `seen_set` (a SeenSet made
+        with counted=True) under the set's fold — (word >> SX_SEEN_RESULTS_SHIFT) & 0xFFFFFFFF how many results held it,
+        (word >> SX_SEEN_FINDINGS_SHIFT) & 0xFFFFFFFF how many findings they held of it — or 0 if the set does not hold it: Labels,
+        which download(), free() and select like any other.  The set is only read and no distinct pass runs.  Raises SxError:
+        SX_E_INVALID for a set that does not count or is freed, SX_E_STATE wherever distinct_device() would refuse this Result."""
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        if not isinstance(seen_set, SeenSet) or not seen_set.h:
+            raise SxError(SX_E_INVALID, "the SeenSet has been freed" if isinstance(seen_set, SeenSet) else "seen_counts_device takes a SeenSet")
+        out = C.c_void_p()
+        self._s._chk(lib().sx_result_seen_counts_device(self._s.h, self.h, seen_set.h, C.byref(out)))
+        return Labels(self._s, out)
+
+    def select_range_device(self, labels, shift, bits, lo, hi):
+        """sx_result_select_labels_range_device: the findings whose label word has lo <= ((word >> shift) & mask(bits)) <= hi, out of
+        the Labels made of THIS Result (1 <= bits <= 64, shift + bits <= 64; lo > hi selects nothing): a new Result on the device, as
+        select_device(labels, ...) gives one.  On distinct_device() words shift=32, bits=32, lo=5 are the strings that occur at least
+        five times in this Result; on seen_counts_device() words shift=SX_SEEN_RESULTS_SHIFT, bits=32, lo=k the strings at least k
+        results held.  No string byte is read.  Labels of another Result, or a bad field: SxError SX_E_INVALID."""
+        if not isinstance(labels, Labels):
+            raise TypeError("select_range_device takes Labels")
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        if not (0 <= shift < 1 << 32 and 0 <= bits < 1 << 32 and 0 <= lo < 1 << 64 and 0 <= hi < 1 << 64):
+            raise SxError(SX_E_INVALID, "select_range_device: shift and bits are 32-bit, lo and hi 64-bit unsigned numbers")
+        out = C.c_void_p()
+        self._s._chk(lib().sx_result_select_labels_range_device(self._s.h, self.h, labels._handle(), shift, bits, lo, hi, C.byref(out)))
+        return Result(self._s, out)
+
     def free(self):
         if self.h:
             lib().sx_result_free(self.h)
@@ -790,8 +825,28 @@ class SeenSet(_DeviceHandle):
         self.h, self._s = handle, scanner
 
     def info(self):
-        """sx_seen_set_info as a dict: strings, bytes (what it holds), capacity_strings, capacity_bytes, table_log2, nocase, tag_bits"""
-        return self._info_dict()
+        """sx_seen_set_info as a dict: strings, bytes (what it holds), capacity_strings, capacity_bytes, table_log2, nocase, tag_bits
+        (whether it counts: the property `counted`)"""
+        return {k: v for k, v in self._info_dict().items() if k != "counted"}
+
+    @property
+    def counted(self):
+        """the set was made with counted=True (SX_SEEN_COUNTED), or loaded from such a set's blob"""
+        return bool(self._info().counted)
+
+    def counts(self):
+        """{string: (results, findings)} of a set that counts — how many results held the string, and how many findings they held of
+        it —, parsed from export(); SxError SX_E_INVALID for a set that does not count"""
+        if not self.counted:
+            raise SxError(SX_E_INVALID, "the SeenSet was made without counted=True")
+        blob = self.export()
+        strings = self._strings_of(blob)
+        at = len(blob) - 8 * len(strings)
+        out = {}
+        for k, x in enumerate(strings):
+            word = int.from_bytes(blob[at + 8 * k:at + 8 * k + 8], "little")
+            out[x] = (word >> SX_SEEN_RESULTS_SHIFT & 0xFFFFFFFF, word >> SX_SEEN_FINDINGS_SHIFT & 0xFFFFFFFF)
+        return out
 
     def reset(self):
         """the set is empty again; its capacity is kept"""
@@ -843,8 +898,13 @@ class SeenSet(_DeviceHandle):
 
     def strings(self):
         """the strings the set holds — folded, if it folds — in the order of their entries: parsed from export()"""
-        blob, out, at = self.export(), [], SX_SEEN_BLOB_HEADER_BYTES
-        while at < len(blob):
+        return self._strings_of(self.export())
+
+    @staticmethod
+    def _strings_of(blob):
+        out, at = [], SX_SEEN_BLOB_HEADER_BYTES
+        end = SX_SEEN_BLOB_HEADER_BYTES + int.from_bytes(blob[24:32], "little")      # (behind the entries: a counting set's count words)
+        while at < end:
             n = int.from_bytes(blob[at:at + 4], "little")
             out.append(blob[at + 8:at + 8 + n])
             at += 8 + (n + 7) // 8 * 8
@@ -981,17 +1041,19 @@ class Scanner:
         self._chk(lib().sx_label_set_create(self.h, arr, n, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
         return LabelSet(out, n)
 
-    def seen_set(self, capacity_strings, capacity_bytes, ignore_case=False):
+    def seen_set(self, capacity_strings, capacity_bytes, ignore_case=False, counted=False):
         """sx_seen_set_create: an empty SeenSet for capacity_strings strings whose entries take capacity_bytes at most — a string of
         n bytes takes 8 + n rounded up to a multiple of 8 —; ignore_case: the set folds 'A'..'Z' to 'a'..'z', and so does every
-        Result.seen_device() call that takes it."""
+        Result.seen_device() call that takes it.  counted (SX_SEEN_COUNTED): the set also counts, per string, the results that held it
+        and their findings of it: SeenSet.counts(), Result.seen_counts_device()."""
         out = C.c_void_p()
-        self._chk(lib().sx_seen_set_create(self.h, capacity_strings, capacity_bytes, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        flags = (SX_SELECT_ASCII_NOCASE if ignore_case else 0) | (SX_SEEN_COUNTED if counted else 0)
+        self._chk(lib().sx_seen_set_create(self.h, capacity_strings, capacity_bytes, flags, C.byref(out)))
         return SeenSet(out, self)
 
     def seen_set_from(self, blob_or_path, capacity_strings=0, capacity_bytes=0):
         """sx_seen_set_import: a new SeenSet that holds what SeenSet.export() / save() wrote (bytes, or the path of a file), under the
-        blob's fold and this Scanner's SX_SEEN_TAG_BITS.  A capacity of 0: what the blob holds; a smaller one, or a blob that
+        blob's fold and this Scanner's SX_SEEN_TAG_BITS; a counting set's blob (version 2) gives a set that counts, with those counts.  A capacity of 0: what the blob holds; a smaller one, or a blob that
         seen_blob_info() refuses: SxError SX_E_INVALID."""
         blob = _blob_bytes(blob_or_path)
         out = C.c_void_p()

@@ -280,23 +280,27 @@ hipError_t print_write(const PrintParams& P, hipStream_t stream);
 // What pass 1 looks for, one kind: SelectBy::kPatterns = P.pat's patterns (select_match_kernel); kSet = a compiled keyword set —
 // sx_selset_core.hpp —, whose selset_match_kernel then is pass 1: sx_selset_dev.hip; kRegex = a compiled regex set — sx_selre_core.hpp —,
 // selre_match_kernel: sx_selre_dev.hip; kLabels = the segment's labels and three masks — sx_label_core.hpp —, label_pick_kernel:
-// sx_label_dev.hip.  Of P.pat the three read `invert` at most.
+// sx_label_dev.hip; kLabelRange = the segment's labels, a bit field of them and its bounds — sx_seen_count_core.hpp —,
+// label_range_pick_kernel: sx_seen_count_dev.hip.  Of P.pat the three read `invert` at most.
 struct SelectParams;
 struct SelsetDevice;
 struct SelreDevice;
 struct LabelPick;
+struct LabelRange;
 struct SelectBy {
-    enum Kind { kPatterns, kSet, kRegex, kLabels } kind = kPatterns;
+    enum Kind { kPatterns, kSet, kRegex, kLabels, kLabelRange } kind = kPatterns;
     union {
         const SelsetDevice* set = nullptr;
         const SelreDevice* re;
         const LabelPick* pick;
+        const LabelRange* range;
     };
 };
 size_t select_scratch_bytes(uint64_t n);
 hipError_t selset_launch_match(const SelectParams& P, const SelsetDevice& set, uint64_t waves, hipStream_t stream);
 hipError_t selre_launch_match(const SelectParams& P, const SelreDevice& re, uint64_t waves, hipStream_t stream);
 hipError_t label_launch_pick(const SelectParams& P, const LabelPick& pick, uint64_t waves, hipStream_t stream);
+hipError_t label_range_launch_pick(const SelectParams& P, const LabelRange& range, uint64_t waves, hipStream_t stream);
 hipError_t select_measure(SelectParams* P, const SelectBy& by, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t** count, const uint64_t** bytes);
 size_t select_place_scratch_bytes(uint64_t n_sel);
 hipError_t select_place(const SelectParams& P, void* out_recs, uint64_t n_sel, uint8_t* out_arena, void* scratch, size_t scratch_bytes, hipStream_t stream);
@@ -328,13 +332,20 @@ hipError_t distinct_launch(const DistinctParams& P, int phase, hipStream_t strea
 // finalize: mark writes the segment's words and adds to the call's totals, and reads the set; add — behind every segment's mark, once
 // the host has seen that what is new fits — writes the set's entries, slots and cursors, and nothing else
 struct SeenParams;
-enum SeenPhase { kSeenMark = 0, kSeenAdd = 1 };
+enum SeenPhase { kSeenMark = 0, kSeenAdd = 1, kSeenCount = 2, kSeenCountsLookup = 3 };
 hipError_t seen_launch(const SeenParams& P, int phase, hipStream_t stream);
 // A set's entries into a seen set (sx_seen_merge_dev.hip, SeenMergeParams: sx_seen_merge_core.hpp), one pass over one source per
 // launch (phase: SeenPhase): mark writes held[] and adds to the call's totals, and reads the destination; add — once the host has seen
 // that what is new fits — writes the destination's entries, slots and cursors, and the error total
 struct SeenMergeParams;
 hipError_t seen_merge_launch(const SeenMergeParams& P, int phase, hipStream_t stream);
+// A set that counts (sx_seen_count_dev.hip, sx_seen_count_core.hpp).  kSeenCount: behind the add pass of a call that adds to a counted
+// set, one more pass of every segment (seen_count_launch) or over the source (seen_merge_count_launch), which adds to the set's count
+// words, to the counted total behind the call's totals and to the error total, and writes nothing else.  kSeenCountsLookup
+// (seen_count_launch): a segment's words become the count words of its strings; the set is read
+struct SeenMergeCountParams;
+hipError_t seen_count_launch(const SeenParams& P, int phase, hipStream_t stream);
+hipError_t seen_merge_count_launch(const SeenMergeCountParams& C, hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
 hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit

@@ -1,6 +1,6 @@
 // sx_result_api.cpp — the C-ABI of include/stringsext_amd.h for a result that stays in HBM (SX_OPT_RESULT_ON_DEVICE): the print, the
 // selections, the extraction, the tally, the labels, the duplicate strings and the seen set — with its merge, growth, blob and string
-// lists —, and the compiled sets they take.  What the operations share is here once — the view of a segment, a set's upload, a
+// lists, and its counts —, and the compiled sets they take.  What the operations share is here once — the view of a segment, a set's upload, a
 // handle's device and memory, the counters' reset, a buffer that grows, a result's labels, the two passes of whatever writes a new
 // result, the mark and add passes of whatever goes into a seen set —; what tells them apart is in their lane functions
 // (sx_*_core.hpp) and kernels (sx_*_dev.hip).
@@ -20,6 +20,7 @@
 #include "sx_distinct_core.hpp"
 #include "sx_seen_core.hpp"
 #include "sx_seen_merge_core.hpp"
+#include "sx_seen_count_core.hpp"
 #include "sx_seen_blob.hpp"
 
 using namespace sx;
@@ -77,7 +78,7 @@ struct sx_labels : sx_device_handle {
 };
 
 // sx_seen_set_create: strings remembered from result to result; `mem` = [the cursors and a call's totals: kSeenHeadBytes][the slots]
-// [the entries], each 256-byte aligned.  info's strings and bytes are not kept here: the cursors say
+// [the entries][a counted set's count words], each 256-byte aligned.  info's strings and bytes are not kept here: the cursors say
 struct sx_seen_set : sx_device_handle {
     SeenSet dev{};
     sx_seen_set_info info{};
@@ -245,12 +246,14 @@ struct TwoPass {
 };
 
 // grep (sx_select_dev.hip): pass 1 by `by.kind` — the patterns of `pat`, a compiled keyword set, a compiled regex set (of `pat` they
-// read `invert`), or `labels` with masks = { any, all, none }, which reads no string byte —, pass 2 the same for all four
+// read `invert`), `labels` with masks = { any, all, none }, or `labels` with the field and bounds of `range`, neither of which reads a
+// string byte —, pass 2 the same for all five
 struct Selection final : TwoPass {
     SelectBy by;
     SelectPatterns pat{};
     const sx_labels* labels = nullptr;
     uint64_t masks[3] = { 0, 0, 0 };
+    LabelRange range{};
     std::vector<SelectParams> P;
     explicit Selection(size_t ns) : P(ns) {}
     size_t count_bytes() const override { return sizeof(uint32_t); }
@@ -261,6 +264,8 @@ struct Selection final : TwoPass {
         SelectBy b = by;
         LabelPick pick{ nullptr, masks[0], masks[1], masks[2] };
         if (by.kind == SelectBy::kLabels) { pick.labels = labels->segs[i].d; b.pick = &pick; }
+        LabelRange field = range;
+        if (by.kind == SelectBy::kLabelRange) { field.labels = labels->segs[i].d; b.range = &field; }
         return select_measure(&P[i], b, scratch, bytes, st, (const uint32_t**)count, nbytes);
     }
     size_t place_scratch_bytes(uint64_t c) const override { return select_place_scratch_bytes(c); }
@@ -446,29 +451,36 @@ int distinct_on_device(sx_ctx* ctx, const sx_result* r, uint32_t nocase, const c
 // `lost` (a lookup walked every slot), then `full` (what is new does not fit: SX_E_NOMEM BEFORE the add pass, the set is as it was);
 // the caller's add launches, only if adding and something is new; the same read again behind them: the error total — an adder that
 // found no slot — and the cursors, which have to be the sums.  launch(phase): the caller's launches of one pass, kSeenMark / kSeenAdd.
+// A destination that COUNTS (dst.counts) has a third phase, kSeenCount, only when adding: behind the add launches — or in their place
+// when nothing is new but something was held —, in front of that read: every class of the call (held + new) adds to its slot's count
+// word, and the counted total, the word behind the totals, has to be their number.  A plain destination launches what it always did.
 // what: the call's name in a refusal ("seen set", "seen set merge"), err_what: in an error.  tot: the totals as mark left them.
 template <class Launch>
 int seen_mark_add(sx_ctx* ctx, const std::string& what, const std::string& err_what, const SeenSet& dst, uint64_t capacity_strings, uint64_t capacity_bytes,
                   bool add, Launch launch, uint64_t tot[kSeenTotals], const uint64_t* d_held, std::vector<uint64_t>* held) {
     hipStream_t st = ctx->post_stream;
-    uint64_t words[2 + kSeenTotals] = { 0 };      // the cursors, the totals
-    auto read_back = [&] { return hipMemcpyAsync(words, dst.cursors, sizeof words, hipMemcpyDeviceToHost, st); };
-    hipError_t e = hipMemsetAsync(dst.cursors + 2, 0, kSeenTotals * sizeof(uint64_t), st);
+    const bool counts = add && dst.counts != nullptr;
+    const size_t n_words = 2 + kSeenTotals + (counts ? 1u : 0u);      // the cursors, the totals, a counting call's counted total
+    uint64_t words[2 + kSeenTotals + 1] = { 0 };
+    auto read_back = [&] { return hipMemcpyAsync(words, dst.cursors, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, st); };
+    hipError_t e = hipMemsetAsync(dst.cursors + 2, 0, (n_words - 2) * sizeof(uint64_t), st);
     if (e == hipSuccess) e = launch(kSeenMark);
     if (e == hipSuccess) e = read_back();
     if (e == hipSuccess && held && !held->empty()) e = hipMemcpyAsync(held->data(), d_held, held->size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
     { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
     memcpy(tot, words + 2, kSeenTotals * sizeof(uint64_t));
-    const uint64_t had[2] = { words[0], words[1] }, fresh = tot[kSeenNewClasses], fresh_bytes = tot[kSeenNewBytes];
+    const uint64_t had[2] = { words[0], words[1] }, fresh = tot[kSeenNewClasses], fresh_bytes = tot[kSeenNewBytes], classes = tot[kSeenClasses] + fresh;
     bool lost = e == hipSuccess && tot[kSeenError] != 0, added = false;
     const bool full = e == hipSuccess && !lost && add && (had[0] + fresh > capacity_strings || had[1] + fresh_bytes > capacity_bytes);
-    if (e == hipSuccess && !lost && !full && add && fresh) {
+    const bool count = counts && classes != 0;
+    if (e == hipSuccess && !lost && !full && add && (fresh || count)) {
         added = true;
-        e = launch(kSeenAdd);
+        if (fresh) e = launch(kSeenAdd);
+        if (e == hipSuccess && count) e = launch(kSeenCount);
         if (e == hipSuccess) e = read_back();
         const hipError_t e2 = hipStreamSynchronize(st);
         if (e == hipSuccess) e = e2;
-        lost = e == hipSuccess && (words[2 + kSeenError] != 0 || words[0] != had[0] + fresh || words[1] != had[1] + fresh_bytes);
+        lost = e == hipSuccess && (words[2 + kSeenError] != 0 || words[0] != had[0] + fresh || words[1] != had[1] + fresh_bytes || (count && words[2 + kSeenCounted] != classes));
     }
     if (e == hipSuccess && !lost && !full) return SX_OK;
     (void)hipGetLastError();
@@ -476,7 +488,7 @@ int seen_mark_add(sx_ctx* ctx, const std::string& what, const std::string& err_w
         ctx->set_err(what + ": " + std::to_string(had[0]) + " + " + std::to_string(fresh) + " strings of " + std::to_string(capacity_strings) + ", "
                      + std::to_string(had[1]) + " + " + std::to_string(fresh_bytes) + " bytes of " + std::to_string(capacity_bytes) + ": the set is as it was, sx_seen_set_grow gives it room");
     else if (lost)
-        ctx->set_err(err_what + (added ? ": an adder walked every slot of the set and met no empty one, or the cursors are not the sums"
+        ctx->set_err(err_what + (added ? ": an adder walked every slot of the set and met no empty one, the cursors are not the sums, or not every string was counted"
                                        : ": a probe walked every slot of the set and met no empty one"));
     else
         ctx->set_err(err_what + ": " + hipGetErrorString(e));
@@ -855,9 +867,8 @@ int sx_labels_segment_device(const sx_labels* labels, uint64_t segment, const ui
 
 void sx_labels_free(sx_labels* labels) { handle_free(labels); }
 
-int sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels, uint64_t any, uint64_t all, uint64_t none, sx_result** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !r || !labels || !out) return SX_E_INVALID;
+// What both selections by labels ask, the pointers checked: a device, a result in HBM, and labels made from it
+static int labels_of_result(sx_ctx* ctx, const sx_result* r, const sx_labels* labels) {
     if (host_only(ctx, "selection")) return SX_E_STATE;
     if (on_another_device(ctx, *labels, "the labels lie")) return SX_E_INVALID;
     { const int rc = result_on_device(ctx, r, "filter on the host"); if (rc != SX_OK) return rc; }
@@ -869,10 +880,33 @@ int sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_lab
         same = l.recs == s.dev_copy && l.n == s.ext_nf && l.epoch_ref == s.dev_epoch_ref && l.epoch == s.dev_epoch;
     }
     if (!same) { ctx->set_err("the labels were not made from this result"); return SX_E_INVALID; }
+    return SX_OK;
+}
+
+int sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels, uint64_t any, uint64_t all, uint64_t none, sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !labels || !out) return SX_E_INVALID;
+    { const int rc = labels_of_result(ctx, r, labels); if (rc != SX_OK) return rc; }
     Selection sel(r->r.segs.size());
     sel.by.kind = SelectBy::kLabels;
     sel.labels = labels;
     sel.masks[0] = any; sel.masks[1] = all; sel.masks[2] = none;
+    return select_on_device(ctx, r, sel, out);
+}
+
+int sx_result_select_labels_range_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels, uint32_t shift, uint32_t bits, uint64_t lo, uint64_t hi,
+                                         sx_result** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !labels || !out) return SX_E_INVALID;
+    if (bits < 1 || bits > 64 || shift > 64 - bits) {
+        ctx->set_err("select by range: a field of " + std::to_string(bits) + " bits at bit " + std::to_string(shift) + ": 1 to 64 bits that end at bit 64 at most");
+        return SX_E_INVALID;
+    }
+    { const int rc = labels_of_result(ctx, r, labels); if (rc != SX_OK) return rc; }
+    Selection sel(r->r.segs.size());
+    sel.by.kind = SelectBy::kLabelRange;
+    sel.labels = labels;
+    sel.range = LabelRange{ nullptr, lo, hi, shift, bits };
     return select_on_device(ctx, r, sel, out);
 }
 
@@ -888,6 +922,7 @@ int sx_seen_set_reset(sx_seen_set* set) {
     if (hipSetDevice(set->device) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
     hipError_t e = hipMemset(set->mem, 0, kSeenHeadBytes);                                  // the cursors (and the totals of a call)
     if (e == hipSuccess) e = hipMemset(set->dev.slots, 0xFF, sizeof(uint64_t) << set->dev.table_log2);
+    if (e == hipSuccess && set->dev.counts) e = hipMemset(set->dev.counts, 0, sizeof(uint64_t) << set->dev.table_log2);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (as reset_counters: the kernels run on a stream that does not wait for this one)
     if (e != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
     return SX_OK;
@@ -900,11 +935,12 @@ static bool seen_capacity_refused(sx_ctx* ctx, uint64_t capacity_strings, uint64
     return true;
 }
 
-// An empty set of checked capacities on the context's device (nocase: 0 / 1)
-static int seen_set_make(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capacity_bytes, uint32_t nocase, uint32_t tag_bits, sx_seen_set** out) {
+// An empty set of checked capacities on the context's device (nocase: 0 / 1; counted: it gets count words)
+static int seen_set_make(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capacity_bytes, uint32_t nocase, uint32_t tag_bits, bool counted, sx_seen_set** out) {
     uint32_t table_log2 = 1;
     while (((uint64_t)1 << table_log2) < 2 * capacity_strings) table_log2++;
-    const uint64_t table_bytes = sizeof(uint64_t) << table_log2, at_arena = kSeenHeadBytes + up256(table_bytes), bytes = at_arena + up256(capacity_bytes ? capacity_bytes : 1);
+    const uint64_t table_bytes = sizeof(uint64_t) << table_log2, at_arena = kSeenHeadBytes + up256(table_bytes), at_counts = at_arena + up256(capacity_bytes ? capacity_bytes : 1),
+                   bytes = at_counts + (counted ? up256(table_bytes) : 0u);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint8_t* mem = nullptr;
     if (hipMalloc((void**)&mem, bytes) != hipSuccess) {
@@ -914,8 +950,8 @@ static int seen_set_make(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capaci
     }
     sx_seen_set* set = new_handle<sx_seen_set>(ctx, mem);
     if (!set) return SX_E_NOMEM;
-    set->dev = SeenSet{ (uint64_t*)(mem + kSeenHeadBytes), mem + at_arena, (uint64_t*)mem, table_log2, tag_bits, nocase, 0u };
-    set->info = sx_seen_set_info{ 0, 0, capacity_strings, capacity_bytes, table_log2, set->dev.nocase, set->dev.tag_bits, 0 };
+    set->dev = SeenSet{ (uint64_t*)(mem + kSeenHeadBytes), mem + at_arena, (uint64_t*)mem, table_log2, tag_bits, nocase, 0u, counted ? (uint64_t*)(mem + at_counts) : nullptr };
+    set->info = sx_seen_set_info{ 0, 0, capacity_strings, capacity_bytes, table_log2, set->dev.nocase, set->dev.tag_bits, counted ? 1u : 0u };
     if (sx_seen_set_reset(set) != SX_OK) { ctx->set_err("seen set: the slots could not be emptied"); sx_seen_set_free(set); return SX_E_HIP; }
     *out = set;
     return SX_OK;
@@ -924,10 +960,10 @@ static int seen_set_make(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capaci
 int sx_seen_set_create(sx_ctx* ctx, uint64_t capacity_strings, uint64_t capacity_bytes, uint32_t flags, sx_seen_set** out) {
     if (out) *out = nullptr;
     if (!ctx || !out) return SX_E_INVALID;
-    if (flags & ~(uint32_t)SX_SELECT_ASCII_NOCASE) { ctx->set_err("seen set: flags other than SX_SELECT_ASCII_NOCASE"); return SX_E_INVALID; }
+    if (flags & ~(uint32_t)(SX_SELECT_ASCII_NOCASE | SX_SEEN_COUNTED)) { ctx->set_err("seen set: flags other than SX_SELECT_ASCII_NOCASE and SX_SEEN_COUNTED"); return SX_E_INVALID; }
     if (seen_capacity_refused(ctx, capacity_strings, capacity_bytes)) return SX_E_INVALID;
     if (host_only(ctx, "for the seen set")) return SX_E_STATE;
-    return seen_set_make(ctx, capacity_strings, capacity_bytes, flags & SX_SELECT_ASCII_NOCASE ? 1u : 0u, (uint32_t)ctx->sw.seen_tag_bits, out);
+    return seen_set_make(ctx, capacity_strings, capacity_bytes, flags & SX_SELECT_ASCII_NOCASE ? 1u : 0u, (uint32_t)ctx->sw.seen_tag_bits, (flags & SX_SEEN_COUNTED) != 0, out);
 }
 
 // (strings and bytes are the cursors, read where they lie)
@@ -942,7 +978,8 @@ int sx_seen_set_info_get(const sx_seen_set* set, sx_seen_set_info* out) {
 void sx_seen_set_free(sx_seen_set* set) { handle_free(set); }
 
 // The seen set where the findings lie: the distinct pass under the set's fold, as sx_result_distinct_device runs it; then seen_mark_add
-// with every segment's mark and every segment's add.  On any refusal or error the labels are freed.
+// with every segment's mark, every segment's add and, for a set that counts, every segment's count.  On any refusal or error the
+// labels are freed.
 int sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, uint32_t flags, sx_labels** out, sx_seen_info* info) {
     if (out) *out = nullptr;
     if (!ctx || !r || !set || !out) return SX_E_INVALID;
@@ -959,7 +996,7 @@ int sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, uin
             memset(&p, 0, sizeof p);
             p.recs = segs[i].recs; p.arena = segs[i].arena; p.n = segs[i].n; p.packed = segs[i].packed;
             p.labels = (uint64_t*)lab->segs[i].d; p.totals = set->dev.cursors + 2; p.set = set->dev;
-            const hipError_t pe = seen_launch(p, which, ctx->post_stream);
+            const hipError_t pe = which == kSeenCount ? seen_count_launch(p, which, ctx->post_stream) : seen_launch(p, which, ctx->post_stream);
             if (pe != hipSuccess) return pe;
         }
         return hipSuccess;
@@ -968,9 +1005,46 @@ int sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, uin
     uint64_t tot[kSeenTotals];
     const int rc = seen_mark_add(ctx, "seen set", "device seen", set->dev, set->info.capacity_strings, set->info.capacity_bytes, add, pass, tot, nullptr, nullptr);
     if (rc != SX_OK) { sx_labels_free(lab); return rc; }
+    if (add && set->dev.counts && tot[kSeenClasses] + tot[kSeenNewClasses] != di.distinct) {      // (what the count pass was checked against)
+        sx_labels_free(lab);
+        ctx->set_err("device seen: " + std::to_string(tot[kSeenClasses] + tot[kSeenNewClasses]) + " classes were counted, the distinct pass found " + std::to_string(di.distinct));
+        return SX_E_HIP;
+    }
     if (info)
         *info = sx_seen_info{ di.findings, di.distinct, di.repeated, tot[kSeenFindings], tot[kSeenClasses], add ? tot[kSeenNewClasses] : 0u, add ? tot[kSeenNewBytes] : 0u,
                               di.rounds, di.table_log2 };
+    *out = lab;
+    return SX_OK;
+}
+
+// The counts where the findings lie: the words' memory as the labels' is had, then one lookup launch per segment and one read of the
+// error total.  No distinct pass: a word depends on its own record and the set alone.
+int sx_result_seen_counts_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, sx_labels** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !set || !out) return SX_E_INVALID;
+    if (!set->dev.counts) { ctx->set_err("seen counts: the set was made without SX_SEEN_COUNTED"); return SX_E_INVALID; }
+    if (host_only(ctx, "seen counts")) return SX_E_STATE;
+    if (on_another_device(ctx, *set, "the seen set lies")) return SX_E_INVALID;
+    { const int rc = result_on_device(ctx, r, "compare the strings on the host"); if (rc != SX_OK) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    uint64_t bytes = 0, lost = 0;
+    sx_labels* lab = labels_of(ctx, r, &bytes);
+    if (!lab) { ctx->set_err("seen counts: no memory for " + std::to_string(bytes) + " bytes of words"); return SX_E_NOMEM; }
+    hipError_t e = hipMemsetAsync(set->dev.cursors + 2, 0, kSeenTotals * sizeof(uint64_t), st);
+    for (size_t i = 0; e == hipSuccess && i < lab->segs.size(); i++) {
+        SeenParams p = params_of<SeenParams>(seg_ref(r->r.segs[i]));
+        p.labels = (uint64_t*)lab->segs[i].d; p.totals = set->dev.cursors + 2; p.set = set->dev;
+        e = seen_count_launch(p, kSeenCountsLookup, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&lost, set->dev.cursors + 2 + kSeenError, sizeof lost, hipMemcpyDeviceToHost, st);
+    { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
+    if (e != hipSuccess || lost) {
+        (void)hipGetLastError();
+        sx_labels_free(lab);
+        ctx->set_err(e != hipSuccess ? std::string("seen counts: ") + hipGetErrorString(e) : std::string("seen counts: a probe walked every slot of the set and met no empty one"));
+        return SX_E_HIP;
+    }
     *out = lab;
     return SX_OK;
 }
@@ -980,9 +1054,10 @@ struct SeenSource {
     const uint64_t* words;
     const uint8_t* arena;
     uint64_t n;
+    const uint64_t* counts;      // a count word per source word, or NULL: every entry counts (1, 1).  Read only by a destination that counts
 };
 
-// A source into a set: seen_mark_add with the source's one mark launch and one add launch.  dst, capacity_*: the destination; d_held:
+// A source into a set: seen_mark_add with the source's one mark launch, one add launch and, into a set that counts, one count launch.  dst, capacity_*: the destination; d_held:
 // ceil(src.n / 64) words of scratch; what: the call's name in the messages; held (may be NULL): held[] as mark left it.  *info is
 // written for a refused call too: what would have been added.
 static int seen_merge_run(sx_ctx* ctx, const char* what, const SeenSet& dst, uint64_t capacity_strings, uint64_t capacity_bytes, const SeenSource& src,
@@ -993,7 +1068,9 @@ static int seen_merge_run(sx_ctx* ctx, const char* what, const SeenSet& dst, uin
     if (held) held->assign((src.n + kSelectRecs - 1) / kSelectRecs, 0);
     uint64_t tot[kSeenTotals];
     const std::string name = std::string("seen set ") + what;
-    const int rc = seen_mark_add(ctx, name, name, dst, capacity_strings, capacity_bytes, add, [&](int which) { return seen_merge_launch(p, which, ctx->post_stream); }, tot, d_held, held);
+    const int rc = seen_mark_add(ctx, name, name, dst, capacity_strings, capacity_bytes, add, [&](int which) {
+        return which == kSeenCount ? seen_merge_count_launch(SeenMergeCountParams{ p, src.counts }, ctx->post_stream) : seen_merge_launch(p, which, ctx->post_stream);
+    }, tot, d_held, held);
     if (info) *info = sx_seen_merge_info{ tot[kSeenMergeOccupied], tot[kSeenMergeHeld], add ? tot[kSeenNewClasses] : 0u, add ? tot[kSeenNewBytes] : 0u };
     return rc;
 }
@@ -1005,20 +1082,24 @@ static int seen_merge_room(sx_ctx* ctx, const char* what, uint64_t bytes) {
     return SX_E_NOMEM;
 }
 
-// A source the host built — n words, and the arena_bytes of entries they point into — uploaded behind held[] and put into `set`
+// A source the host built — n words, and the arena_bytes of entries they point into — uploaded behind held[] and put into `set`.
+// counts (may be NULL: (1, 1) each): n count words, uploaded behind the entries if the set counts
 static int seen_merge_list(sx_ctx* ctx, const char* what, sx_seen_set* set, const uint64_t* words, uint64_t n, const uint8_t* arena, uint64_t arena_bytes,
-                           bool add, sx_seen_merge_info* info, std::vector<uint64_t>* held) {
+                           const uint64_t* counts, bool add, sx_seen_merge_info* info, std::vector<uint64_t>* held) {
     if (info) *info = sx_seen_merge_info{ 0, 0, 0, 0 };
     if (held) held->clear();
     if (n == 0) return SX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t at_words = up256((n + kSelectRecs - 1) / kSelectRecs * sizeof(uint64_t)), at_arena = at_words + up256(n * sizeof(uint64_t));
-    { const int rc = seen_merge_room(ctx, what, at_arena + up256(arena_bytes)); if (rc != SX_OK) return rc; }
+    if (!set->dev.counts || !add) counts = nullptr;
+    const uint64_t at_counts = at_arena + up256(arena_bytes);
+    { const int rc = seen_merge_room(ctx, what, at_counts + (counts ? up256(n * sizeof(uint64_t)) : 0u)); if (rc != SX_OK) return rc; }
     uint8_t* const d = ctx->d_distinct;
     HIP_TRY(ctx, hipMemcpy(d + at_words, words, n * sizeof(uint64_t), hipMemcpyHostToDevice));      // (done when they return: the kernels' stream need not wait)
     HIP_TRY(ctx, hipMemcpy(d + at_arena, arena, arena_bytes, hipMemcpyHostToDevice));
-    return seen_merge_run(ctx, what, set->dev, set->info.capacity_strings, set->info.capacity_bytes, SeenSource{ (const uint64_t*)(d + at_words), d + at_arena, n },
-                          (uint64_t*)d, add, info, held);
+    if (counts) HIP_TRY(ctx, hipMemcpy(d + at_counts, counts, n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return seen_merge_run(ctx, what, set->dev, set->info.capacity_strings, set->info.capacity_bytes,
+                          SeenSource{ (const uint64_t*)(d + at_words), d + at_arena, n, counts ? (const uint64_t*)(d + at_counts) : nullptr }, (uint64_t*)d, add, info, held);
 }
 
 // A set's slot table as the source
@@ -1027,7 +1108,7 @@ static int seen_merge_set(sx_ctx* ctx, const char* what, const SeenSet& dst, uin
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t n = (uint64_t)1 << src->dev.table_log2;
     { const int rc = seen_merge_room(ctx, what, up256((n + kSelectRecs - 1) / kSelectRecs * sizeof(uint64_t))); if (rc != SX_OK) return rc; }
-    return seen_merge_run(ctx, what, dst, capacity_strings, capacity_bytes, SeenSource{ src->dev.slots, src->dev.arena, n }, (uint64_t*)ctx->d_distinct, add, info, nullptr);
+    return seen_merge_run(ctx, what, dst, capacity_strings, capacity_bytes, SeenSource{ src->dev.slots, src->dev.arena, n, src->dev.counts }, (uint64_t*)ctx->d_distinct, add, info, nullptr);
 }
 
 int sx_seen_set_merge(sx_ctx* ctx, sx_seen_set* dst, const sx_seen_set* src, uint32_t flags, sx_seen_merge_info* info) {
@@ -1053,7 +1134,7 @@ int sx_seen_set_grow(sx_ctx* ctx, sx_seen_set* set, uint64_t capacity_strings, u
         return SX_E_INVALID;
     }
     sx_seen_set* fresh = nullptr;
-    { const int rc = seen_set_make(ctx, capacity_strings, capacity_bytes, set->dev.nocase, set->dev.tag_bits, &fresh); if (rc != SX_OK) return rc; }
+    { const int rc = seen_set_make(ctx, capacity_strings, capacity_bytes, set->dev.nocase, set->dev.tag_bits, set->dev.counts != nullptr, &fresh); if (rc != SX_OK) return rc; }
     sx_seen_merge_info mi{};
     int rc = seen_merge_set(ctx, "grow", fresh->dev, capacity_strings, capacity_bytes, set, true, &mi);
     if (rc == SX_OK && (mi.source_strings != cursors[0] || mi.added_strings != cursors[0] || mi.added_bytes != cursors[1])) {
@@ -1071,7 +1152,7 @@ int sx_seen_set_export_size(const sx_seen_set* set, uint64_t* bytes) {
     if (!set || !bytes) return SX_E_INVALID;
     uint64_t cursors[2];
     { const int rc = read_counters(set->device, set->dev.cursors, cursors, 2); if (rc != SX_OK) return rc; }
-    *bytes = kSeenBlobHeaderBytes + cursors[1];
+    *bytes = kSeenBlobHeaderBytes + cursors[1] + (set->dev.counts ? 8u * cursors[0] : 0u);
     return SX_OK;
 }
 
@@ -1080,11 +1161,31 @@ int sx_seen_set_export(const sx_seen_set* set, void* buf, uint64_t cap, uint64_t
     if (!set || !buf || !written) return SX_E_INVALID;
     uint64_t cursors[2];
     { const int rc = read_counters(set->device, set->dev.cursors, cursors, 2); if (rc != SX_OK) return rc; }
-    if (cap < kSeenBlobHeaderBytes + cursors[1]) return SX_E_INVALID;
+    const bool counted = set->dev.counts != nullptr;
+    const uint64_t size = kSeenBlobHeaderBytes + cursors[1] + (counted ? 8u * cursors[0] : 0u);
+    if (cap < size) return SX_E_INVALID;
     uint8_t* const area = (uint8_t*)buf + kSeenBlobHeaderBytes;
     if (cursors[1] && hipMemcpy(area, set->dev.arena, cursors[1], hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
-    seen_blob_header((uint8_t*)buf, set->dev.nocase, cursors[0], area, cursors[1]);
-    *written = kSeenBlobHeaderBytes + cursors[1];
+    if (counted) {
+        // the count words in the order the entries lie in the area: the slot and count tables as they lie, the occupied slots' (entry
+        // offset, count) pairs sorted by offset on the host
+        try {
+            const uint64_t slots = (uint64_t)1 << set->dev.table_log2;
+            std::vector<uint64_t> words(slots), counts(slots);
+            if (hipMemcpy(words.data(), set->dev.slots, slots * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess
+                || hipMemcpy(counts.data(), set->dev.counts, slots * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return SX_E_HIP; }
+            std::vector<std::pair<uint64_t, uint64_t>> by_offset;
+            for (uint64_t k = 0; k < slots; k++)
+                if (words[k] != kSeenEmpty) by_offset.emplace_back(words[k] & (((uint64_t)1 << kSeenOffsetBits) - 1u), counts[k]);
+            if (by_offset.size() != cursors[0]) return SX_E_HIP;      // (the table holds what the cursor says)
+            std::sort(by_offset.begin(), by_offset.end());
+            for (uint64_t k = 0; k < by_offset.size(); k++) memcpy(area + cursors[1] + 8u * k, &by_offset[k].second, 8);      // (little-endian hosts, as everywhere here)
+        } catch (const std::exception&) {
+            return SX_E_NOMEM;
+        }
+    }
+    seen_blob_header((uint8_t*)buf, set->dev.nocase, cursors[0], area, cursors[1], counted ? SX_SEEN_BLOB_VERSION_COUNTED : SX_SEEN_BLOB_VERSION);
+    *written = size;
     return SX_OK;
 }
 
@@ -1099,9 +1200,9 @@ int sx_seen_set_import(sx_ctx* ctx, const void* blob, uint64_t len, uint64_t cap
     if (!ctx || !blob || !out) return SX_E_INVALID;
     if (host_only(ctx, "for the seen set")) return SX_E_STATE;
     sx_seen_blob_info bi{};
-    std::vector<uint64_t> words;
+    std::vector<uint64_t> words, counts;
     std::string why;
-    { const int rc = seen_blob_check(blob, len, &bi, &words, &why); if (rc != SX_OK) { ctx->set_err("seen set import: " + why); return rc; } }
+    { const int rc = seen_blob_check(blob, len, &bi, &words, &why, &counts); if (rc != SX_OK) { ctx->set_err("seen set import: " + why); return rc; } }
     if (capacity_strings == 0) capacity_strings = bi.strings ? bi.strings : 1;
     if (capacity_bytes == 0) capacity_bytes = bi.bytes;
     if (capacity_strings < bi.strings || capacity_bytes < bi.bytes) {
@@ -1111,9 +1212,10 @@ int sx_seen_set_import(sx_ctx* ctx, const void* blob, uint64_t len, uint64_t cap
     }
     if (seen_capacity_refused(ctx, capacity_strings, capacity_bytes)) return SX_E_INVALID;
     sx_seen_set* set = nullptr;
-    { const int rc = seen_set_make(ctx, capacity_strings, capacity_bytes, bi.nocase, (uint32_t)ctx->sw.seen_tag_bits, &set); if (rc != SX_OK) return rc; }
+    const bool counted = bi.version == SX_SEEN_BLOB_VERSION_COUNTED;
+    { const int rc = seen_set_make(ctx, capacity_strings, capacity_bytes, bi.nocase, (uint32_t)ctx->sw.seen_tag_bits, counted, &set); if (rc != SX_OK) return rc; }
     sx_seen_merge_info mi{};
-    int rc = seen_merge_list(ctx, "import", set, words.data(), words.size(), (const uint8_t*)blob + kSeenBlobHeaderBytes, bi.bytes, true, &mi, nullptr);
+    int rc = seen_merge_list(ctx, "import", set, words.data(), words.size(), (const uint8_t*)blob + kSeenBlobHeaderBytes, bi.bytes, counted ? counts.data() : nullptr, true, &mi, nullptr);
     if (rc == SX_OK && (mi.added_strings != bi.strings || mi.added_bytes != bi.bytes)) { ctx->set_err("seen set import: not every entry of the blob was added"); rc = SX_E_HIP; }
     if (rc != SX_OK) { sx_seen_set_free(set); return rc; }
     *out = set;
@@ -1131,7 +1233,14 @@ int sx_seen_set_add_strings(sx_ctx* ctx, sx_seen_set* set, const uint8_t* bytes,
     std::vector<uint32_t> kept_of;
     std::string why;
     { const int rc = seen_entries_build(bytes, offsets, n, set->dev.nocase, &arena, &words, &kept_of, &why); if (rc != SX_OK) { ctx->set_err("seen set add_strings: " + why); return rc; } }
-    const int rc = seen_merge_list(ctx, "add_strings", set, words.data(), words.size(), arena.data(), arena.size(), !(flags & SX_SEEN_LOOKUP_ONLY), info, held_out ? &held : nullptr);
+    // (into a set that counts the list is one result: a kept string was in 1 result, as often as the list has it)
+    std::vector<uint64_t> counts;
+    if (set->dev.counts && !(flags & SX_SEEN_LOOKUP_ONLY)) {
+        try { counts.assign(words.size(), (uint64_t)1 << SX_SEEN_RESULTS_SHIFT); } catch (const std::exception&) { ctx->set_err("seen set add_strings: no host memory for the counts"); return SX_E_NOMEM; }
+        for (uint64_t i = 0; i < n; i++) counts[kept_of[i]] = seen_count_sum(counts[kept_of[i]], (uint64_t)1 << SX_SEEN_FINDINGS_SHIFT);
+    }
+    const int rc = seen_merge_list(ctx, "add_strings", set, words.data(), words.size(), arena.data(), arena.size(), counts.empty() ? nullptr : counts.data(),
+                                   !(flags & SX_SEEN_LOOKUP_ONLY), info, held_out ? &held : nullptr);
     if (rc != SX_OK) return rc;
     if (held_out)
         for (uint64_t i = 0; i < n; i++) held_out[i] = (uint8_t)((held[kept_of[i] / kSelectRecs] >> (kept_of[i] % kSelectRecs)) & 1u);

@@ -31,29 +31,35 @@ uint64_t seen_blob_fnv(const uint8_t* p, uint64_t n) {
     return h;
 }
 
-void seen_blob_header(uint8_t* header, uint32_t nocase, uint64_t strings, const uint8_t* area, uint64_t bytes) {
+void seen_blob_header(uint8_t* header, uint32_t nocase, uint64_t strings, const uint8_t* area, uint64_t bytes, uint32_t version) {
     memset(header, 0, kSeenBlobHeaderBytes);
     memcpy(header, kMagic, 8);
-    put_le(header + 8, SX_SEEN_BLOB_VERSION, 4);
+    put_le(header + 8, version, 4);
     put_le(header + 12, nocase, 4);
     put_le(header + 16, strings, 8);
     put_le(header + 24, bytes, 8);
-    put_le(header + 32, seen_blob_fnv(area, bytes), 8);
+    put_le(header + 32, seen_blob_fnv(area, bytes + (version == SX_SEEN_BLOB_VERSION_COUNTED ? 8u * strings : 0u)), 8);
 }
 
-int seen_blob_check(const void* blob, uint64_t len, sx_seen_blob_info* info, std::vector<uint64_t>* words, std::string* why) {
+int seen_blob_check(const void* blob, uint64_t len, sx_seen_blob_info* info, std::vector<uint64_t>* words, std::string* why, std::vector<uint64_t>* counts) {
     const uint8_t* const b = (const uint8_t*)blob;
     if (!b || len < kSeenBlobHeaderBytes) { *why = "shorter than its header"; return SX_E_INVALID; }
     if (memcmp(b, kMagic, 8) != 0) { *why = "no SXSEEN magic"; return SX_E_INVALID; }
     const uint64_t version = le(b + 8, 4), nocase = le(b + 12, 4), strings = le(b + 16, 8), bytes = le(b + 24, 8), sum = le(b + 32, 8);
-    if (version != SX_SEEN_BLOB_VERSION) { *why = "version " + std::to_string(version); return SX_E_INVALID; }
+    if (version != SX_SEEN_BLOB_VERSION && version != SX_SEEN_BLOB_VERSION_COUNTED) { *why = "version " + std::to_string(version); return SX_E_INVALID; }
     if (nocase > 1) { *why = "nocase " + std::to_string(nocase); return SX_E_INVALID; }
     for (uint64_t k = 40; k < kSeenBlobHeaderBytes; k++)
         if (b[k]) { *why = "a header byte behind the checksum is not 0"; return SX_E_INVALID; }
     if (bytes % 8 != 0) { *why = std::to_string(bytes) + " bytes of entries: no multiple of 8"; return SX_E_INVALID; }
-    if (len - kSeenBlobHeaderBytes != bytes) { *why = std::to_string(len) + " bytes, the header says 64 + " + std::to_string(bytes); return SX_E_INVALID; }
+    const bool counted = version == SX_SEEN_BLOB_VERSION_COUNTED;
+    const uint64_t body = len - kSeenBlobHeaderBytes;
+    // (version 2: body = bytes + 8 x strings, said without a sum or a product that could wrap)
+    if (counted ? bytes > body || (body - bytes) % 8 != 0 || (body - bytes) / 8 != strings : body != bytes) {
+        *why = std::to_string(len) + " bytes, the header says 64 + " + std::to_string(bytes) + (counted ? " + 8 x " + std::to_string(strings) : std::string());
+        return SX_E_INVALID;
+    }
     const uint8_t* const area = b + kSeenBlobHeaderBytes;
-    if (seen_blob_fnv(area, bytes) != sum) { *why = "the checksum does not match"; return SX_E_INVALID; }
+    if (seen_blob_fnv(area, body) != sum) { *why = "the checksum does not match"; return SX_E_INVALID; }
     try {
         std::unordered_set<std::string_view> have;
         if (words) words->clear();
@@ -73,6 +79,12 @@ int seen_blob_check(const void* blob, uint64_t len, sx_seen_blob_info* info, std
             at = end; count++;
         }
         if (count != strings) { *why = std::to_string(count) + " entries, the header says " + std::to_string(strings); return SX_E_INVALID; }
+        if (counts) counts->clear();
+        for (uint64_t k = 0; counted && k < strings; k++) {
+            const uint64_t c = le(area + bytes + 8u * k, 8), results = (c >> SX_SEEN_RESULTS_SHIFT) & 0xFFFFFFFFu, findings = (c >> SX_SEEN_FINDINGS_SHIFT) & 0xFFFFFFFFu;
+            if (results == 0 || findings < results) { *why = "count word " + std::to_string(k) + ": " + std::to_string(results) + " results, " + std::to_string(findings) + " findings"; return SX_E_INVALID; }
+            if (counts) counts->push_back(c);
+        }
     } catch (const std::exception&) {
         *why = "no host memory to check the blob";
         return SX_E_NOMEM;

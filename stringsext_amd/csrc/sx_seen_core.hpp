@@ -1,7 +1,8 @@
 // sx_seen_core.hpp — the seen set (sx_seen_set, sx_result_seen_device): strings remembered in HBM from one result to the next.  This
 // file owns THE SET — its slot words (seen_entry_at), its bounded walk for lookups (seen_lookup) and for inserts (seen_claim), its
 // call totals (SeenTotal) and its validity (seen_set_ok) — and what ONE lane does for a RECORD of a result, written as lane functions;
-// sx_seen_merge_core.hpp puts entries that are already a set's through the same two walks.  Included by sx_seen_dev.hip with SXD =
+// sx_seen_merge_core.hpp puts entries that are already a set's through the same two walks, and sx_seen_count_core.hpp, for a set that
+// counts (SeenSet::counts), through the lookup's walk once more, which says on which slot it ended.  Included by sx_seen_dev.hip with SXD =
 // `__device__ __forceinline__`; the test-only harness tests/native/seen_core_host.cpp includes it with SXD = `inline`, so the very same
 // code is checked against a Python set carried across calls on a machine without GPU (tests/test_seen_core.py).
 //
@@ -50,6 +51,7 @@ struct SeenSet {
     uint8_t* arena;          // capacity_bytes, 8-byte aligned
     uint64_t* cursors;       // [0] the strings the set holds, [1] their entries' bytes: where the next entry begins
     uint32_t table_log2, tag_bits, nocase, reserved;
+    uint64_t* counts;        // NULL: the set does not count; else 2^table_log2 words, one per slot (sx_seen_count_core.hpp), 0 where the slot is empty
 };
 // (a set the kernels can walk: what both launchers ask)
 inline bool seen_set_ok(const SeenSet& S) {
@@ -92,18 +94,24 @@ SXD uint64_t seen_tag(const SeenSet& S, uint64_t hash) { return hash & (((uint64
 SXD const uint8_t* seen_entry_at(const uint8_t* arena, uint64_t word) { return arena + (word & (((uint64_t)1 << kSeenOffsetBits) - 1u)) * 8u; }
 
 // THE walk of a lookup.  Does the set hold the string whose hash is `hash`?  From the home slot on: empty = no; another tag = next
-// slot; the same tag = same(entry) decides, the caller's comparison, inlined.  *exhausted: every slot was looked at and none was empty
+// slot; the same tag = same(entry) decides, the caller's comparison, inlined.  *exhausted: every slot was looked at and none was empty.
+// *slot_out: the slot the string's entry has, written only where the answer is yes
 template <class Same>
-SXD bool seen_lookup(const SeenSet& S, uint64_t hash, Same same, bool* exhausted) {
+SXD bool seen_lookup_at(const SeenSet& S, uint64_t hash, Same same, bool* exhausted, uint64_t* slot_out) {
     const uint64_t mask = ((uint64_t)1 << S.table_log2) - 1u, tag = seen_tag(S, hash);
     uint64_t slot = distinct_slot(hash, S.table_log2);
     for (uint64_t walked = 0; walked <= mask; walked++, slot = (slot + 1u) & mask) {
         const uint64_t word = S.slots[slot];
         if (word == kSeenEmpty) return false;
-        if (word >> kSeenOffsetBits == tag && same(seen_entry_at(S.arena, word))) return true;
+        if (word >> kSeenOffsetBits == tag && same(seen_entry_at(S.arena, word))) { *slot_out = slot; return true; }
     }
     *exhausted = true;
     return false;
+}
+template <class Same>
+SXD bool seen_lookup(const SeenSet& S, uint64_t hash, Same same, bool* exhausted) {
+    uint64_t slot;
+    return seen_lookup_at(S, hash, same, exhausted, &slot);
 }
 
 // THE walk of an insert: the entry at arena offset `at`, whose hash is `hash`, takes the first empty slot from its home slot on.
@@ -116,14 +124,19 @@ SXD bool seen_claim(const SeenSet& S, uint64_t hash, uint64_t at) {
     return false;
 }
 
-// Does the set hold the (folded) string s[0, len)?  Byte for byte: a record's string is neither aligned nor padded
-SXD bool seen_find(const SeenSet& S, const uint8_t* s, uint32_t len, bool* exhausted) {
-    return seen_lookup(S, distinct_hash(s, len, S.nocase, kSeenSeed), [&](const uint8_t* entry) {
+// Does the set hold the (folded) string s[0, len)?  Byte for byte: a record's string is neither aligned nor padded.  *slot_out: as
+// seen_lookup_at's
+SXD bool seen_find_at(const SeenSet& S, const uint8_t* s, uint32_t len, bool* exhausted, uint64_t* slot_out) {
+    return seen_lookup_at(S, distinct_hash(s, len, S.nocase, kSeenSeed), [&](const uint8_t* entry) {
         if (*(const uint32_t*)entry != len) return false;
         uint32_t j = 0;
         while (j < len && entry[8u + j] == select_fold(S.nocase, s[j])) j++;
         return j == len;
-    }, exhausted);
+    }, exhausted, slot_out);
+}
+SXD bool seen_find(const SeenSet& S, const uint8_t* s, uint32_t len, bool* exhausted) {
+    uint64_t slot;
+    return seen_find_at(S, s, len, exhausted, &slot);
 }
 
 // mark, lane `lane` of wavefront `w`: its record's word gets SX_DISTINCT_SEEN if the set holds its string.  *seen = it does; *first =

@@ -69,15 +69,19 @@ SXD uint64_t seen_merge_hash(const uint64_t* entry, uint32_t nocase) {
 }
 
 // Does the set hold `entry` (whose hash is `hash`)?  Word for word, the length first: a comparison ends at the first word that
-// differs, so it never leaves the shorter entry.  *exhausted: every slot was looked at and none was empty
-SXD bool seen_merge_find(const SeenSet& S, const uint64_t* entry, uint64_t hash, bool* exhausted) {
+// differs, so it never leaves the shorter entry.  *exhausted: every slot was looked at and none was empty; *slot_out: as seen_lookup_at's
+SXD bool seen_merge_find_at(const SeenSet& S, const uint64_t* entry, uint64_t hash, bool* exhausted, uint64_t* slot_out) {
     const uint64_t words = 1u + ((entry[0] & 0xFFFFFFFFu) + 7u) / 8u;
-    return seen_lookup(S, hash, [&](const uint8_t* at) {
+    return seen_lookup_at(S, hash, [&](const uint8_t* at) {
         const uint64_t* have = (const uint64_t*)at;
         uint64_t j = 0;
         while (j < words && have[j] == entry[j]) j++;
         return j == words;
-    }, exhausted);
+    }, exhausted, slot_out);
+}
+SXD bool seen_merge_find(const SeenSet& S, const uint64_t* entry, uint64_t hash, bool* exhausted) {
+    uint64_t slot;
+    return seen_merge_find_at(S, entry, hash, exhausted, &slot);
 }
 
 // mark, lane `lane` of wavefront `w`.  *occupied = its source word has an entry; *held = the destination holds it; *bytes = the entry

@@ -71,6 +71,7 @@ hipError_t select_measure(SelectParams* P, const SelectBy& by, void* scratch, si
     hipError_t e;
     switch (by.kind) {
     case SelectBy::kLabels: e = by.pick ? label_launch_pick(*P, *by.pick, waves, stream) : hipErrorInvalidValue; break;
+    case SelectBy::kLabelRange: e = by.range ? label_range_launch_pick(*P, *by.range, waves, stream) : hipErrorInvalidValue; break;
     case SelectBy::kSet: e = by.set ? selset_launch_match(*P, *by.set, waves, stream) : hipErrorInvalidValue; break;
     case SelectBy::kRegex: e = by.re ? selre_launch_match(*P, *by.re, waves, stream) : hipErrorInvalidValue; break;
     default:

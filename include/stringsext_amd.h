@@ -971,6 +971,45 @@ int  sx_result_seen_counts_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* 
 int  sx_result_select_labels_range_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels, uint32_t shift, uint32_t bits,
                                           uint64_t lo, uint64_t hi, sx_result** out);
 
+/* IN WHICH ORDER: sx_result_order_device.  *out (sx_result_free) is a new result in HBM that holds the findings of r that take part —
+ * those the label pick of sx_result_select_labels_device lets through; any = all = none = 0: every finding — in sorted order, the
+ * first `limit` of them (0: all).  It is sorted(range(n), key, reverse): findings with equal keys keep print order — segment order,
+ * then record order —, and SX_ORDER_DESCENDING reverses the order of the distinct keys and leaves the ties in print order.
+ *   SX_ORDER_BY_STRING       the strings as unsigned bytes, memcmp and then the shorter one first: LC_ALL=C sort.  With
+ *                            SX_ORDER_NOCASE the bytes are compared after 'A'..'Z' became 'a'..'z', no other byte; the output's
+ *                            strings stay as they are.
+ *   SX_ORDER_BY_LABEL_FIELD  (label >> shift) & mask(bits) as an unsigned number, 1 <= bits <= 64, shift + bits <= 64: on distinct
+ *                            words shift = 32, bits = 32 is the size of the class, on count words a half of the word.
+ * `labels` (of r, as sx_result_select_labels_device checks it) serves the filter and the field; it may be NULL where neither needs it.
+ * `sort -u` is sx_result_distinct_device, then by = STRING, any = SX_DISTINCT_FIRST; `uniq -c | sort -rn | head -20` is by =
+ * LABEL_FIELD, shift = 32, bits = 32, DESCENDING, any = SX_DISTINCT_FIRST, limit = 20.
+ * The output is ONE segment of sx_finding records in the order, their strings back to back in record order, every field what
+ * sx_result_segment() gives for the source record (a packed source's input_file_id and slice_index come from its sx_segment_info);
+ * a call in which nothing takes part gives a result without segments, as a selection that selects nothing does.  It lies in the
+ * selection block whose turn it is: the call takes a turn and ages selections exactly as a selection does; a call that returns an
+ * error takes none and writes no block.  r is read, never moved.
+ * *info (may be NULL): findings = how many took part, kept = how many were written, rounds = the refinement rounds of the string key
+ * (a round looks at eight more bytes of the strings still undecided; 0 for the label key and where nothing takes part), tied = the
+ * written findings whose key equals another written finding's, max_depth = the deepest 8-byte word a comparison needed (rounds - 1).
+ * SX_E_STATE wherever sx_print_findings_device refuses the source, and for a source in the block this call would write.
+ * SX_E_INVALID (sx_last_error says which): a NULL pointer, an unknown `by` or flag, SX_ORDER_NOCASE with the label key, `labels` NULL
+ * where the key or the filter needs them, a field that sx_result_select_labels_range_device would refuse, labels of another result,
+ * more than 2^32 - 2 findings that take part or 2^32 or more bytes of their strings — decided before anything is written.
+ * SX_E_NOMEM: a block or the tables cannot be had.  *out = NULL on every error.
+ * Not built: locale collation, Unicode folding, a second key, numeric-string keys, sharded entry points, top-k without a full sort. */
+enum { SX_ORDER_BY_STRING = 0, SX_ORDER_BY_LABEL_FIELD = 1 };
+enum { SX_ORDER_DESCENDING = 1u, SX_ORDER_NOCASE = 2u };
+typedef struct sx_order_spec {
+    uint32_t by;            /* SX_ORDER_BY_STRING | SX_ORDER_BY_LABEL_FIELD */
+    uint32_t flags;         /* SX_ORDER_DESCENDING, SX_ORDER_NOCASE (strings only) */
+    uint32_t shift, bits;   /* the field of a label word, as sx_result_select_labels_range_device reads it */
+    uint64_t any, all, none;/* the label pick of sx_result_select_labels_device; all three 0: every finding */
+    uint64_t limit;         /* keep only the first `limit` findings of the order; 0: all */
+} sx_order_spec;
+typedef struct sx_order_info { uint64_t findings, kept, rounds, tied, max_depth; } sx_order_info;
+int  sx_result_order_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels /* may be NULL */,
+                            const sx_order_spec* spec, sx_result** out, sx_order_info* info /* may be NULL */);
+
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);
 

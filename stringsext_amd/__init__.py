@@ -30,6 +30,8 @@ SX_DISTINCT_SEEN, SX_SEEN_LOOKUP_ONLY = 4, 0x100   # sx_result_seen_device (Resu
 SX_SEEN_BLOB_HEADER_BYTES, SX_SEEN_BLOB_VERSION = 64, 1   # sx_seen_set_export (SeenSet.export): the header of a saved set
 # a set that counts (Scanner.seen_set(counted=True)): the create flag, the two halves of a count word, and its blob's version
 SX_SEEN_COUNTED, SX_SEEN_RESULTS_SHIFT, SX_SEEN_FINDINGS_SHIFT, SX_SEEN_BLOB_VERSION_COUNTED = 0x200, 0, 32, 2
+# sx_result_order_device (Result.order_device): the key, and the flags
+SX_ORDER_BY_STRING, SX_ORDER_BY_LABEL_FIELD, SX_ORDER_DESCENDING, SX_ORDER_NOCASE = 0, 1, 1, 2
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -56,7 +58,7 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_result_label_device", "sx_labels_segment_device", "sx_labels_segments", "sx_labels_free", "sx_result_select_labels_device", "sx_result_distinct_device",
            "sx_seen_set_create", "sx_seen_set_info_get", "sx_seen_set_reset", "sx_seen_set_free", "sx_result_seen_device",
            "sx_seen_set_merge", "sx_seen_set_grow", "sx_seen_set_export_size", "sx_seen_set_export", "sx_seen_blob_info_get", "sx_seen_set_import", "sx_seen_set_add_strings",
-           "sx_result_seen_counts_device", "sx_result_select_labels_range_device",
+           "sx_result_seen_counts_device", "sx_result_select_labels_range_device", "sx_result_order_device",
            "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
@@ -212,6 +214,15 @@ class LabelSetInfo(C.Structure):   # sx_label_set_info
                 ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32), ("here_states", C.c_uint32)]
 
 
+class OrderSpec(C.Structure):   # sx_order_spec
+    _fields_ = [("by", C.c_uint32), ("flags", C.c_uint32), ("shift", C.c_uint32), ("bits", C.c_uint32), ("any", C.c_uint64), ("all", C.c_uint64),
+                ("none", C.c_uint64), ("limit", C.c_uint64)]
+
+
+class OrderInfo(C.Structure):   # sx_order_info
+    _fields_ = [("findings", C.c_uint64), ("kept", C.c_uint64), ("rounds", C.c_uint64), ("tied", C.c_uint64), ("max_depth", C.c_uint64)]
+
+
 class DistinctInfo(C.Structure):   # sx_distinct_info
     _fields_ = [("findings", C.c_uint64), ("distinct", C.c_uint64), ("repeated", C.c_uint64), ("rounds", C.c_uint32), ("table_log2", C.c_uint32)]
 
@@ -352,6 +363,7 @@ def lib():
     L.sx_seen_set_add_strings.argtypes = [vp, vp, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.c_char_p, C.POINTER(SeenMergeInfo)]
     L.sx_result_seen_counts_device.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.sx_result_select_labels_range_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(vp)]
+    L.sx_result_order_device.argtypes = [vp, vp, vp, C.POINTER(OrderSpec), C.POINTER(vp), C.POINTER(OrderInfo)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -366,6 +378,8 @@ def lib():
 
 class Result:
     """Findings of one sx_scan call, in the reference merger's order (src/main.rs:118-136)."""
+
+    order_info = None      # order_device(): sx_order_info as a dict
 
     def __init__(self, scanner, handle):
         self._s, self.h = scanner, handle
@@ -629,6 +643,36 @@ class Result:
         out = C.c_void_p()
         self._s._chk(lib().sx_result_select_labels_range_device(self._s.h, self.h, labels._handle(), shift, bits, lo, hi, C.byref(out)))
         return Result(self._s, out)
+
+    def order_device(self, by="string", labels=None, shift=0, bits=64, descending=False, ignore_case=False, any=0, all=0, none=0, limit=0):
+        """sx_result_order_device: IN WHICH ORDER — a new Result on the device that holds this Result's findings sorted by their
+        string (by="string": unsigned bytes, the shorter of two first, `LC_ALL=C sort`; ignore_case: 'A'..'Z' compare as 'a'..'z') or
+        by the field (word >> shift) & mask(bits) of their word in `labels` (by="field"; the Labels made of THIS Result).  Findings
+        with equal keys keep print order; descending reverses the distinct keys and leaves the ties as they are:
+        sorted(range(n), key=..., reverse=descending).  any, all, none: only the findings whose label passes the pick of
+        select_device(labels, ...) take part (all 0: every finding); limit: only the first `limit` findings of the order (0: all).
+        distinct_device() then order_device(labels=d, any=SX_DISTINCT_FIRST) is `sort -u`; order_device("field", d, shift=32,
+        bits=32, descending=True, any=SX_DISTINCT_FIRST, limit=20) is `uniq -c | sort -rn | head -20`.  The new Result is one
+        segment of unpacked records, lies on the device like a selection, counts as one for "valid until the second select_device()
+        after this one", and .order_info is sx_order_info as a dict: findings (took part), kept (written), rounds, tied, max_depth.
+        This Result is not moved.  Raises ValueError for another `by`, SxError: SX_E_INVALID for labels that are missing where the
+        key or the masks need them, of another Result or freed, a bad field, ignore_case with by="field"; SX_E_STATE wherever
+        printed_device() would refuse this Result."""
+        if by not in ("string", "field"):
+            raise ValueError('order_device: by is "string" or "field"')
+        if labels is not None and not isinstance(labels, Labels):
+            raise TypeError("order_device takes Labels")
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        if not (0 <= shift < 1 << 32 and 0 <= bits < 1 << 32 and 0 <= min(any, all, none, limit) and max(any, all, none, limit) < 1 << 64):
+            raise SxError(SX_E_INVALID, "order_device: shift and bits are 32-bit, the masks and the limit 64-bit unsigned numbers")
+        spec = OrderSpec(SX_ORDER_BY_LABEL_FIELD if by == "field" else SX_ORDER_BY_STRING,
+                         (SX_ORDER_DESCENDING if descending else 0) | (SX_ORDER_NOCASE if ignore_case else 0), shift, bits, any, all, none, limit)
+        out, info = C.c_void_p(), OrderInfo()
+        self._s._chk(lib().sx_result_order_device(self._s.h, self.h, labels._handle() if labels is not None else None, C.byref(spec), C.byref(out), C.byref(info)))
+        res = Result(self._s, out)
+        res.order_info = {k: getattr(info, k) for k, _ in OrderInfo._fields_}
+        return res
 
     def free(self):
         if self.h:

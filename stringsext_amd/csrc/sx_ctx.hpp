@@ -211,7 +211,7 @@ struct sx_ctx {
     uint8_t* d_select_scratch = nullptr; uint64_t d_select_scratch_cap = 0;
     uint8_t* d_select_scratch2 = nullptr; uint64_t d_select_scratch2_cap = 0;
     // sx_result_distinct_device, and the distinct pass of sx_result_seen_device: the call's tables (the segments, the counters, rep, count, the slots), grown on demand and reused; no
-    // result and no selection lies here
+    // result and no selection lies here.  sx_result_order_device lays its sort's tables here too (a seen set's merge: its scratch)
     uint8_t* d_distinct = nullptr; uint64_t d_distinct_cap = 0;
     bool merge_async = false;                           // device_merge returns with its last copies in flight; merge_drain() waits
     bool merge_copy_pending[2] = { false, false };      // a copy out of output buffer 0 / 1 was queued and not waited for

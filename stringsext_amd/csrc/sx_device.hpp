@@ -346,6 +346,26 @@ hipError_t seen_merge_launch(const SeenMergeParams& P, int phase, hipStream_t st
 struct SeenMergeCountParams;
 hipError_t seen_count_launch(const SeenParams& P, int phase, hipStream_t stream);
 hipError_t seen_merge_count_launch(const SeenMergeCountParams& C, hipStream_t stream);
+// The sorted order on the device (sx_order_dev.hip, sx_order_core.hpp).  order_pick_tables / order_sort_tables: the call's tables in a
+// 256-byte aligned block (base NULL: only the size).  order_launch_pick: a segment's picked records per wavefront and the call's totals;
+// order_scan_picks behind every segment's; order_launch_number: the picked records' keys in print order.  order_round: one round of
+// the string key over list `cur`; T.scan[n] then holds the next list's slots and groups.  order_by_field: the label key's one sort.
+// order_launch_measure: the kept findings' bytes and ties; order_launch_gather: their records and the addresses of their strings
+struct OrderSeg;
+struct OrderPick;
+struct OrderOut;
+struct OrderPickTables;
+struct OrderSortTables;
+size_t order_pick_tables(uint8_t* base, uint64_t n_segs, uint64_t n_packed, uint64_t waves, OrderPickTables* T);
+size_t order_sort_tables(uint8_t* base, uint64_t m, OrderSortTables* T);
+hipError_t order_launch_pick(const OrderPick& P, hipStream_t stream);
+hipError_t order_scan_picks(const OrderPickTables& T, uint64_t waves, hipStream_t stream);
+hipError_t order_launch_number(const OrderPick& P, hipStream_t stream);
+hipError_t order_round(const OrderSortTables& T, const OrderSeg* segs, int cur, uint64_t n, uint64_t groups, uint32_t depth, uint32_t nocase, uint32_t descending,
+                       hipStream_t stream);
+hipError_t order_by_field(const OrderSortTables& T, uint64_t m, uint32_t bits, hipStream_t stream);
+hipError_t order_launch_measure(const OrderOut& P, hipStream_t stream);
+hipError_t order_launch_gather(const OrderOut& P, hipStream_t stream);
 // (threads, nontemporal: Switches::merge_copy_threads, merge_copy_nt)
 hipError_t launch_copy_bytes(void* dst, const void* src, uint64_t bytes, uint32_t workgroups, hipStream_t stream, int threads, bool nontemporal);
 // a few words (4-aligned, a multiple of 4 bytes) into pinned host memory by a one-wavefront kernel instead of the runtime's blit

@@ -18,6 +18,7 @@
 #include "sx_label_build.hpp"
 #include "sx_label_core.hpp"
 #include "sx_distinct_core.hpp"
+#include "sx_order_core.hpp"
 #include "sx_seen_core.hpp"
 #include "sx_seen_merge_core.hpp"
 #include "sx_seen_count_core.hpp"
@@ -442,6 +443,144 @@ int distinct_on_device(sx_ctx* ctx, const sx_result* r, uint32_t nocase, const c
     if (info) *info = sx_distinct_info{ findings, words[1], words[2], rounds, table_log2 };
     if (segs_out) *segs_out = std::move(segs);
     *out = lab;
+    return SX_OK;
+}
+
+// The findings in sorted order where they lie (sx_order_dev.hip), for sx_result_order_device, whose arguments are checked.  The pick's
+// tables — per wavefront of the call — go into the selections' wavefront tables, the sort's into sx_ctx::d_distinct, which grows on
+// demand and is no selection block.  On the selections' stream: every segment's pick, one scan, ONE read of the totals — how many
+// take part, their bytes, the longest string: the 32-bit limits are decided here, before anything else is written —; every segment's
+// number; then the label key's one sort, or the rounds of the string key with ONE read each — the scan's total: the slots still
+// undecided and their groups —, at most longest / 8 + 2 of them (one more is an error, never a reason to go on); measure and one
+// read — the kept findings' bytes and ties —; the block whose turn it is, gather, order_part_strings, one wait.  The call takes its
+// turn only when both blocks are had: an error in front of that ages nothing.
+int order_on_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels, const sx_order_spec& spec, sx_result** out, sx_order_info* info) {
+    const int slot = (int)(ctx->select_calls & 1u);
+    for (const MissionFindings& s : r->r.segs)
+        if (s.dev_epoch_ref == ctx->select_epoch[slot]) { ctx->set_err("this order reuses the source's device memory: it was selected two calls ago"); return SX_E_STATE; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    const size_t ns = r->r.segs.size();
+    const bool by_field = spec.by == SX_ORDER_BY_LABEL_FIELD;
+    const uint32_t descending = spec.flags & SX_ORDER_DESCENDING ? 1u : 0u, nocase = spec.flags & SX_ORDER_NOCASE ? 1u : 0u;
+    std::vector<OrderSeg> segs;
+    std::vector<uint64_t> pos0;
+    std::vector<size_t> pos0_of(ns, 0);
+    uint64_t waves = 0, n_packed = 0;
+    for (size_t i = 0; i < ns; i++) {
+        const MissionFindings& s = r->r.segs[i];
+        const SegRef v = seg_ref(s);
+        if (v.n >> 32 || ns >> 31) { ctx->set_err("order: a segment of 2^32 findings or more"); return SX_E_INVALID; }
+        OrderSeg g;
+        memset(&g, 0, sizeof g);
+        g.recs = v.recs; g.arena = v.arena; g.n = v.n; g.packed = v.packed; g.file_id = -1;
+        g.labels = labels ? labels->segs[i].d : nullptr; g.wave0 = waves;
+        if (v.packed) {
+            pos0_of[i] = n_packed++;
+            pos0.resize(n_packed * 256, 0);
+            if (s.info) { g.file_id = s.info->file_id; g.slice_base = s.info->slice_base; memcpy(&pos0[pos0_of[i] * 256], s.info->pos0, 256 * sizeof(uint64_t)); }
+        }
+        segs.push_back(g);
+        waves += (v.n + kSelectRecs - 1) / kSelectRecs;
+    }
+    { const int rc = grow_device(ctx, &ctx->d_select_scratch, &ctx->d_select_scratch_cap, order_pick_tables(nullptr, ns, n_packed, waves, nullptr), "wavefront tables"); if (rc != SX_OK) return rc; }
+    OrderPickTables PT;
+    (void)order_pick_tables(ctx->d_select_scratch, ns, n_packed, waves, &PT);
+    for (size_t i = 0; i < ns; i++)
+        if (segs[i].packed) segs[i].pos0 = PT.pos0 + pos0_of[i] * 256;
+    OrderPick pick;
+    memset(&pick, 0, sizeof pick);
+    pick.filter = (spec.any | spec.all | spec.none) != 0 ? 1u : 0u; pick.any = spec.any; pick.all = spec.all; pick.none = spec.none;
+    pick.wmask = PT.wmask; pick.wcount = PT.wcount; pick.wbase = PT.wbase; pick.totals = PT.totals;
+    pick.shift = spec.shift; pick.descending = descending; pick.mask = spec.bits >= 64 ? ~(uint64_t)0 : ((uint64_t)1 << spec.bits) - 1u;
+    uint64_t tot[kOrderTotals] = { 0 };
+    hipError_t e = hipMemcpy(PT.segs, segs.data(), ns * sizeof(OrderSeg), hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_packed) e = hipMemcpy(PT.pos0, pos0.data(), pos0.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(PT.totals, 0, kOrderTotals * sizeof(uint64_t), st);
+    for (size_t i = 0; e == hipSuccess && i < ns; i++) { pick.seg = segs[i]; pick.seg_index = (uint32_t)i; e = order_launch_pick(pick, st); }
+    if (e == hipSuccess) e = order_scan_picks(PT, waves, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(tot, PT.totals, sizeof tot, hipMemcpyDeviceToHost, st);
+    { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
+    auto failed = [&](const std::string& what) {
+        (void)hipGetLastError();
+        ctx->set_err("device order: " + what);
+        return SX_E_HIP;
+    };
+    if (e != hipSuccess) return failed(hipGetErrorString(e));
+    const uint64_t m = tot[kOrderCount];
+    if (m > 0xFFFFFFFEull || tot[kOrderBytes] >> 32) {
+        ctx->set_err("order: " + std::to_string(m) + " findings with " + std::to_string(tot[kOrderBytes]) + " bytes of strings take part: one segment holds 2^32 - 2 findings and less than 2^32 bytes");
+        return SX_E_INVALID;
+    }
+    ResultHolder res;
+    res.r->r.pool = ctx->pool;
+    if (m == 0) {      // (as a selection that selects nothing: the call counts, the result has no segment)
+        ctx->select_epoch[slot]->fetch_add(1);
+        ctx->select_calls++;
+        if (info) *info = sx_order_info{ 0, 0, 0, 0, 0 };
+        *out = res.release();
+        return SX_OK;
+    }
+    const uint64_t sort_bytes = order_sort_tables(nullptr, m, nullptr);
+    if (!device_room(&ctx->d_distinct, &ctx->d_distinct_cap, sort_bytes)) {
+        ctx->set_err("device order: no memory for " + std::to_string(sort_bytes) + " bytes of tables");
+        return SX_E_NOMEM;
+    }
+    OrderSortTables ST;
+    (void)order_sort_tables(ctx->d_distinct, m, &ST);
+    pick.ikey = ST.ikey[0]; pick.slotpos = ST.slotpos[0]; pick.slotgrp = ST.slotgrp[0]; pick.field = by_field ? ST.wkey : nullptr;
+    for (size_t i = 0; e == hipSuccess && i < ns; i++) { pick.seg = segs[i]; pick.seg_index = (uint32_t)i; e = order_launch_number(pick, st); }
+    uint64_t rounds = 0;
+    if (by_field) {
+        if (e == hipSuccess) e = order_by_field(ST, m, spec.bits, st);
+    } else {
+        const uint64_t most = tot[kOrderLongest] / 8 + 2;
+        uint64_t left = m, groups = 1;
+        int cur = 0;
+        while (e == hipSuccess && left != 0) {
+            if (rounds >= most) return failed("round " + std::to_string(rounds) + " would look behind the longest string's end, and " + std::to_string(left) + " findings are not yet in order");
+            uint64_t word = 0;
+            e = order_round(ST, PT.segs, cur, left, groups, (uint32_t)rounds, nocase, descending, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(&word, ST.scan + left, sizeof word, hipMemcpyDeviceToHost, st);
+            { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
+            if (e != hipSuccess) break;
+            rounds++;
+            if (ctx->sw.timing) fprintf(stderr, "[sx] order round %llu: %llu of %llu findings left in %llu groups\n", (unsigned long long)(rounds - 1), (unsigned long long)(word & 0xFFFFFFFFu), (unsigned long long)m, (unsigned long long)(word >> 32));
+            if ((word & 0xFFFFFFFFu) > left) return failed("round " + std::to_string(rounds - 1) + " left more findings undecided than it began with");
+            left = word & 0xFFFFFFFFu; groups = word >> 32; cur ^= 1;
+        }
+    }
+    const uint64_t kept = spec.limit && spec.limit < m ? spec.limit : m;
+    OrderOut O;
+    memset(&O, 0, sizeof O);
+    O.segs = PT.segs; O.order = ST.order; O.classhead = ST.classhead; O.kept = kept; O.totals = PT.totals;
+    if (e == hipSuccess) e = order_launch_measure(O, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(tot, PT.totals, sizeof tot, hipMemcpyDeviceToHost, st);
+    { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
+    if (e != hipSuccess) return failed(hipGetErrorString(e));
+    // the two blocks; where the output's block is had anew, what lay there is gone whether or not the call goes on
+    const uint64_t kept_bytes = tot[kOrderKeptBytes], block = up256(kept * sizeof(sx_finding) + kept_bytes), src_bytes = up256(kept * sizeof(uint64_t)),
+                   scratch2 = src_bytes + order_strings_scratch_bytes(kept);
+    if (!device_room(&ctx->d_select[slot], &ctx->d_select_cap[slot], block)) {
+        ctx->select_epoch[slot]->fetch_add(1);
+        ctx->set_err("device order: no memory for " + std::to_string(block) + " bytes of ordered findings");
+        return SX_E_NOMEM;
+    }
+    { const int rc = grow_device(ctx, &ctx->d_select_scratch2, &ctx->d_select_scratch2_cap, scratch2, "string offsets"); if (rc != SX_OK) return rc; }
+    ctx->select_epoch[slot]->fetch_add(1);
+    ctx->select_calls++;
+    uint8_t* recs = ctx->d_select[slot];
+    O.out = (sx_finding*)recs; O.out_src = (uint64_t*)ctx->d_select_scratch2;
+    e = order_launch_gather(O, st);
+    if (e == hipSuccess) e = order_part_strings(recs, kept, 0, O.out_src, recs + kept * sizeof(sx_finding), ctx->d_select_scratch2 + src_bytes, scratch2 - src_bytes, st);
+    { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
+    if (e != hipSuccess) return failed(hipGetErrorString(e));
+    MissionFindings o;
+    o.ext_nf = kept; o.ext_na = kept_bytes; o.dev_copy = recs; o.dev_only = true; o.keep_on_device = true;
+    o.dev_epoch_ref = ctx->select_epoch[slot]; o.dev_epoch = ctx->select_epoch[slot]->load();
+    res.r->r.segs.push_back(std::move(o));
+    if (info) *info = sx_order_info{ m, kept, rounds, tot[kOrderTied], rounds ? rounds - 1 : 0 };
+    *out = res.release();
     return SX_OK;
 }
 
@@ -908,6 +1047,29 @@ int sx_result_select_labels_range_device(sx_ctx* ctx, const sx_result* r, const 
     sel.labels = labels;
     sel.range = LabelRange{ nullptr, lo, hi, shift, bits };
     return select_on_device(ctx, r, sel, out);
+}
+
+int sx_result_order_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels, const sx_order_spec* spec, sx_result** out, sx_order_info* info) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !spec || !out) return SX_E_INVALID;
+    if (spec->by != SX_ORDER_BY_STRING && spec->by != SX_ORDER_BY_LABEL_FIELD) { ctx->set_err("order: `by` is neither SX_ORDER_BY_STRING nor SX_ORDER_BY_LABEL_FIELD"); return SX_E_INVALID; }
+    if (spec->flags & ~(uint32_t)(SX_ORDER_DESCENDING | SX_ORDER_NOCASE)) { ctx->set_err("order: flags other than SX_ORDER_DESCENDING and SX_ORDER_NOCASE"); return SX_E_INVALID; }
+    const bool by_field = spec->by == SX_ORDER_BY_LABEL_FIELD;
+    if (by_field && (spec->flags & SX_ORDER_NOCASE)) { ctx->set_err("order: SX_ORDER_NOCASE folds strings, and the key is a label field"); return SX_E_INVALID; }
+    if (by_field && (spec->bits < 1 || spec->bits > 64 || spec->shift > 64 - spec->bits)) {
+        ctx->set_err("order: a field of " + std::to_string(spec->bits) + " bits at bit " + std::to_string(spec->shift) + ": 1 to 64 bits that end at bit 64 at most");
+        return SX_E_INVALID;
+    }
+    if (!labels && (by_field || spec->any || spec->all || spec->none)) {
+        ctx->set_err(by_field ? "order: the key is a label field, and there are no labels" : "order: the masks any, all and none pick by labels, and there are none");
+        return SX_E_INVALID;
+    }
+    if (labels) { const int rc = labels_of_result(ctx, r, labels); if (rc != SX_OK) return rc; }
+    else {
+        if (host_only(ctx, "order")) return SX_E_STATE;
+        { const int rc = result_on_device(ctx, r, "sort on the host"); if (rc != SX_OK) return rc; }
+    }
+    return order_on_device(ctx, r, labels, *spec, out, info);
 }
 
 int sx_result_distinct_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_labels** out, sx_distinct_info* info) {

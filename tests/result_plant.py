@@ -189,8 +189,8 @@ def oracle_text(ms, data):
 
 
 def expected(ms, data):
-    """the oracle's findings of `data`: a Rows (cached by the Missions' encodings and the data)"""
-    key = (tuple(m["encoding"] for m in ms), len(data), hash(data))
+    """the oracle's findings of `data`: a Rows (cached by every field of every Mission and the data)"""
+    key = (tuple(tuple(sorted(m.items())) for m in ms), len(data), hash(data))
     if key not in _expected:
         _expected[key] = Rows(*parse(oracle_text(ms, data), len(ms) > 1))
     return _expected[key]

@@ -344,7 +344,6 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
                 d.h_runs_cap = cap;
             }
             rl.p = d.h_runs; rl.n = nruns; rl.on_device = true; rl.dev_ptr = d_list;
-            if (large_regions && nruns < s.n_regions * ctx->region_cap / 4) ctx->dense[(size_t)which[k]] = 0;  // sparse again
             if (nruns) {
                 // The list is complete on the device (the count was just read).  Its copy for the host's
                 // part of stage B runs on a stream of its own, started on demand: whoever reads rl.p[] calls
@@ -367,6 +366,7 @@ int stage_a_finish(sx_ctx* ctx, const std::vector<int>& which, const uint8_t* d_
             else merge_device_runs(recs_p, nrec, min_chars[k], 64 * 1024, &rl.own);
             rl.use_own();
         }
+        if (large_regions && rl.size() < s.n_regions * ctx->region_cap / 4) ctx->dense[(size_t)which[k]] = 0;  // sparse again, after either join
         if (ctx->sw.timing)
             fprintf(stderr, "[sx] mission %d: kernel %.2f ms, %u %s, %s %.2f ms, %s %.2f ms -> %zu runs\n", which[k], ms, nrec,
                     regions ? "records (regions)" : (large_regions ? "record slots (large regions)" : "record slots (pool)"), dev_sorted ? (regions ? "device pack+join" : "device sort+join") : "d2h",

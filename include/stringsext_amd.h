@@ -566,7 +566,8 @@ int  sx_result_select_set_device(sx_ctx* ctx, const sx_result* r, const sx_selec
  *   ^ or $ in mid-pattern                 legal: (^a|b)c, a$|b; a^b is legal and matches nothing
  *   every other backslash + alphanumeric (\b \B \A \Z \1 \e ...)  refused
  * Refused means SX_E_INVALID, and sx_last_error names the pattern's index, the byte offset and the reason.  Not in the language:
- * Unicode-aware classes and folding ([а-я] is a byte class), \b, lookaround, back-references, captures.
+ * Unicode-aware classes and folding ([а-я] is a byte class; sx_result_fold_device in front of the call folds the strings by simple
+ * folding, sx_fold_utf8 a pattern's literals), \b, lookaround, back-references, captures.
  * (Where the matches lie: sx_result_extract_regex_device, below; which patterns match in a finding: sx_result_label_device, below.)
  * flags: 0 or SX_SELECT_ASCII_NOCASE — the fold is compiled into the set, and it is re.IGNORECASE on a bytes pattern: a literal
  * letter matches both cases, a class holds a letter's other case too and negation applies after that ([Z-a] matches z and A,
@@ -757,7 +758,8 @@ int  sx_tally_set_counters_device(const sx_tally_set* set, const uint64_t** d_hi
  * itself would be.  The labels of a selection are not carried to its output: label the output again, or select by label first.
  * Not thread-safe: one sx_result_label_device call per set at a time, and no reset or read during it.
  * Not built: which pattern matched WHERE (labels on an extraction's matches by their own pattern), labels for keyword sets of 65536
- * entries, labels carried through a selection, Unicode folding. */
+ * entries, labels carried through a selection, Unicode folding inside this call (sx_result_fold_device in front of it: simple
+ * folding). */
 typedef struct sx_label_set sx_label_set;   /* compiled patterns + their counters, in HBM */
 typedef struct sx_labels    sx_labels;      /* one result's labels, in HBM */
 typedef struct sx_label_set_info {
@@ -807,7 +809,8 @@ int  sx_result_select_labels_device(sx_ctx* ctx, const sx_result* r, const sx_la
  * by sx_destroy; the labels are the caller's.  It returns when the kernels are done.  SX_E_INVALID: a NULL pointer (info may be), flags other than 0 or SX_SELECT_ASCII_NOCASE.
  * SX_E_STATE: a host-only context; a result in host memory, or one whose device memory a later call has reused — as
  * sx_result_label_device refuses them.  SX_E_NOMEM: the labels or the tables cannot be allocated.  *out is NULL on every error.
- * Not built: classes per Mission, Unicode folding, the counts carried through a selection (they are in the labels of the source:
+ * Not built: classes per Mission, Unicode folding inside this call (sx_result_fold_device in front of it: simple folding), the
+ * counts carried through a selection (they are in the labels of the source:
  * distinct the selection again, or read the words), a sorted output.  (Classes across several results or buffers: the seen set below.) */
 enum { SX_DISTINCT_FIRST = 1u, SX_DISTINCT_REPEATED = 2u };
 #define SX_DISTINCT_COUNT_SHIFT 32
@@ -850,7 +853,8 @@ int  sx_result_distinct_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, 
  * Sources, refusals and lifetime are exactly sx_result_distinct_device's — SX_E_STATE where that refuses —: r is read and never moved,
  * no result or selection block is written, no selection ages.  SX_E_INVALID also: a NULL set, flags other than 0 or
  * SX_SEEN_LOOKUP_ONLY, a set on another device.  Not thread-safe: one call per set at a time, and no reset or info during it.
- * Not built: removing strings, Unicode folding, sharded entry points.  (Growth, saving and loading a set, and a list of strings as
+ * Not built: removing strings, Unicode folding inside this call (sx_result_fold_device in front of it: simple folding), sharded
+ * entry points.  (Growth, saving and loading a set, and a list of strings as
  * the source: below.  A count per stored string over the stream: SX_SEEN_COUNTED, further below.) */
 typedef struct sx_seen_set sx_seen_set;         /* the slots, the entries and their cursors, in HBM */
 enum { SX_DISTINCT_SEEN = 4u };                 /* bit 2 of a word made by sx_result_seen_device */
@@ -908,7 +912,8 @@ int  sx_result_seen_device(sx_ctx* ctx, const sx_result* r, sx_seen_set* set, ui
  * offsets that decrease.  Capacity as sx_seen_set_merge.
  * All of them but the two host-only blob calls refuse a host-only context (SX_E_STATE), age no selection and write no result or
  * selection block; like every call on a set they are not thread-safe per set.
- * Not built: removing strings, canonical (sorted) blobs, Unicode folding, sharded entry points. */
+ * Not built: removing strings, canonical (sorted) blobs, Unicode folding inside this call (sx_result_fold_device in front of it:
+ * simple folding), sharded entry points. */
 typedef struct sx_seen_merge_info { uint64_t source_strings, already_held, added_strings, added_bytes; } sx_seen_merge_info;
 typedef struct sx_seen_blob_info  { uint64_t strings, bytes; uint32_t nocase, version; } sx_seen_blob_info;
 #define SX_SEEN_BLOB_HEADER_BYTES 64u
@@ -961,7 +966,8 @@ int  sx_seen_set_add_strings(sx_ctx* ctx, sx_seen_set* set, const uint8_t* bytes
  * 8 bytes per record and the records, no string byte.  It takes any labels: on distinct words shift = 32, bits = 32, lo = 5 gives the
  * strings that occur at least five times in r; on count words shift = SX_SEEN_RESULTS_SHIFT, bits = 32, lo = k the strings at least
  * k results held.
- * Not built: removing strings, counts per Mission, canonical (sorted) blobs, Unicode folding, sharded entry points, an accessor to
+ * Not built: removing strings, counts per Mission, canonical (sorted) blobs, Unicode folding inside this call (sx_result_fold_device
+ * in front of it: simple folding), sharded entry points, an accessor to
  * the raw count table for hosts that stay on the GPU. */
 #define SX_SEEN_COUNTED 0x200u                  /* sx_seen_set_create flag: the set counts */
 #define SX_SEEN_RESULTS_SHIFT 0
@@ -996,7 +1002,8 @@ int  sx_result_select_labels_range_device(sx_ctx* ctx, const sx_result* r, const
  * where the key or the filter needs them, a field that sx_result_select_labels_range_device would refuse, labels of another result,
  * more than 2^32 - 2 findings that take part or 2^32 or more bytes of their strings — decided before anything is written.
  * SX_E_NOMEM: a block or the tables cannot be had.  *out = NULL on every error.
- * Not built: locale collation, Unicode folding, a second key, numeric-string keys, sharded entry points, top-k without a full sort. */
+ * Not built: locale collation, Unicode folding inside this call (sx_result_fold_device in front of it: simple folding), a second
+ * key, numeric-string keys, sharded entry points, top-k without a full sort. */
 enum { SX_ORDER_BY_STRING = 0, SX_ORDER_BY_LABEL_FIELD = 1 };
 enum { SX_ORDER_DESCENDING = 1u, SX_ORDER_NOCASE = 2u };
 typedef struct sx_order_spec {
@@ -1009,6 +1016,49 @@ typedef struct sx_order_spec {
 typedef struct sx_order_info { uint64_t findings, kept, rounds, tied, max_depth; } sx_order_info;
 int  sx_result_order_device(sx_ctx* ctx, const sx_result* r, const sx_labels* labels /* may be NULL */,
                             const sx_order_spec* spec, sx_result** out, sx_order_info* info /* may be NULL */);
+
+/* WHATEVER THE LETTER CASE, IN EVERY SCRIPT: sx_result_fold_device.  *out (sx_result_free) is a new result in HBM with the findings of
+ * r in the same order, every string replaced by its Unicode SIMPLE case folding; every operation above then works on the folded
+ * strings unchanged, and sx_labels_rebind carries an answer back to the original strings.  Output segment i corresponds to source
+ * segment i record for record: the same number of records of the same type (sx_finding or sx_finding16), the same sx_segment_info,
+ * every field of a record but str_off and str_len as it was, the folded strings back to back in record order.
+ * The rule, SX_FOLD_SIMPLE (flags = 0; no other flag is accepted yet): the string is walked from the left.  At a well-formed UTF-8
+ * sequence (Unicode Table 3-7: no overlong form, no surrogate, nothing above U+10FFFF, the whole sequence inside the string) of the
+ * code point c, fold(c) is written as UTF-8; any other byte is copied as it is and the walk goes on at the next byte.  fold() is
+ * CaseFolding.txt's statuses C and S (csrc/gen_fold_table.py, csrc/sx_fold_table.inc, which names its Unicode version): 'A' -> 'a',
+ * 'П' -> 'п', 'Σ' and 'ς' -> 'σ', U+212A KELVIN SIGN -> 'k'; a code point that has only a FULL folding stays: 'ß', 'İ'.  In Python:
+ * b.decode('utf-8', 'surrogateescape'), per character x = c.casefold() if that is one character, else c.lower() if that is one, else
+ * c; .encode('utf-8', 'surrogateescape').  The fold is idempotent.  A folded string has between a third and one and a half times
+ * its source's bytes (U+023A and U+023E grow from 2 to 3 bytes).
+ * `grep -i` in every script: fold the result, fold the patterns with sx_fold_utf8, label or select on the fold, sx_labels_rebind the
+ * labels to r, sx_result_select_labels_device on r — the ORIGINAL strings whose folding matches.  `sort -u`, the seen sets and the
+ * order work on the fold the same way.
+ * The fold counts as a selection: it lies in the selection block whose turn it is, takes a turn and ages selections exactly as a
+ * selection does; a call that returns an error takes none and writes no block.  r is read, never moved.
+ * *info (may be NULL): findings, bytes_in = the source strings' bytes, bytes_out = the folded strings', changed = the findings whose
+ * string the fold changes.
+ * Sources and SX_E_STATE exactly as sx_result_label_device, and for a source in the block this call would write.  SX_E_INVALID
+ * (sx_last_error says which): a NULL pointer, a flag, a segment whose folded strings have 2^32 bytes or more (str_off is 32-bit), a
+ * packed segment with a folded string longer than 65535 bytes (its str_len is 16-bit) — decided before anything is written.
+ * SX_E_NOMEM: a block or the tables cannot be had.  *out = NULL on every error.
+ *
+ * sx_fold_utf8: the same rule, the same code, for one byte string on the host; no context.  The folded bytes go to out[0, *written);
+ * out = NULL asks for the size: *written = the folded length, nothing is written.  SX_E_INVALID: a NULL pointer, a flag, or cap <
+ * the folded length — then *written says what is needed and out is untouched.  A caller folds its patterns with it.
+ *
+ * sx_labels_rebind: *out (sx_labels_free) is a new labels object with the words of `labels`, copied on the device, bound to the
+ * result `to`: sx_result_select_labels_device, sx_result_select_labels_range_device and sx_result_order_device accept it for `to`
+ * as they accept the labels made from it.  `to` must lie in HBM as sx_result_label_device asks of its source (else SX_E_STATE) and
+ * have as many segments as the labels' source and as many records in each (else SX_E_INVALID).  It is meant for a fold and its
+ * source, which correspond record for record; the library checks the shape only — that record i of `to` is the finding that word i
+ * speaks of is what the CALLER vouches for.  It is no selection and ages nothing; `labels` stays valid.
+ * Not built: full case folding ('ß' -> "ss"), Turkic rules, normalization (NFC / NFKC), locale collation, a packed segment expanded
+ * where a folded string outgrows it, sharded entry points. */
+enum { SX_FOLD_SIMPLE = 0u };
+typedef struct sx_fold_info { uint64_t findings, bytes_in, bytes_out, changed; } sx_fold_info;
+int  sx_fold_utf8(const uint8_t* in, uint64_t len, uint32_t flags, uint8_t* out, uint64_t cap, uint64_t* written);
+int  sx_result_fold_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_result** out, sx_fold_info* info /* may be NULL */);
+int  sx_labels_rebind(sx_ctx* ctx, const sx_labels* labels, const sx_result* to, sx_labels** out);
 
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);

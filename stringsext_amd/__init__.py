@@ -32,6 +32,7 @@ SX_SEEN_BLOB_HEADER_BYTES, SX_SEEN_BLOB_VERSION = 64, 1   # sx_seen_set_export (
 SX_SEEN_COUNTED, SX_SEEN_RESULTS_SHIFT, SX_SEEN_FINDINGS_SHIFT, SX_SEEN_BLOB_VERSION_COUNTED = 0x200, 0, 32, 2
 # sx_result_order_device (Result.order_device): the key, and the flags
 SX_ORDER_BY_STRING, SX_ORDER_BY_LABEL_FIELD, SX_ORDER_DESCENDING, SX_ORDER_NOCASE = 0, 1, 1, 2
+SX_FOLD_SIMPLE = 0   # sx_result_fold_device (Result.fold_device), sx_fold_utf8 (fold): Unicode simple case folding, the only rule yet
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -59,6 +60,7 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_seen_set_create", "sx_seen_set_info_get", "sx_seen_set_reset", "sx_seen_set_free", "sx_result_seen_device",
            "sx_seen_set_merge", "sx_seen_set_grow", "sx_seen_set_export_size", "sx_seen_set_export", "sx_seen_blob_info_get", "sx_seen_set_import", "sx_seen_set_add_strings",
            "sx_result_seen_counts_device", "sx_result_select_labels_range_device", "sx_result_order_device",
+           "sx_fold_utf8", "sx_result_fold_device", "sx_labels_rebind",
            "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
@@ -223,6 +225,10 @@ class OrderInfo(C.Structure):   # sx_order_info
     _fields_ = [("findings", C.c_uint64), ("kept", C.c_uint64), ("rounds", C.c_uint64), ("tied", C.c_uint64), ("max_depth", C.c_uint64)]
 
 
+class FoldInfo(C.Structure):   # sx_fold_info
+    _fields_ = [("findings", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64), ("changed", C.c_uint64)]
+
+
 class DistinctInfo(C.Structure):   # sx_distinct_info
     _fields_ = [("findings", C.c_uint64), ("distinct", C.c_uint64), ("repeated", C.c_uint64), ("rounds", C.c_uint32), ("table_log2", C.c_uint32)]
 
@@ -364,6 +370,9 @@ def lib():
     L.sx_result_seen_counts_device.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.sx_result_select_labels_range_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(vp)]
     L.sx_result_order_device.argtypes = [vp, vp, vp, C.POINTER(OrderSpec), C.POINTER(vp), C.POINTER(OrderInfo)]
+    L.sx_fold_utf8.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.sx_result_fold_device.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(FoldInfo)]
+    L.sx_labels_rebind.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -376,10 +385,28 @@ def lib():
     return L
 
 
+def fold(data):
+    """sx_fold_utf8: `data` (bytes) under Unicode SIMPLE case folding, the rule of Result.fold_device() and the same code —
+    data.decode('utf-8', 'surrogateescape'), per character c.casefold() if that is one character, else c.lower() if that is one,
+    else c, .encode('utf-8', 'surrogateescape'): 'ПАРОЛЬ' -> 'пароль', 'ς' -> 'σ', U+212A -> 'k'; 'ß' and 'İ' stay, and so does every
+    byte that is no well-formed UTF-8.  A caller folds its patterns with it before it looks for them in a folded Result."""
+    data = bytes(data)
+    n = C.c_uint64()
+    rc = lib().sx_fold_utf8(data, len(data), SX_FOLD_SIMPLE, None, 0, C.byref(n))
+    if rc != SX_OK:
+        raise SxError(rc, "sx_fold_utf8")
+    out = C.create_string_buffer(max(1, n.value))
+    rc = lib().sx_fold_utf8(data, len(data), SX_FOLD_SIMPLE, out, n.value, C.byref(n))
+    if rc != SX_OK:
+        raise SxError(rc, "sx_fold_utf8")
+    return out.raw[:n.value]
+
+
 class Result:
     """Findings of one sx_scan call, in the reference merger's order (src/main.rs:118-136)."""
 
     order_info = None      # order_device(): sx_order_info as a dict
+    fold_info = None       # fold_device(): sx_fold_info as a dict
 
     def __init__(self, scanner, handle):
         self._s, self.h = scanner, handle
@@ -672,6 +699,25 @@ class Result:
         self._s._chk(lib().sx_result_order_device(self._s.h, self.h, labels._handle() if labels is not None else None, C.byref(spec), C.byref(out), C.byref(info)))
         res = Result(self._s, out)
         res.order_info = {k: getattr(info, k) for k, _ in OrderInfo._fields_}
+        return res
+
+    def fold_device(self):
+        """sx_result_fold_device: WHATEVER THE LETTER CASE, IN EVERY SCRIPT — a new Result on the device with this Result's findings
+        in the same order, segment for segment and record for record, every string replaced by its Unicode simple case folding
+        (fold() is the rule); every other field and the segments' SegmentInfo stay.  select_device(), label_device(),
+        distinct_device(), seen_device(), order_device() ... of the new Result then compare folded strings — fold() the patterns —,
+        and Labels.rebind(this Result) carries their answer back to the original strings: `grep -i` is
+        f = r.fold_device(); r.select_device(f.label_device(s.label_set([fold(p)])).rebind(r), any=1).  The new Result lies on the
+        device like a selection and counts as one for "valid until the second select_device() after this one"; .fold_info is
+        sx_fold_info as a dict: findings, bytes_in, bytes_out, changed.  This Result is not moved.  Raises SxError: SX_E_STATE
+        wherever printed_device() would refuse this Result, SX_E_INVALID for a segment whose folded strings outgrow 32-bit offsets
+        or a packed record's 16-bit length."""
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        out, info = C.c_void_p(), FoldInfo()
+        self._s._chk(lib().sx_result_fold_device(self._s.h, self.h, SX_FOLD_SIMPLE, C.byref(out), C.byref(info)))
+        res = Result(self._s, out)
+        res.fold_info = {k: getattr(info, k) for k, _ in FoldInfo._fields_}
         return res
 
     def free(self):
@@ -998,6 +1044,19 @@ class Labels(_DeviceHandle):
                 raise SxError(rc, "sx_labels_segment_device")
             out.append((p.value, n.value))
         return out
+
+    def rebind(self, result):
+        """sx_labels_rebind: new Labels with these words, copied on the device, bound to `result` — which select_device(),
+        select_range_device() and order_device() of `result` then take as they take the Labels made from it.  `result` lies on the
+        device and has this Labels' segments and record counts (else SxError SX_E_INVALID); that record i of `result` is the
+        finding word i speaks of — a fold and its source — is what the caller vouches for.  No selection: nothing ages."""
+        if not isinstance(result, Result):
+            raise TypeError("rebind takes a Result")
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        out = C.c_void_p()
+        self._s._chk(lib().sx_labels_rebind(self._s.h, self._handle(), result.h, C.byref(out)))
+        return Labels(self._s, out)
 
     def download(self):
         """one list of ints per segment: the labels in record order (sx_device_download)"""

@@ -314,6 +314,15 @@ size_t extract_scratch_bytes(uint64_t n);
 hipError_t extract_measure(ExtractParams* P, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint64_t** count, const uint64_t** bytes);
 size_t extract_place_scratch_bytes(uint64_t n_out);
 hipError_t extract_place(const ExtractParams& P, void* out_recs, uint64_t n_out, uint8_t* out_arena, void* scratch, size_t scratch_bytes, hipStream_t stream);
+// The Unicode case fold on the device (sx_fold_dev.hip, FoldParams: sx_fold_core.hpp), a segment at a time, in the shape of the
+// selection's two passes.  fold_measure: pass 1 — fills P's per-record and per-wavefront tables inside `scratch`
+// (fold_scratch_bytes(n), 256-aligned); *count, *bytes, *totals = the device words with the number of records, the folded bytes and
+// the segment's kFoldTotals totals, valid once `stream` has got there; fold_place: every record, with its new str_off and str_len, to
+// out_recs, the folded strings back to back to out_arena — what it writes is what pass 1 measured, the caller has checked that it fits
+struct FoldParams;
+size_t fold_scratch_bytes(uint64_t n);
+hipError_t fold_measure(FoldParams* P, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint64_t** count, const uint64_t** bytes, const uint64_t** totals);
+hipError_t fold_place(const FoldParams& P, void* out_recs, uint8_t* out_arena, hipStream_t stream);
 // The keyword tally on the device (sx_seltally_dev.hip, SeltallyParams: sx_seltally_core.hpp), a segment at a time: seltally_kernel adds
 // the segment's hits to the set's counters; nothing else is written, and the counters are valid once `stream` has got there
 struct SeltallyParams;

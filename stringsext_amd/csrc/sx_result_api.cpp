@@ -1,5 +1,5 @@
 // sx_result_api.cpp — the C-ABI of include/stringsext_amd.h for a result that stays in HBM (SX_OPT_RESULT_ON_DEVICE): the print, the
-// selections, the extraction, the tally, the labels, the duplicate strings and the seen set — with its merge, growth, blob and string
+// selections, the extraction, the Unicode case fold, the tally, the labels and their rebinding, the duplicate strings and the seen set — with its merge, growth, blob and string
 // lists, and its counts —, and the compiled sets they take.  What the operations share is here once — the view of a segment, a set's upload, a
 // handle's device and memory, the counters' reset, a buffer that grows, a result's labels, the two passes of whatever writes a new
 // result, the mark and add passes of whatever goes into a seen set —; what tells them apart is in their lane functions
@@ -19,6 +19,7 @@
 #include "sx_label_core.hpp"
 #include "sx_distinct_core.hpp"
 #include "sx_order_core.hpp"
+#include "sx_fold_core.hpp"
 #include "sx_seen_core.hpp"
 #include "sx_seen_merge_core.hpp"
 #include "sx_seen_count_core.hpp"
@@ -236,7 +237,9 @@ sx_labels* labels_of(const sx_ctx* ctx, const sx_result* r, uint64_t* bytes) {
 // The two passes of an operation that writes a new result, a segment at a time, as select_on_device drives them.  measure: pass 1
 // of segment i inside `scratch` (scratch_bytes(seg.n), 256-aligned); *count and *bytes = the device words that will hold the output's
 // records — a word of count_bytes() bytes — and string bytes.  place: pass 2 of segment i, its c records to `recs`, their strings to
-// `arena` (scratch: place_scratch_bytes(c)).
+// `arena` (scratch: place_scratch_bytes(c)).  settle: between the passes, once per segment and in segment order, with what measure left of
+// segment i: SX_OK, or the code — and in *why the message — that ends the call before a block is written or aged.  A selection and an
+// extraction have nothing to settle; the fold reads its totals there (SX_E_HIP if it cannot), judges them (SX_E_INVALID) and keeps them.
 struct TwoPass {
     virtual ~TwoPass() = default;
     virtual size_t count_bytes() const = 0;
@@ -244,6 +247,7 @@ struct TwoPass {
     virtual hipError_t measure(size_t i, const SegRef& seg, void* scratch, size_t bytes, hipStream_t st, const void** count, const uint64_t** nbytes) = 0;
     virtual size_t place_scratch_bytes(uint64_t c) const = 0;
     virtual hipError_t place(size_t i, void* recs, uint64_t c, uint8_t* arena, void* scratch, size_t bytes, hipStream_t st) = 0;
+    virtual int settle(size_t i, uint64_t c, uint64_t bytes, std::string* why) { return SX_OK; }
 };
 
 // grep (sx_select_dev.hip): pass 1 by `by.kind` — the patterns of `pat`, a compiled keyword set, a compiled regex set (of `pat` they
@@ -293,7 +297,36 @@ struct Extraction final : TwoPass {
     }
 };
 
-// A new result out of one in HBM, for the five entry points, whose arguments are checked: pass 1 of every segment, one wait for the
+// casefold (sx_fold_dev.hip): an output record is its source record with another string, so segment i of the output is segment i of
+// the source record for record; the folded strings may have more bytes than the source's
+struct Fold final : TwoPass {
+    std::vector<FoldParams> F;
+    std::vector<const uint64_t*> d_totals;
+    sx_fold_info info{ 0, 0, 0, 0 };
+    explicit Fold(size_t ns) : F(ns), d_totals(ns) {}
+    size_t count_bytes() const override { return sizeof(uint64_t); }
+    size_t scratch_bytes(uint64_t n) const override { return fold_scratch_bytes(n); }
+    hipError_t measure(size_t i, const SegRef& seg, void* scratch, size_t bytes, hipStream_t st, const void** count, const uint64_t** nbytes) override {
+        F[i] = params_of<FoldParams>(seg);
+        return fold_measure(&F[i], scratch, bytes, st, (const uint64_t**)count, nbytes, &d_totals[i]);
+    }
+    size_t place_scratch_bytes(uint64_t c) const override { return 0; }
+    hipError_t place(size_t i, void* recs, uint64_t c, uint8_t* arena, void* scratch, size_t bytes, hipStream_t st) override {
+        return c == F[i].n ? fold_place(F[i], recs, arena, st) : hipErrorInvalidValue;
+    }
+    int settle(size_t i, uint64_t c, uint64_t bytes, std::string* why) override {
+        uint64_t tot[kFoldTotals] = { 0 };
+        const hipError_t e = hipMemcpy(tot, d_totals[i], sizeof tot, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { (void)hipGetLastError(); *why = "device fold: segment " + std::to_string(i) + "'s totals: " + hipGetErrorString(e); return SX_E_HIP; }
+        const FoldFit fit = fold_segment_fits(F[i].packed, bytes, tot[kFoldLongest]);
+        if (fit == kFoldTooManyBytes) { *why = "fold: segment " + std::to_string(i) + " has " + std::to_string(bytes) + " bytes of folded strings: a 32-bit str_off holds less than 2^32"; return SX_E_INVALID; }
+        if (fit == kFoldPackedTooLong) { *why = "fold: a string of the packed segment " + std::to_string(i) + " has " + std::to_string(tot[kFoldLongest]) + " bytes when it is folded: the 16-bit str_len of sx_finding16 holds 65535"; return SX_E_INVALID; }
+        info.findings += c; info.bytes_in += tot[kFoldBytesIn]; info.bytes_out += bytes; info.changed += tot[kFoldChanged];
+        return SX_OK;
+    }
+};
+
+// A new result out of one in HBM, for the six entry points, whose arguments are checked: pass 1 of every segment, one wait for the
 // segments' totals, the selection block, pass 2 of every segment that has output records, one more wait.  The source is read, never
 // moved.  The blocks take turns: the one this call writes held the selection before the last one.
 int select_on_device(sx_ctx* ctx, const sx_result* r, TwoPass& pass, sx_result** out) {
@@ -326,6 +359,8 @@ int select_on_device(sx_ctx* ctx, const sx_result* r, TwoPass& pass, sx_result**
             ctx->set_err("segment " + std::to_string(i) + " has " + std::to_string(c) + " matches: more than the 32-bit counters of a segment hold");
             return SX_E_INVALID;
         }
+        std::string why;
+        { const int rc = pass.settle(i, c, b_sel[i], &why); if (rc != SX_OK) { ctx->set_err(why); return rc; } }
         n_sel[i] = c;
         if (!c) continue;
         base[i] = block;
@@ -1070,6 +1105,62 @@ int sx_result_order_device(sx_ctx* ctx, const sx_result* r, const sx_labels* lab
         { const int rc = result_on_device(ctx, r, "sort on the host"); if (rc != SX_OK) return rc; }
     }
     return order_on_device(ctx, r, labels, *spec, out, info);
+}
+
+static const FoldTable kFoldHost{ kFoldIndex, kFoldPages };
+
+int sx_fold_utf8(const uint8_t* in, uint64_t len, uint32_t flags, uint8_t* out, uint64_t cap, uint64_t* written) {
+    if (written) *written = 0;
+    if ((!in && len) || !written || flags != SX_FOLD_SIMPLE) return SX_E_INVALID;
+    bool changed;
+    const uint64_t need = fold_measure_string(kFoldHost, in, len, &changed);
+    *written = need;
+    if (!out) return SX_OK;            // (the size was asked for)
+    if (need > cap) return SX_E_INVALID;
+    (void)fold_place_string(kFoldHost, in, len, out);
+    return SX_OK;
+}
+
+int sx_result_fold_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_result** out, sx_fold_info* info) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !out) return SX_E_INVALID;
+    if (flags != SX_FOLD_SIMPLE) { ctx->set_err("fold: flags other than SX_FOLD_SIMPLE"); return SX_E_INVALID; }
+    if (host_only(ctx, "fold")) return SX_E_STATE;
+    { const int rc = result_on_device(ctx, r, "fold on the host, with sx_fold_utf8"); if (rc != SX_OK) return rc; }
+    Fold fold(r->r.segs.size());
+    const int rc = select_on_device(ctx, r, fold, out);
+    if (rc == SX_OK && info) *info = fold.info;
+    return rc;
+}
+
+int sx_labels_rebind(sx_ctx* ctx, const sx_labels* labels, const sx_result* to, sx_labels** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !labels || !to || !out) return SX_E_INVALID;
+    if (host_only(ctx, "labels")) return SX_E_STATE;
+    if (on_another_device(ctx, *labels, "the labels lie")) return SX_E_INVALID;
+    { const int rc = result_on_device(ctx, to, "label on the host"); if (rc != SX_OK) return rc; }
+    bool same = labels->segs.size() == to->r.segs.size();
+    for (size_t i = 0; same && i < labels->segs.size(); i++) same = labels->segs[i].n == to->r.segs[i].ext_nf;
+    if (!same) { ctx->set_err("rebind: the result has other segments or other record counts than the labels' source"); return SX_E_INVALID; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    uint64_t bytes = 0;
+    sx_labels* lab = labels_of(ctx, to, &bytes);
+    if (!lab) {
+        ctx->set_err("rebind: no memory for " + std::to_string(bytes) + " bytes of labels");
+        return SX_E_NOMEM;
+    }
+    // (the same record counts: the same layout, an array per segment, each 256-byte aligned)
+    hipError_t e = bytes ? hipMemcpyAsync(lab->mem, labels->mem, bytes, hipMemcpyDeviceToDevice, st) : hipSuccess;
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) {
+        sx_labels_free(lab);
+        ctx->set_err(std::string("rebind: ") + hipGetErrorString(e));
+        return SX_E_HIP;
+    }
+    *out = lab;
+    return SX_OK;
 }
 
 int sx_result_distinct_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_labels** out, sx_distinct_info* info) {

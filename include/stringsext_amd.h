@@ -1060,6 +1060,47 @@ int  sx_fold_utf8(const uint8_t* in, uint64_t len, uint32_t flags, uint8_t* out,
 int  sx_result_fold_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_result** out, sx_fold_info* info /* may be NULL */);
 int  sx_labels_rebind(sx_ctx* ctx, const sx_labels* labels, const sx_result* to, sx_labels** out);
 
+/* WHAT A STRING LOOKS LIKE: sx_result_measure_device.  *out (sx_labels_free) holds one word per finding of r, laid out and bound to r
+ * as every other labels object, so sx_result_select_labels_device, sx_result_select_labels_range_device, sx_result_order_device and
+ * sx_labels_rebind take it: `awk 'length >= 32'` is a range on the chars field, "only hex digits" a mask on the class bits, "entropy
+ * above 4.5 bits per byte" a range on the entropy field with lo = 4.5 x 4096.
+ * The word of a string of n bytes, c[b] = how often byte b occurs in it (n = 0: the word is 0):
+ *   bits  0..15  SX_MEASURE_ENTROPY_SHIFT, 16 bits   ENT: the Shannon entropy of the bytes, in bits per byte x 4096: 0 for "aaaa",
+ *                                                    4096 for "abab", 16384 for the 16 hex digits once each, 32768 for all 256 bytes
+ *                                                    equally often
+ *   bits 16..24  SX_MEASURE_DISTINCT_SHIFT, 9 bits   the number of b with c[b] > 0: 0 to 256
+ *   bits 25..31  the class bits, each set iff the string holds at least one such byte: SX_MEASURE_LOWER 'a'..'z', SX_MEASURE_UPPER
+ *                'A'..'Z', SX_MEASURE_DIGIT '0'..'9', SX_MEASURE_SPACE 0x20 and 0x09, SX_MEASURE_PUNCT the other bytes of 0x21..0x7E,
+ *                SX_MEASURE_CONTROL 0x00..0x1F without 0x09, and 0x7F, SX_MEASURE_HIGH 0x80 and above
+ *   bits 32..63  SX_MEASURE_CHARS_SHIFT, 32 bits     the bytes outside 0x80..0xBF: the UTF-8 characters of well-formed text, the byte
+ *                                                    count of ASCII
+ * ENT is defined in integers, so that the device, the host and a restatement agree bit for bit.  LG(x) for 1 <= x < 2^32 is log2(x) in
+ * units of 2^-16, at most 1.00001 units below it and never above: e = 31 - clz(x); m = x << (31 - e); f = 0; sixteen times { m = (m * m)
+ * >> 31 (a 64-bit product); f <<= 1; if m >= 2^32 { f |= 1; m >>= 1 } }; LG = e << 16 | f.  Then T = n x LG(n) - sum over b of c[b] x
+ * LG(c[b]) in 64 bits — LG is monotone, so T >= 0 —, and ENT = min(65535, T / (16 x n)).
+ * flags must be 0.  *info (may be NULL): findings, bytes = the strings' bytes, chars = the sum of the chars fields, wide = the strings
+ * of more than 255 bytes (which a wavefront measures, where the others take a lane), ascii = the strings without SX_MEASURE_HIGH.
+ * The call is no selection: it lies in no selection block, takes no turn, ages nothing, and r is read, never moved; only the words, a
+ * list of the wide strings' records and the call's totals are written.  Sources, SX_E_STATE, SX_E_INVALID and SX_E_NOMEM exactly as
+ * sx_result_seen_counts_device, and SX_E_INVALID for a flag or a segment of 2^32 findings or more.  *out = NULL on every error.
+ *
+ * sx_measure_bytes: the same rule, the same code, for one byte string on the host; no context.  SX_E_INVALID: a NULL pointer (s may
+ * be NULL where len is 0), a flag, or len >= 2^32.
+ * Not built: entropy over characters instead of bytes, n-gram statistics, per-script classes, longest run, sharded entry points. */
+#define SX_MEASURE_ENTROPY_SHIFT 0
+#define SX_MEASURE_DISTINCT_SHIFT 16
+#define SX_MEASURE_CHARS_SHIFT 32
+#define SX_MEASURE_LOWER   ((uint64_t)1 << 25)
+#define SX_MEASURE_UPPER   ((uint64_t)1 << 26)
+#define SX_MEASURE_DIGIT   ((uint64_t)1 << 27)
+#define SX_MEASURE_SPACE   ((uint64_t)1 << 28)
+#define SX_MEASURE_PUNCT   ((uint64_t)1 << 29)
+#define SX_MEASURE_CONTROL ((uint64_t)1 << 30)
+#define SX_MEASURE_HIGH    ((uint64_t)1 << 31)
+typedef struct sx_measure_info { uint64_t findings, bytes, chars, wide, ascii; } sx_measure_info;
+int  sx_result_measure_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_labels** out, sx_measure_info* info /* may be NULL */);
+int  sx_measure_bytes(const uint8_t* s, uint64_t len, uint32_t flags, uint64_t* word);
+
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);
 

@@ -33,6 +33,10 @@ SX_SEEN_COUNTED, SX_SEEN_RESULTS_SHIFT, SX_SEEN_FINDINGS_SHIFT, SX_SEEN_BLOB_VER
 # sx_result_order_device (Result.order_device): the key, and the flags
 SX_ORDER_BY_STRING, SX_ORDER_BY_LABEL_FIELD, SX_ORDER_DESCENDING, SX_ORDER_NOCASE = 0, 1, 1, 2
 SX_FOLD_SIMPLE = 0   # sx_result_fold_device (Result.fold_device), sx_fold_utf8 (fold): Unicode simple case folding, the only rule yet
+# sx_result_measure_device (Result.measure_device), sx_measure_bytes (measure): the fields and the class bits of a word
+SX_MEASURE_ENTROPY_SHIFT, SX_MEASURE_DISTINCT_SHIFT, SX_MEASURE_CHARS_SHIFT = 0, 16, 32
+SX_MEASURE_LOWER, SX_MEASURE_UPPER, SX_MEASURE_DIGIT, SX_MEASURE_SPACE = 1 << 25, 1 << 26, 1 << 27, 1 << 28
+SX_MEASURE_PUNCT, SX_MEASURE_CONTROL, SX_MEASURE_HIGH = 1 << 29, 1 << 30, 1 << 31
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -60,7 +64,7 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_seen_set_create", "sx_seen_set_info_get", "sx_seen_set_reset", "sx_seen_set_free", "sx_result_seen_device",
            "sx_seen_set_merge", "sx_seen_set_grow", "sx_seen_set_export_size", "sx_seen_set_export", "sx_seen_blob_info_get", "sx_seen_set_import", "sx_seen_set_add_strings",
            "sx_result_seen_counts_device", "sx_result_select_labels_range_device", "sx_result_order_device",
-           "sx_fold_utf8", "sx_result_fold_device", "sx_labels_rebind",
+           "sx_fold_utf8", "sx_result_fold_device", "sx_labels_rebind", "sx_result_measure_device", "sx_measure_bytes",
            "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
@@ -229,6 +233,10 @@ class FoldInfo(C.Structure):   # sx_fold_info
     _fields_ = [("findings", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64), ("changed", C.c_uint64)]
 
 
+class MeasureInfo(C.Structure):   # sx_measure_info
+    _fields_ = [("findings", C.c_uint64), ("bytes", C.c_uint64), ("chars", C.c_uint64), ("wide", C.c_uint64), ("ascii", C.c_uint64)]
+
+
 class DistinctInfo(C.Structure):   # sx_distinct_info
     _fields_ = [("findings", C.c_uint64), ("distinct", C.c_uint64), ("repeated", C.c_uint64), ("rounds", C.c_uint32), ("table_log2", C.c_uint32)]
 
@@ -373,6 +381,8 @@ def lib():
     L.sx_fold_utf8.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.sx_result_fold_device.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(FoldInfo)]
     L.sx_labels_rebind.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.sx_result_measure_device.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(MeasureInfo)]
+    L.sx_measure_bytes.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -400,6 +410,19 @@ def fold(data):
     if rc != SX_OK:
         raise SxError(rc, "sx_fold_utf8")
     return out.raw[:n.value]
+
+
+def measure(data):
+    """sx_measure_bytes: the word of Result.measure_device() for `data` (bytes), by the same code — (word >> SX_MEASURE_ENTROPY_SHIFT)
+    & 0xFFFF the entropy of its bytes in bits per byte x 4096, (word >> SX_MEASURE_DISTINCT_SHIFT) & 0x1FF how many different bytes
+    it has, the class bits SX_MEASURE_LOWER ... SX_MEASURE_HIGH, word >> SX_MEASURE_CHARS_SHIFT the bytes outside 0x80..0xBF; 0 for
+    b"".  SxError SX_E_INVALID for 2^32 bytes or more."""
+    data = bytes(data)
+    word = C.c_uint64()
+    rc = lib().sx_measure_bytes(data, len(data), 0, C.byref(word))
+    if rc != SX_OK:
+        raise SxError(rc, "sx_measure_bytes")
+    return word.value
 
 
 class Result:
@@ -720,6 +743,24 @@ class Result:
         res.fold_info = {k: getattr(info, k) for k, _ in FoldInfo._fields_}
         return res
 
+    def measure_device(self):
+        """sx_result_measure_device: WHAT the strings LOOK like — Labels, one 64-bit word per finding in HBM, measure() of its
+        string: the entropy of its bytes (bits 0..15, bits per byte x 4096), how many different bytes (bits 16..24), the class bits
+        SX_MEASURE_LOWER, UPPER, DIGIT, SPACE, PUNCT, CONTROL, HIGH (set iff the string holds such a byte) and its characters (bits
+        32..63: the bytes outside 0x80..0xBF).  select_range_device(m, SX_MEASURE_CHARS_SHIFT, 32, 32, 2**32 - 1) is
+        `awk 'length >= 32'`; select_range_device(m, SX_MEASURE_ENTROPY_SHIFT, 16, int(4.5 * 4096), 65535) "entropy above 4.5 bits
+        per byte"; select_device(m, none=SX_MEASURE_HIGH | SX_MEASURE_SPACE) one ASCII token; order_device("field", m, shift=0,
+        bits=16, descending=True, limit=100) the hundred most random strings.  The Labels' .info is sx_measure_info as a dict:
+        findings, bytes, chars, wide (strings of more than 255 bytes), ascii (strings without SX_MEASURE_HIGH).  This Result is read,
+        not moved, and no selection ages.  Raises SxError: SX_E_STATE wherever printed_device() would refuse this Result."""
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        out, info = C.c_void_p(), MeasureInfo()
+        self._s._chk(lib().sx_result_measure_device(self._s.h, self.h, 0, C.byref(out), C.byref(info)))
+        labels = Labels(self._s, out)
+        labels.info = {k: getattr(info, k) for k, _ in MeasureInfo._fields_}
+        return labels
+
     def free(self):
         if self.h:
             lib().sx_result_free(self.h)
@@ -1028,7 +1069,7 @@ class Labels(_DeviceHandle):
     device memory: free() them before or after the Scanner's close()."""
 
     _free, _freed = "sx_labels_free", "the Labels have been freed"
-    info = None      # distinct_device(): sx_distinct_info as a dict; seen_device(): sx_seen_info
+    info = None      # distinct_device(): sx_distinct_info as a dict; seen_device(): sx_seen_info; measure_device(): sx_measure_info
 
     def __init__(self, scanner, handle):
         self._s, self.h = scanner, handle

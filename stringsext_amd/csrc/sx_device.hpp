@@ -323,6 +323,11 @@ struct FoldParams;
 size_t fold_scratch_bytes(uint64_t n);
 hipError_t fold_measure(FoldParams* P, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint64_t** count, const uint64_t** bytes, const uint64_t** totals);
 hipError_t fold_place(const FoldParams& P, void* out_recs, uint8_t* out_arena, hipStream_t stream);
+// What the strings look like, on the device (sx_measure_dev.hip, MeasureParams: sx_measure_core.hpp), a segment at a time:
+// measure_narrow_kernel writes the words of the strings a lane can measure and lists the others, measure_wide_kernel behind it writes
+// theirs; both add to the call's totals.  Nothing else is written, and all of it is valid once `stream` has got there
+struct MeasureParams;
+hipError_t measure_launch(const MeasureParams& P, hipStream_t stream);
 // The keyword tally on the device (sx_seltally_dev.hip, SeltallyParams: sx_seltally_core.hpp), a segment at a time: seltally_kernel adds
 // the segment's hits to the set's counters; nothing else is written, and the counters are valid once `stream` has got there
 struct SeltallyParams;

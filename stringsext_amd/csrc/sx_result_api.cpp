@@ -1,5 +1,5 @@
 // sx_result_api.cpp — the C-ABI of include/stringsext_amd.h for a result that stays in HBM (SX_OPT_RESULT_ON_DEVICE): the print, the
-// selections, the extraction, the Unicode case fold, the tally, the labels and their rebinding, the duplicate strings and the seen set — with its merge, growth, blob and string
+// selections, the extraction, the Unicode case fold, what the strings look like, the tally, the labels and their rebinding, the duplicate strings and the seen set — with its merge, growth, blob and string
 // lists, and its counts —, and the compiled sets they take.  What the operations share is here once — the view of a segment, a set's upload, a
 // handle's device and memory, the counters' reset, a buffer that grows, a result's labels, the two passes of whatever writes a new
 // result, the mark and add passes of whatever goes into a seen set —; what tells them apart is in their lane functions
@@ -20,6 +20,7 @@
 #include "sx_distinct_core.hpp"
 #include "sx_order_core.hpp"
 #include "sx_fold_core.hpp"
+#include "sx_measure_core.hpp"
 #include "sx_seen_core.hpp"
 #include "sx_seen_merge_core.hpp"
 #include "sx_seen_count_core.hpp"
@@ -1131,6 +1132,60 @@ int sx_result_fold_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_re
     const int rc = select_on_device(ctx, r, fold, out);
     if (rc == SX_OK && info) *info = fold.info;
     return rc;
+}
+
+static constexpr MeasureClg kMeasureClgHost = measure_clg_table();
+
+int sx_measure_bytes(const uint8_t* s, uint64_t len, uint32_t flags, uint64_t* word) {
+    if (word) *word = 0;
+    if ((!s && len) || !word || flags != 0 || len >> 32) return SX_E_INVALID;
+    *word = measure_string_host(s, (uint32_t)len, kMeasureClgHost.v);
+    return SX_OK;
+}
+
+// What the strings look like, where the findings lie (sx_measure_dev.hip): the words' memory is had as the labels' is, then the call's
+// own tables — [the totals and the cursor: 256 bytes][the list of the longest segment's records] in sx_ctx::d_distinct, which grows on
+// demand and is no selection block —, then one launch per segment on the selections' stream, the list used by one segment after the
+// other, and one read of the totals.
+int sx_result_measure_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_labels** out, sx_measure_info* info) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !out) return SX_E_INVALID;
+    if (flags != 0) { ctx->set_err("measure: no flag is defined yet"); return SX_E_INVALID; }
+    if (host_only(ctx, "measure")) return SX_E_STATE;
+    { const int rc = result_on_device(ctx, r, "measure on the host, with sx_measure_bytes"); if (rc != SX_OK) return rc; }
+    uint64_t longest = 0;
+    for (const MissionFindings& s : r->r.segs) {
+        if (s.ext_nf >> 32) { ctx->set_err("measure: a segment of 2^32 findings or more"); return SX_E_INVALID; }
+        longest = s.ext_nf > longest ? s.ext_nf : longest;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    uint64_t bytes = 0, tot[kMeasureTotals] = { 0, 0, 0, 0, 0 };
+    const uint64_t table_bytes = 256 + up256(longest * sizeof(uint32_t));
+    sx_labels* lab = labels_of(ctx, r, &bytes);
+    if (!lab || !device_room(&ctx->d_distinct, &ctx->d_distinct_cap, table_bytes)) {
+        ctx->set_err("device measure: no memory for " + std::to_string(bytes) + " bytes of words and " + std::to_string(table_bytes) + " bytes of tables");
+        sx_labels_free(lab);
+        return SX_E_NOMEM;
+    }
+    uint8_t* const tab = ctx->d_distinct;
+    hipError_t e = hipMemsetAsync(tab, 0, 256, st);
+    for (size_t i = 0; e == hipSuccess && i < lab->segs.size(); i++) {
+        MeasureParams p = params_of<MeasureParams>(seg_ref(r->r.segs[i]));
+        p.labels = (uint64_t*)lab->segs[i].d; p.totals = (uint64_t*)tab; p.cursor = (uint64_t*)tab + kMeasureTotals; p.list = (uint32_t*)(tab + 256);
+        e = measure_launch(p, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(tot, tab, sizeof tot, hipMemcpyDeviceToHost, st);
+    { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        sx_labels_free(lab);
+        ctx->set_err(std::string("device measure: ") + hipGetErrorString(e));
+        return SX_E_HIP;
+    }
+    if (info) *info = sx_measure_info{ tot[kMeasureFindings], tot[kMeasureBytes], tot[kMeasureChars], tot[kMeasureWide], tot[kMeasureAscii] };
+    *out = lab;
+    return SX_OK;
 }
 
 int sx_labels_rebind(sx_ctx* ctx, const sx_labels* labels, const sx_result* to, sx_labels** out) {

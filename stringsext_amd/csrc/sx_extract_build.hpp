@@ -1,6 +1,6 @@
 // sx_extract_build.hpp — a list of byte regular expressions compiled into the table that the extraction kernels walk
 // (sx_extract_regex_create): the front end of sx_selre_build.cpp (sx_selre_front.hpp: the same parser, the same count of positions, the
-// same NFA — so the same language, refusals, limits and texts), then a subset construction of its own.  Host only, no HIP header:
+// same NFA — so the same language, refusals, limits and texts), then that header's subset construction with a Rule of its own.  Host only, no HIP header:
 // the test-only harness tests/native/extract_core_host.cpp compiles it with g++ (tests/test_extract_core.py).
 //
 // The question is "where do the matches lie", as `grep -oE` answers it: at an offset o the longest e such that some pattern matches

@@ -2,19 +2,25 @@
 // sx_extract_build.cpp: "where do the matches lie"; sx_label_build.cpp: "which patterns match"), host only and internal to them: the parser (a syntax tree per pattern; whatever
 // Python's `re` would read differently is refused with the offset), the count of the positions with the repeats unrolled (on the
 // tree: nothing is allocated for a pattern that is refused for it), the Thompson NFA, the closure over its edges without a byte, the
-// byte classes of the construction, and, behind either builder's subset construction, Hopcroft's minimisation with the merge of the
-// byte classes whose columns have become equal.  All builders accept the same language, refuse the same forms and meet the same
-// limits with the same texts because they are these functions.  No HIP header: the test-only harnesses compile it with g++.
+// byte classes of the construction, the subset construction (a builder's Rule says whether the patterns are re-entered and what
+// tells two subsets apart), Hopcroft's minimisation with the merge of the byte classes whose columns have become equal, the
+// breadth-first order, the numbering by rank, the rows, and the shell that says what memory ran out for.  All builders accept the
+// same language, refuse the same forms and meet the same limits with the same texts because they are these functions; what is left
+// in a builder's own file is its Rule, its ranks and the fields that only its table has.  No HIP header: the test-only harnesses
+// compile it with g++.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
+#include <new>
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
 #include "../../include/stringsext_amd.h"
+#include "sx_selset_build.hpp"
 
 namespace sx {
 namespace refront {
@@ -287,10 +293,10 @@ struct Nfa {
     }
 };
 
-// what is reached from NFA nodes without a byte: the byte nodes, and whether the string is accepted here whatever follows
-// (`always`) or if it ends here (`at_end`: through a `$`); `here` and `end` say the same per accept node: bit p for pattern p's
-// (bit 0 alone where the NFA has one accept for all)
-struct Closure { std::vector<uint32_t> chars; bool always = false, at_end = false; uint64_t here = 0, end = 0; };
+// what is reached from NFA nodes without a byte: the byte nodes, and the accept nodes through which the string is accepted here
+// whatever follows (`here`) or if it ends here (`end`: through a `$`): bit p for pattern p's (bit 0 alone where the NFA has one
+// accept for all)
+struct Closure { std::vector<uint32_t> chars; uint64_t here = 0, end = 0; };
 
 struct Closer {
     const Nfa& nfa;
@@ -313,10 +319,7 @@ struct Closer {
             case nSplit: stack.push_back({ N.b, mode }); stack.push_back({ N.a, mode }); break;
             case nBol: if (at_start) stack.push_back({ N.a, mode }); break;
             case nEol: stack.push_back({ N.a, 1 }); break;
-            case nAccept:
-                if (mode) { out->at_end = true; out->end |= (uint64_t)1 << N.set; }
-                else { out->always = true; out->here |= (uint64_t)1 << N.set; }
-                break;
+            case nAccept: (mode ? out->end : out->here) |= (uint64_t)1 << N.set; break;
             }
         }
         std::sort(out->chars.begin(), out->chars.end());
@@ -413,22 +416,121 @@ inline int front_build(const sx_pattern* patterns, uint32_t n_patterns, uint32_t
     return SX_OK;
 }
 
-// Step 5.  The minimal automaton of a complete DFA D[s * K + c] over n states whose states are told apart by `kinds` (values below
-// n_kinds; Kind: uint8_t for the regex set and the extraction, uint32_t where there may be more than 256 of them) to begin with: Hopcroft's blocks of states that no string tells apart, the quotient, then the byte classes whose columns
-// are equal in every block, numbered by their lowest byte.
-template <class Kind>
-struct QuotientOf {
-    uint32_t M = 0;                   // blocks
+// Step 4.  The subset construction: a complete DFA D[s * K + c] over n subsets of the NFA's byte nodes, each of a kind below
+// n_kinds, and its starts (one, twice, where the patterns are re-entered).
+struct SubsetDfa {
+    uint32_t n = 0, n_kinds = 0, starts[2] = { 0, 0 };
+    std::vector<uint32_t> D, kinds;
+};
+
+// A Rule says what a builder's automaton is.  `reenter`: the unanchored search — every pattern is entered again in front of every
+// byte, without the `^` edges; one start, with them.  A subset then always holds the re-entry's byte nodes, so its key is what it
+// holds BESIDES them (a keyword list's re-entry has a node per keyword), and what the re-entry's own nodes give with a byte is worked
+// out once per class.  Not `reenter`: the anchored walk, two starts — with the `^` edges, then without them —, and what may be
+// accepted in front of the first byte does not count.  mark(here, end, key), of the subset that holds the byte nodes in `key` and
+// whose closures' accepts are `here` and `end`: it brings the masks to what counts of them and appends to the key whatever else
+// tells two subsets of these nodes apart (the key's words count against kSubsetEntries); true: the subset is, whatever its nodes,
+// the ONE absorbing state — made when first needed, its row points at itself.  kind(here, end), of a new subset, with the masks
+// as mark left them: what Hopcroft tells states apart by to begin with.
+// SX_OK, or SX_E_INVALID with *err said: more than SX_SELECT_REGEX_MAX_STATES subsets, or more than kSubsetEntries words in their keys.
+template <class Rule>
+inline int subsets(const Front& F, Rule& rule, SubsetDfa* out, std::string* err) {
+    const Nfa& nfa = F.nfa;
+    const uint32_t K = F.K, none = 0xFFFFFFFFu;
+    Closer closer(nfa);
+    std::vector<Closure> after(nfa.n.size());      // behind a byte node: closure(its successor), made when first needed
+    std::vector<uint8_t> after_made(nfa.n.size(), 0), in_again(nfa.n.size(), 0);
+    std::unordered_map<std::vector<uint32_t>, uint32_t, KeyHash> ids;
+    std::vector<std::vector<uint32_t>> keys;
+    std::vector<uint32_t> held;                    // subset -> how many words of its key are byte nodes: the first ones
+    std::vector<uint32_t>& D = out->D, &kinds = out->kinds;
+    uint32_t absorber = none;
+    uint64_t entries = 0;
+    auto state_of = [&](std::vector<uint32_t>&& key, uint64_t here, uint64_t end) -> uint32_t {
+        const uint32_t nodes = (uint32_t)key.size(), id = (uint32_t)keys.size();
+        if (rule.mark(here, end, key)) {
+            if (absorber != none) return absorber;
+            absorber = id;
+            key.clear();
+        } else {
+            auto it = ids.find(key);
+            if (it != ids.end()) return it->second;
+            entries += key.size();
+            ids.emplace(key, id);
+        }
+        held.push_back(absorber == id ? 0 : nodes);
+        kinds.push_back(rule.kind(here, end));
+        out->n_kinds = std::max(out->n_kinds, kinds.back() + 1);
+        keys.push_back(std::move(key));
+        return id;
+    };
+    std::vector<uint32_t> mark(nfa.n.size(), 0);
+    uint32_t mark_stamp = 0;
+    // `to` joined with what is behind the first `count` nodes of `from` that take a byte of class c
+    auto step = [&](const std::vector<uint32_t>& from, size_t count, uint32_t c, Closure* to) {
+        for (size_t k = 0; k < count; k++) {
+            const uint32_t v = from[k];
+            if (!F.sets[nfa.n[v].set].has(F.rep[c])) continue;
+            if (!after_made[v]) { closer.run(nfa.n[v].a, false, &after[v]); after_made[v] = 1; }
+            const Closure& C = after[v];
+            to->here |= C.here; to->end |= C.end;
+            for (uint32_t u : C.chars) if (!in_again[u] && mark[u] != mark_stamp) { mark[u] = mark_stamp; to->chars.push_back(u); }
+        }
+    };
+    Closure again;                                 // the re-entry in front of every later byte: no `^` edge
+    if (Rule::reenter) closer.run(F.start, false, &again);
+    for (uint32_t v : again.chars) in_again[v] = 1;
+    std::vector<Closure> again_to(K);
+    for (uint32_t c = 0; c < K; c++) {
+        again_to[c].here = again.here; again_to[c].end = again.end;
+        mark_stamp++;
+        step(again.chars, again.chars.size(), c, &again_to[c]);
+    }
+    for (int k = 0; k < (Rule::reenter ? 1 : 2); k++) {      // with the `^` edges, then, for the anchored walk, without them
+        Closure c;
+        closer.run(F.start, k == 0, &c);
+        c.chars.erase(std::remove_if(c.chars.begin(), c.chars.end(), [&](uint32_t v) { return in_again[v] != 0; }), c.chars.end());
+        if (!Rule::reenter) c.here = c.end = 0;              // (a match is never empty)
+        out->starts[k] = out->starts[1] = state_of(std::move(c.chars), c.here, c.end);
+    }
+    bool too_many = false;
+    for (uint32_t s = 0; s < keys.size() && !too_many; s++) {
+        D.resize((size_t)(s + 1) * K);
+        if (s == absorber) { for (uint32_t c = 0; c < K; c++) D[(size_t)s * K + c] = s; continue; }
+        const std::vector<uint32_t> key = keys[s];     // (a copy: keys grows)
+        for (uint32_t c = 0; c < K; c++) {
+            Closure to = again_to[c];
+            mark_stamp++;
+            for (uint32_t v : to.chars) mark[v] = mark_stamp;
+            step(key, held[s], c, &to);
+            std::sort(to.chars.begin(), to.chars.end());
+            D[(size_t)s * K + c] = state_of(std::move(to.chars), to.here, to.end);
+            if (keys.size() > SX_SELECT_REGEX_MAX_STATES || entries > kSubsetEntries) { too_many = true; break; }
+        }
+    }
+    if (too_many)
+        return fail(err, keys.size() > SX_SELECT_REGEX_MAX_STATES ? std::string("the patterns need more than SX_SELECT_REGEX_MAX_STATES (65536) states")
+                                                                  : "the subset construction was stopped at the bound on its memory: its " + std::to_string(keys.size()) + " states so far hold more than 33554432 NFA positions in all");
+    out->n = (uint32_t)keys.size();
+    return SX_OK;
+}
+
+// Step 5.  The minimal automaton of a subset construction's DFA, whose states are told apart by their kinds to begin with:
+// Hopcroft's blocks of states that no string tells apart, the quotient, then the byte classes whose columns are equal in every
+// block, numbered by their lowest byte.
+struct Quotient {
+    uint32_t M = 0, K = 0;            // blocks, construction classes
     std::vector<uint32_t> blk;        // state -> block
-    std::vector<Kind> kind;           // block -> its states' kind
+    std::vector<uint32_t> kind;       // block -> its states' kind
     std::vector<uint32_t> Q;          // Q[B * K + c]: block, construction class -> block
     std::vector<uint32_t> first_of;   // final class -> a construction class of it
     uint8_t map[256] = {};            // byte -> final class
 };
-using Quotient = QuotientOf<uint8_t>;
 
-template <class Kind>
-inline void minimise(uint32_t n, uint32_t K, const std::vector<uint32_t>& D, const std::vector<Kind>& kinds, uint32_t n_kinds, const uint8_t* cls, QuotientOf<Kind>* out) {
+inline void minimise(const SubsetDfa& S, const Front& F, Quotient* out) {
+    const uint32_t n = S.n, K = F.K, n_kinds = S.n_kinds;
+    const std::vector<uint32_t>&D = S.D, &kinds = S.kinds;
+    const uint8_t* cls = F.cls;
     std::vector<uint32_t> elems(n), loc(n), blk(n), bbeg, bend, marked;
     {
         std::vector<uint32_t> at(n_kinds + 1, 0);
@@ -514,10 +616,72 @@ inline void minimise(uint32_t n, uint32_t K, const std::vector<uint32_t>& D, con
         for (uint32_t f = 0; f < first_of.size(); f++) by_number[number[f]] = first_of[f];
         first_of = by_number;
     }
-    out->M = M;
+    out->M = M; out->K = K;
     out->blk = std::move(blk);
     out->Q = std::move(Q);
     out->first_of = std::move(first_of);
+}
+
+// Step 6.  The numbering and the rows.  The minimal automaton is unique, its final classes are numbered by their lowest byte and
+// the order is breadth first over them, so a table is a function of the language and the ranks alone.
+
+inline bool absorbing(const Quotient& Qt, uint32_t B) {      // every byte leads back to it
+    for (uint32_t c = 0; c < Qt.K; c++) if (Qt.Q[(size_t)B * Qt.K + c] != B) return false;
+    return true;
+}
+
+// the blocks that the starts reach, the starts first, then breadth first with the final classes in ascending order
+inline std::vector<uint32_t> bfs_order(const Quotient& Qt, const uint32_t* starts) {
+    std::vector<uint32_t> order;
+    std::vector<uint8_t> seen(Qt.M, 0);
+    auto reach = [&](uint32_t B) { if (!seen[B]) { seen[B] = 1; order.push_back(B); } };
+    reach(Qt.blk[starts[0]]); reach(Qt.blk[starts[1]]);
+    for (size_t i = 0; i < order.size(); i++)
+        for (uint32_t c : Qt.first_of) reach(Qt.Q[(size_t)order[i] * Qt.K + c]);
+    return order;
+}
+
+// place[B]: the number of block B — the blocks of rank 0 in their order, then those of rank 1, ... —, first[r]: the first number
+// of rank r (first[n_ranks]: the count).  root_is_zero: order[0] is number 0 whatever its rank, and counts for none.
+struct Numbering { std::vector<uint32_t> place, first; };
+template <class Rank>
+inline Numbering number_by_rank(const Quotient& Qt, const std::vector<uint32_t>& order, uint32_t n_ranks, bool root_is_zero, Rank rank) {
+    Numbering N;
+    N.place.assign(Qt.M, 0);
+    std::vector<uint32_t> ranks(order.size());
+    for (size_t i = 0; i < order.size(); i++) ranks[i] = rank(order[i]);
+    uint32_t number = root_is_zero ? 1 : 0;
+    for (uint32_t r = 0; r < n_ranks; r++) {
+        N.first.push_back(number);
+        for (size_t i = root_is_zero ? 1 : 0; i < order.size(); i++) if (ranks[i] == r) N.place[order[i]] = number++;
+    }
+    N.first.push_back(number);
+    return N;
+}
+
+// what every builder's table has: the counts, the class map, and the rows next[state * classes + class]
+template <class Table>
+inline void write_table(const Quotient& Qt, const std::vector<uint32_t>& order, const std::vector<uint32_t>& place, uint32_t n_patterns, uint32_t flags, Table* T) {
+    const uint32_t classes = (uint32_t)Qt.first_of.size();
+    T->n_patterns = n_patterns; T->nocase = (flags & SX_SELECT_ASCII_NOCASE) ? 1u : 0u;
+    T->states = (uint32_t)order.size(); T->classes = classes;
+    T->lds_states = std::min(T->states, kSelsetLdsBytes / (classes * 2u));
+    memcpy(T->map, Qt.map, sizeof T->map);
+    T->next.assign((size_t)T->states * classes, 0);
+    for (uint32_t B : order)
+        for (uint32_t f = 0; f < classes; f++) T->next[(size_t)place[B] * classes + f] = (uint16_t)place[Qt.Q[(size_t)B * Qt.K + Qt.first_of[f]]];
+}
+
+// A builder's shell: `body` makes the table and answers SX_OK or what refused the patterns; `what`: "regex set", ...
+template <class Body>
+inline int build_table(bool pointers, const char* what, std::string* err, Body body) {
+    if (!pointers) return fail(err, "a NULL pointer");
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        if (err) *err = std::string("no host memory for the ") + what + "'s table";
+        return SX_E_NOMEM;
+    }
 }
 
 }  // namespace refront

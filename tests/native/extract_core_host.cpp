@@ -4,15 +4,13 @@
 // caller may force fewer rows into "LDS" than the builder allows), wavefront after wavefront every lane in front of its string,
 // rounds of one step per active lane until no lane is active, the per-record counts and the wavefront's sums; then the exclusive
 // scan over the wavefronts' counts, pass 2 with the lane's base from the stored per-record counts, and the ordered string gather
-// of sx_result_core.hpp.  It also hands out the tables of both builders as bytes (sx_selre_build.cpp shares the front end).
+// of sx_result_core.hpp.  It also hands out the table as bytes.
 #include <stdint.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 #include <vector>
 #define SXD inline
+#include "guarded_host.hpp"
 #include "../../stringsext_amd/csrc/sx_result_core.hpp"
-#include "../../stringsext_amd/csrc/sx_selre_build.cpp"
 #include "../../stringsext_amd/csrc/sx_extract_build.cpp"
 #include "../../stringsext_amd/csrc/sx_extract_core.hpp"
 
@@ -44,27 +42,16 @@ extern "C" void sxs_extract_info(const void* ex, sx_extract_regex_info* out, uin
     shape[0] = T.end_first; shape[1] = T.here_first; shape[2] = T.dead_first; shape[3] = T.start0; shape[4] = T.start1;
 }
 
-static uint64_t table_bytes(const uint32_t* words, size_t n_words, const uint8_t* map, const std::vector<uint16_t>& next, uint8_t* out, uint64_t cap) {
-    const uint64_t bytes = n_words * 4 + 256 + next.size() * 2;
-    if (bytes > cap) return 0;
-    memcpy(out, words, n_words * 4);
-    memcpy(out + n_words * 4, map, 256);
-    memcpy(out + n_words * 4 + 256, next.data(), next.size() * 2);
-    return bytes;
-}
 // the set's table as bytes: ten words, the class map, the entries; 0 if it does not fit
 extern "C" uint64_t sxs_extract_table(const void* ex, uint8_t* out, uint64_t cap) {
     const sx::ExtractTable& T = ((const HostExtract*)ex)->T;
     const uint32_t words[10] = { T.n_patterns, T.states, T.classes, T.nocase, T.lds_states, T.end_first, T.here_first, T.dead_first, T.start0, T.start1 };
-    return table_bytes(words, 10, T.map, T.next, out, cap);
-}
-// the table selre_build makes of the patterns, the same way; 0 if refused or if it does not fit
-extern "C" uint64_t sxs_selre_table(const sx_pattern* patterns, uint32_t n_patterns, uint32_t flags, uint8_t* out, uint64_t cap) {
-    sx::SelreTable T;
-    std::string err;
-    if (sx::selre_build(patterns, n_patterns, flags, &T, &err) != SX_OK) return 0;
-    const uint32_t words[10] = { T.n_patterns, T.states, T.classes, T.nocase, T.lds_states, T.end_first, T.stop_first, T.matched, T.root_end, T.end_states };
-    return table_bytes(words, 10, T.map, T.next, out, cap);
+    const uint64_t bytes = sizeof words + 256 + T.next.size() * 2;
+    if (bytes > cap) return 0;
+    memcpy(out, words, sizeof words);
+    memcpy(out + sizeof words, T.map, 256);
+    memcpy(out + sizeof words + 256, T.next.data(), T.next.size() * 2);
+    return bytes;
 }
 
 // recs: n records (sx_finding16 if packed), arena: their strings.  counts: n words, the matches per record.  out_recs: room for
@@ -158,13 +145,3 @@ extern "C" int sxs_extract_host(const void* ex, const void* recs, uint64_t n, in
     }
     return 0;
 }
-
-// `bytes` bytes that end where a page without access begins: a read behind the arena faults
-extern "C" void* sxs_guarded(uint64_t bytes, void** region, uint64_t* region_bytes) {
-    const uint64_t page = (uint64_t)sysconf(_SC_PAGESIZE), body = (bytes + page - 1) / page * page;
-    uint8_t* p = (uint8_t*)mmap(nullptr, body + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (p == MAP_FAILED || mprotect(p + body, page, PROT_NONE) != 0) return nullptr;
-    *region = p; *region_bytes = body + page;
-    return p + body - bytes;
-}
-extern "C" void sxs_unmap(void* region, uint64_t region_bytes) { munmap(region, region_bytes); }

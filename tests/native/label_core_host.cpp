@@ -5,14 +5,13 @@
 // per active lane until no lane is active, the labels, the OR over the lanes, per bit of it the ballot into the workgroup's
 // counters, and the flush when the workgroup ends; then, for the selection by label, label_pick_lane per lane, and as
 // selre_core_host.cpp the exclusive scan over the wavefronts' counts, select_place_lane and the ordered string gather of
-// sx_result_core.hpp.
+// sx_result_core.hpp (select_pass2_host.hpp).  It also hands out the table as bytes.
 #include <stdint.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 #include <vector>
 #define SXD inline
-#include "../../stringsext_amd/csrc/sx_result_core.hpp"
+#include "guarded_host.hpp"
+#include "select_pass2_host.hpp"
 #include "../../stringsext_amd/csrc/sx_label_build.cpp"
 #include "../../stringsext_amd/csrc/sx_label_core.hpp"
 
@@ -40,6 +39,19 @@ extern "C" void sxs_label_info(const void* set, sx_label_set_info* out, uint64_t
     const sx::LabelTable& T = ((const HostLabels*)set)->T;
     *out = sx_label_set_info{ T.n_patterns, T.states, T.classes, T.nocase, (uint64_t)(256 + T.next.size() * 2 + T.here.size() * 8 + T.end.size() * 8), T.lds_states, (uint32_t)T.here.size() };
     shape[0] = T.here_first; shape[1] = T.dead; shape[2] = T.root_here; shape[3] = T.all; shape[4] = T.here.size(); shape[5] = T.end.size();
+}
+// the set's table as bytes: LabelTable's seven words, its two masks, the class map, then next, here, end; 0 if it does not fit
+extern "C" uint64_t sxs_label_table(const void* set, uint8_t* out, uint64_t cap) {
+    const sx::LabelTable& T = ((const HostLabels*)set)->T;
+    const uint32_t words[7] = { T.n_patterns, T.states, T.classes, T.nocase, T.lds_states, T.here_first, T.dead };
+    const uint64_t masks[2] = { T.root_here, T.all };
+    const struct { const void* at; uint64_t bytes; } parts[6] = { { words, sizeof words }, { masks, sizeof masks }, { T.map, 256 }, { T.next.data(), T.next.size() * 2 },
+                                                                  { T.here.data(), T.here.size() * 8 }, { T.end.data(), T.end.size() * 8 } };
+    uint64_t bytes = 0;
+    for (const auto& p : parts) bytes += p.bytes;
+    if (bytes > cap) return 0;
+    for (const auto& p : parts) if (p.bytes) { memcpy(out, p.at, p.bytes); out += p.bytes; }
+    return bytes;
 }
 
 constexpr uint32_t kWaves = 8;      // wavefronts per workgroup, as kLabelWaves
@@ -105,7 +117,7 @@ extern "C" int sxs_label_pick_host(const void* recs, uint64_t n, int packed, con
     if (n == 0) return 0;
     const uint64_t waves = (n + sx::kSelectRecs - 1) / sx::kSelectRecs;
     std::vector<uint64_t> wmask(waves + 1), wbytes(waves + 1);
-    std::vector<uint32_t> wcount(waves + 1), wbase(waves + 1);
+    std::vector<uint32_t> wcount(waves + 1);
     sx::SelectParams Q;
     memset(&Q, 0, sizeof Q);
     Q.recs = recs; Q.arena = nullptr; Q.n = n; Q.packed = packed ? 1u : 0u;      // (pass 1 has no arena: it reads no string byte)
@@ -119,44 +131,6 @@ extern "C" int sxs_label_pick_host(const void* recs, uint64_t n, int packed, con
         }
         wmask[w] = mask; wcount[w] = (uint32_t)__builtin_popcountll(mask); wbytes[w] = bytes;
     }
-    uint64_t count = 0, bytes = 0;
-    for (uint64_t w = 0; w <= waves; w++) { wbase[w] = (uint32_t)count; count += wcount[w]; bytes += wbytes[w]; }
-    if (wcount[waves] || wbytes[waves]) return -1;
-    if (masks) memcpy(masks, wmask.data(), (waves + 1) * 8);
-    *n_sel = count; *sel_bytes = bytes;
-    if (bytes > arena_cap) return -2;
     // pass 2 is the list selection's (the pick has filled the same per-wavefront words)
-    std::vector<uint64_t> src(count ? count : 1, 0);
-    Q.arena = arena;
-    Q.wmask = wmask.data(); Q.wbase = wbase.data(); Q.out_recs = out_recs; Q.out_src = src.data();
-    for (uint64_t w = 0; w < waves; w++)
-        for (uint32_t lane = 0; lane < sx::kSelectRecs; lane++) sx::select_place_lane(Q, w, lane);
-    if (count == 0) return 0;
-    std::vector<uint32_t> noff(count + 1);
-    uint64_t sum = 0;
-    for (uint64_t i = 0; i < count; i++) {
-        noff[i] = (uint32_t)sum;
-        sum += packed ? ((const sx_finding16*)out_recs)[i].str_len : ((const sx_finding*)out_recs)[i].str_len;
-    }
-    noff[count] = (uint32_t)sum;
-    if (sum != bytes) return -3;
-    sx::GatherParams G{ out_recs, src.data(), noff.data(), out_arena, count, packed ? 1u : 0u };
-    const uint64_t gwaves = (count + sx::kGatherRecs - 1) / sx::kGatherRecs + 1;
-    for (uint64_t w = 0; w < gwaves; w++) {
-        uint32_t offs[sx::kGatherRecs + 1];
-        uint64_t srcs[sx::kGatherRecs];
-        for (uint32_t lane = 0; lane < sx::kGatherRecs; lane++) sx::gather_load_lane(G, w, lane, offs, srcs);
-        for (uint32_t lane = 0; lane < sx::kGatherRecs; lane++) sx::gather_copy_lane(G, lane, offs, srcs);
-    }
-    return 0;
+    return sxs_select_pass2(recs, n, packed, arena, wmask, wcount, wbytes, out_recs, out_arena, arena_cap, masks, n_sel, sel_bytes);
 }
-
-// `bytes` bytes that end where a page without access begins: a read behind the arena faults
-extern "C" void* sxs_guarded(uint64_t bytes, void** region, uint64_t* region_bytes) {
-    const uint64_t page = (uint64_t)sysconf(_SC_PAGESIZE), body = (bytes + page - 1) / page * page;
-    uint8_t* p = (uint8_t*)mmap(nullptr, body + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (p == MAP_FAILED || mprotect(p + body, page, PROT_NONE) != 0) return nullptr;
-    *region = p; *region_bytes = body + page;
-    return p + body - bytes;
-}
-extern "C" void sxs_unmap(void* region, uint64_t region_bytes) { munmap(region, region_bytes); }

@@ -1,27 +1,14 @@
 // Test-only: what the harnesses of the seen set share (distinct_core_host.cpp for the memory, seen_core_host.cpp, seen_merge_host.cpp):
-// memory that ends where a page without access begins, and ONE set in such memory, which both the result path's and the merge path's
-// lane functions work on.  The exported names are what tests/test_seen_core.py and tests/test_seen_merge_core.py bind.
+// memory that ends where a page without access begins (guarded_host.hpp), and ONE set in such memory, which both the result path's
+// and the merge path's lane functions work on.  The exported names are what tests/test_seen_core.py and tests/test_seen_merge_core.py bind.
 #pragma once
 #include <stdint.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 #ifndef SXD
 #define SXD inline
 #endif
 #include "../../stringsext_amd/csrc/sx_seen_core.hpp"
-
-// `bytes` bytes that end where a page without access begins: a read or a write behind them faults.  *region, *region_bytes: what
-// sxs_unmap takes
-extern "C" void* sxs_guarded(uint64_t bytes, void** region, uint64_t* region_bytes) {
-    const uint64_t page = (uint64_t)sysconf(_SC_PAGESIZE), body = (bytes + page - 1) / page * page;
-    uint8_t* p = (uint8_t*)mmap(nullptr, body + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (p == MAP_FAILED) return nullptr;
-    if (mprotect(p + body, page, PROT_NONE) != 0) { munmap(p, body + page); return nullptr; }
-    *region = p; *region_bytes = body + page;
-    return p + body - bytes;
-}
-extern "C" void sxs_unmap(void* region, uint64_t region_bytes) { munmap(region, region_bytes); }
+#include "guarded_host.hpp"
 
 struct SxsGuarded {
     void* at = nullptr;

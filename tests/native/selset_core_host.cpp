@@ -3,14 +3,13 @@
 // place of their own ("LDS" — the table the core takes for the other states has those rows overwritten, so a look-up on the
 // wrong side shows), wavefront after wavefront every lane in front of its string, rounds of one step per active lane until no
 // lane is active, the ballot, the count and the string bytes; then, as select_core_host.cpp, the exclusive scan over the
-// wavefronts' counts, select_place_lane and the ordered string gather of sx_result_core.hpp.
+// wavefronts' counts, select_place_lane and the ordered string gather of sx_result_core.hpp (select_pass2_host.hpp).
 #include <stdint.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 #include <vector>
 #define SXD inline
-#include "../../stringsext_amd/csrc/sx_result_core.hpp"
+#include "guarded_host.hpp"
+#include "select_pass2_host.hpp"
 #include "../../stringsext_amd/csrc/sx_selset_build.cpp"
 #include "../../stringsext_amd/csrc/sx_selset_core.hpp"
 
@@ -68,7 +67,7 @@ extern "C" int sxs_selset_select_host(const void* set, const void* recs, uint64_
     if (n == 0) return 0;   // (sx_result_select_set_device refuses a segment without findings)
     const uint64_t waves = (n + sx::kSelectRecs - 1) / sx::kSelectRecs;
     std::vector<uint64_t> wmask(waves + 1), wbytes(waves + 1);
-    std::vector<uint32_t> wcount(waves + 1), wbase(waves + 1);
+    std::vector<uint32_t> wcount(waves + 1);
     sx::SelsetParams P;
     memset(&P, 0, sizeof P);
     P.recs = recs; P.arena = arena; P.n = n; P.packed = packed ? 1u : 0u; P.invert = invert ? 1u : 0u;
@@ -79,46 +78,6 @@ extern "C" int sxs_selset_select_host(const void* set, const void* recs, uint64_
         else match_wave<uint32_t>(P, S, w, &wmask[w], &wbytes[w], far_steps);
         wcount[w] = (uint32_t)__builtin_popcountll(wmask[w]);
     }
-    uint64_t count = 0, bytes = 0;
-    for (uint64_t w = 0; w <= waves; w++) { wbase[w] = (uint32_t)count; count += wcount[w]; bytes += wbytes[w]; }
-    if (wcount[waves] || wbytes[waves]) return -1;
-    if (masks) memcpy(masks, wmask.data(), (waves + 1) * 8);
-    *n_sel = count; *sel_bytes = bytes;
-    if (bytes > arena_cap) return -2;
     // pass 2 is the list selection's (the set's kernel has filled the same per-wavefront words)
-    std::vector<uint64_t> src(count ? count : 1, 0);
-    sx::SelectParams Q;
-    memset(&Q, 0, sizeof Q);
-    Q.recs = recs; Q.arena = arena; Q.n = n; Q.packed = P.packed;
-    Q.wmask = wmask.data(); Q.wbase = wbase.data(); Q.out_recs = out_recs; Q.out_src = src.data();
-    for (uint64_t w = 0; w < waves; w++)
-        for (uint32_t lane = 0; lane < sx::kSelectRecs; lane++) sx::select_place_lane(Q, w, lane);
-    if (count == 0) return 0;
-    std::vector<uint32_t> noff(count + 1);
-    uint64_t sum = 0;
-    for (uint64_t i = 0; i < count; i++) {
-        noff[i] = (uint32_t)sum;
-        sum += packed ? ((const sx_finding16*)out_recs)[i].str_len : ((const sx_finding*)out_recs)[i].str_len;
-    }
-    noff[count] = (uint32_t)sum;
-    if (sum != bytes) return -3;
-    sx::GatherParams G{ out_recs, src.data(), noff.data(), out_arena, count, packed ? 1u : 0u };
-    const uint64_t gwaves = (count + sx::kGatherRecs - 1) / sx::kGatherRecs + 1;
-    for (uint64_t w = 0; w < gwaves; w++) {
-        uint32_t offs[sx::kGatherRecs + 1];
-        uint64_t srcs[sx::kGatherRecs];
-        for (uint32_t lane = 0; lane < sx::kGatherRecs; lane++) sx::gather_load_lane(G, w, lane, offs, srcs);
-        for (uint32_t lane = 0; lane < sx::kGatherRecs; lane++) sx::gather_copy_lane(G, lane, offs, srcs);
-    }
-    return 0;
+    return sxs_select_pass2(recs, n, packed, arena, wmask, wcount, wbytes, out_recs, out_arena, arena_cap, masks, n_sel, sel_bytes);
 }
-
-// `bytes` bytes that end where a page without access begins: a read behind the arena faults
-extern "C" void* sxs_guarded(uint64_t bytes, void** region, uint64_t* region_bytes) {
-    const uint64_t page = (uint64_t)sysconf(_SC_PAGESIZE), body = (bytes + page - 1) / page * page;
-    uint8_t* p = (uint8_t*)mmap(nullptr, body + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (p == MAP_FAILED || mprotect(p + body, page, PROT_NONE) != 0) return nullptr;
-    *region = p; *region_bytes = body + page;
-    return p + body - bytes;
-}
-extern "C" void sxs_unmap(void* region, uint64_t region_bytes) { munmap(region, region_bytes); }

@@ -6,10 +6,9 @@
 // active, and the flush of the workgroup's counters at its end.
 #include <stdint.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 #include <vector>
 #define SXD inline
+#include "guarded_host.hpp"
 #include "../../stringsext_amd/csrc/sx_seltally_build.cpp"
 #include "../../stringsext_amd/csrc/sx_seltally_core.hpp"
 
@@ -106,13 +105,3 @@ extern "C" int sxs_seltally_read(const void* set, uint64_t* hits, uint64_t* firs
     }
     return SX_OK;
 }
-
-// `bytes` bytes that end where a page without access begins: a read behind the arena faults
-extern "C" void* sxs_guarded(uint64_t bytes, void** region, uint64_t* region_bytes) {
-    const uint64_t page = (uint64_t)sysconf(_SC_PAGESIZE), body = (bytes + page - 1) / page * page;
-    uint8_t* p = (uint8_t*)mmap(nullptr, body + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (p == MAP_FAILED || mprotect(p + body, page, PROT_NONE) != 0) return nullptr;
-    *region = p; *region_bytes = body + page;
-    return p + body - bytes;
-}
-extern "C" void sxs_unmap(void* region, uint64_t region_bytes) { munmap(region, region_bytes); }

@@ -18,15 +18,14 @@ import pytest
 
 import stringsext_amd as sx
 from test_select_core import lay_out, records, text
-from test_selre_core import DEEP, REFUSED, Tree, to_python
+from test_selre_core import DEEP, PINNED_SETS, REFUSED, Tree, to_python
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE = os.path.join(ROOT, "tests", "native")
 CSRC = os.path.join(ROOT, "stringsext_amd", "csrc")
 NOCASE = sx.SX_SELECT_ASCII_NOCASE
-DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h")] + [os.path.join(CSRC, f) for f in (
-    "sx_extract_build.cpp", "sx_extract_build.hpp", "sx_extract_core.hpp", "sx_selre_front.hpp", "sx_selre_build.cpp", "sx_selre_build.hpp",
-    "sx_selset_build.hpp", "sx_select_core.hpp", "sx_result_core.hpp")]
+DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h"), os.path.join(NATIVE, "guarded_host.hpp")] + [os.path.join(CSRC, f) for f in (
+    "sx_extract_build.cpp", "sx_extract_build.hpp", "sx_extract_core.hpp", "sx_selre_front.hpp", "sx_selset_build.hpp", "sx_select_core.hpp", "sx_result_core.hpp")]
 
 
 def built(out, src, flags):
@@ -48,7 +47,6 @@ def core():
     L.sxs_extract_free.restype, L.sxs_extract_free.argtypes = None, [C.c_void_p]
     L.sxs_extract_info.restype, L.sxs_extract_info.argtypes = None, [C.c_void_p, C.POINTER(sx.ExtractRegexInfo), u32p]
     L.sxs_extract_table.restype, L.sxs_extract_table.argtypes = C.c_uint64, [C.c_void_p, C.c_void_p, C.c_uint64]
-    L.sxs_selre_table.restype, L.sxs_selre_table.argtypes = C.c_uint64, [C.POINTER(sx.Pattern), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]
     L.sxs_extract_host.restype = C.c_int
     L.sxs_extract_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, u32p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                    u64p, u64p, u64p, u64p]
@@ -452,32 +450,33 @@ def test_every_refused_form_and_limit_is_the_regex_sets_with_the_same_text(core)
             assert rc == sx.SX_OK and time.perf_counter() - t0 < 1.0, (p[:20], err)
 
 
-# sha256 of sxs_selre_table's bytes — ten words of SelreTable, the class map, the entries — as the harness of the commit before the
-# front end moved into sx_selre_front.hpp gave them: selre_build's output has not changed by a bit
-SELRE_PINNED = [
-    ([b"abc"], 0, "e6b65c91f276f8dd92a28192f6bcee2737989f8e7c1784f5fc80fdd1b549d95c"),
-    ([b"^abc$"], 0, "b3833de49b6d8f4bc8dda30e36da698b346ca39b1c5c39cd9891ea0ad5474c19"),
-    ([b"a*"], 0, "e4b60262073c764435e3ca95d0b86ae886493b46949c78fa49456b821f751159"),
-    ([b"colou?r", b"gr[ae]y$"], NOCASE, "10cca68cd7cfb89b56be4d5e8b52d7a412acd023100da874d5e7e772ba40a908"),
-    ([rb"https?://[^\s/]+(/\S*)?", rb"[\w.+-]+@[\w-]+(\.[\w-]+)+", rb"(\d{1,3}\.){3}\d{1,3}"], 0, "a9ae5668225d5a13ddcbeb54f9619b5d9646b728458580c2b1290d6aa5d8925b"),
-    ([b"^[ab]*a[ab]{9}$"], 0, "9db6c4a75880c20e8beb93715326353c7277a02bb9313168f9b44b7396d05caf"),
-    ([b"(^a|b)c", b"a$|b", b"x{2,5}y?"], 0, "b9927323b63b40889c1d7fff977a37092ee93e46f8a865cc04bb8b6002211671"),
-    ([b"|".join(b"w%03d" % k for k in range(0, 300, 7)), rb"[^\x00-\x7f]{2,4}"], NOCASE, "ee8ec0484ca25f32d857e6fb948d28dd63b422054020b1ff4c869ac99e0b20fa"),
-    ([b"(?:a{2,}){2,}b|^$"], 0, "1be0b569cddd33d9c6e6fca74462441f3a0b20b14ebca7bc12c5b9e15439a6f8"),
+# sha256 of sxs_extract_table's bytes — ten words of ExtractTable, the class map, the entries — of test_selre_core.PINNED_SETS, in
+# its order, as commit 046f17a gave them, the last one in which extract_build had a subset construction, a numbering and a row
+# writer of its own: its output has not changed by a bit
+EXTRACT_PINNED = [
+    "a2c7a946d01ab59951395ac3650cdbd16b31a7602b51cba2eece0d6c7478c103", "998c78a2e52bb590b0bb2406938e4422e66b35de18adbee2dc0dfa846bb038b6",
+    "84803aa2d76f083d603b3de893bc5e4ad2024dd2594a518efdb8c49cfca7aab3", "1080ef1262d92abd94671de15ef363667e5d1fc826c6270c9a6c1068aaa2b764",
+    "4284f52226c0028295a954bead6282f1dc0847e1db85bf66d6576679b2f9dd28", "fce2b6e726ae66015be8a810a503e2e311d3a0c6073bb9d4b1487fd92f26b59f",
+    "5098b76a0dbf99ec310084b55824e487d11ad095b91c54853216f5b233a58f56", "131a16aa129fe3f4c3ba36d19be850632c9c45aa5b051cee7bde2c1686418f74",
+    "d1d2a9225228288c55f4251f57cfc932b0506bac7ef1b8baa6ea4884b15ac4bb", "e4b60262073c764435e3ca95d0b86ae886493b46949c78fa49456b821f751159",
+    "e4b60262073c764435e3ca95d0b86ae886493b46949c78fa49456b821f751159", "201ce1a9fa3930b0e75486ad3a5856c34f175363c1a5b1996fa280d863f275f3",
+    "64587c2551a5aaea32e0154a596df51c0bec5bcb495bf8be5ef3cee8162bffe7", "be22078bb6ddc962e1bec352188d4b421c876076922e139e79b2b4c8b2e928e6",
+    "c9ad4493767e3bf0dba37cfca9a7ac92ef5c19a606f8c88aaf3c2c9f8c610aa5", "af3109e5c6bb91dea650b2374b282b497b04b45b74cd2d20f4c5318d3d86dcfb",
+    "efc363fde00caff2c6347c829cdec6631a68535fbecca69a8f5f2715a1d5bb23",
 ]
 
 
-def selre_digest(L, pats, flags):
-    arr = (sx.Pattern * len(pats))(*[sx.Pattern(p, len(p)) for p in pats])
-    buf = C.create_string_buffer(1 << 22)
-    n = L.sxs_selre_table(arr, len(pats), flags, buf, len(buf))
-    assert n
-    return hashlib.sha256(buf.raw[:n]).hexdigest()
-
-
-def test_the_regex_sets_tables_are_unchanged(core):
-    for pats, flags, digest in SELRE_PINNED:
-        assert selre_digest(core, pats, flags) == digest, pats
+def test_the_extract_sets_tables_are_unchanged(core):
+    assert len(EXTRACT_PINNED) == len(PINNED_SETS)
+    shapes = set()
+    for (pats, flags), digest in zip(PINNED_SETS, EXTRACT_PINNED):
+        hx = HostExtract(core, pats, flags == NOCASE)
+        assert hashlib.sha256(hx.table()).hexdigest() == digest, pats
+        f = hx.info
+        shapes.add((f["start0"] == f["start1"], f["dead_first"] < f["states"], f["end_first"] < f["here_first"], f["here_first"] < f["dead_first"]))
+        hx.free()
+    # every branch of the numbering is among them: one start and two, with and without `dead`, end states, here states
+    assert all({True, False} <= {s[k] for s in shapes} for k in range(4)), shapes
 
 
 # ---- 5. the quadratic case, loosely

@@ -7,6 +7,7 @@ Python's re.search PER PATTERN over the strings — every pattern rendered for P
 re.IGNORECASE.  No expected value comes from the code under test.  The source arena ends where a page without access begins: the
 core may read nothing behind the last string, not even to decide `$`."""
 import ctypes as C
+import hashlib
 import os
 import random
 import re
@@ -17,7 +18,7 @@ import pytest
 import stringsext_amd as sx
 import test_selre_core as tsc
 from test_select_core import fields, lay_out, records, text
-from test_selre_core import DEEP, REFUSED, Tree, to_python
+from test_selre_core import DEEP, PINNED_SETS, REFUSED, Tree, to_python
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE = os.path.join(ROOT, "tests", "native")
@@ -25,7 +26,7 @@ CSRC = os.path.join(ROOT, "stringsext_amd", "csrc")
 NOCASE = sx.SX_SELECT_ASCII_NOCASE
 NEVER = sx.SX_LABEL_NEVER
 NONE = 0xFFFFFFFF          # kLabelNone: `dead` where no state is
-DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h")] + [os.path.join(CSRC, f) for f in (
+DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h"), os.path.join(NATIVE, "guarded_host.hpp"), os.path.join(NATIVE, "select_pass2_host.hpp")] + [os.path.join(CSRC, f) for f in (
     "sx_label_build.cpp", "sx_label_build.hpp", "sx_label_core.hpp", "sx_selre_front.hpp", "sx_selset_build.hpp", "sx_select_core.hpp",
     "sx_seltally_core.hpp", "sx_result_core.hpp")]
 
@@ -48,6 +49,7 @@ def core():
     L.sxs_label_create.argtypes = [C.POINTER(sx.Pattern), C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.c_char_p, C.c_uint32]
     L.sxs_label_free.restype, L.sxs_label_free.argtypes = None, [C.c_void_p]
     L.sxs_label_info.restype, L.sxs_label_info.argtypes = None, [C.c_void_p, C.POINTER(sx.LabelSetInfo), u64p]
+    L.sxs_label_table.restype, L.sxs_label_table.argtypes = C.c_uint64, [C.c_void_p, C.c_void_p, C.c_uint64]
     L.sxs_label_host.restype = C.c_int
     L.sxs_label_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u64p, u64p, u64p]
     L.sxs_label_pick_host.restype = C.c_int
@@ -247,6 +249,42 @@ def test_a_label_set_meets_the_state_limit_sooner_than_a_regex_set(core, selre):
     selre.sxs_selre_free(h)
     rc, err = create_rc(core, pats)
     assert rc == sx.SX_E_INVALID and err == "the patterns need more than SX_SELECT_REGEX_MAX_STATES (65536) states"
+
+
+# sha256 of sxs_label_table's bytes — LabelTable's seven words and two masks, the class map, then next, here and end — of
+# test_selre_core.PINNED_SETS, in its order, as commit 046f17a gave them, the last one in which label_build had a subset construction,
+# a numbering and a row writer of its own: its output has not changed by a bit
+LABEL_PINNED = [
+    "843e8070bd2a1c40f17162d81702a39387431604fb9f5b00bb2ec046ff92b7b1", "98c492ea8b412e2d9c1fd509caa1a40fd0a98f9f6273aac1a5855088ed61830a",
+    "b20fcefad92041b14210e439436e1a38b5241d4767eb67eaaee385a406beec9a", "49d26f4639f9717ca2e03798354cb9ac6e837c517d7dc147149d371363cb7569",
+    "3abba6a11f856b9e68458a2dcdeaff1aa8415e5764f255addc2476d0bdfbd048", "fd82138b83f1d8570f957db8c89acdad11ad4694b610df73288087905f200334",
+    "67a09ac27e79ef4d6f2d951f2e5990618bd68b6c5e56fe47444ebd2e88807793", "178da0314ce9bf6299d78303974c9b76d662d043cf631634a5429ee4e6f90d10",
+    "139ca1494b714f45aa7e06999fce1afe0dc2288956f410ba68fafe7db1d838fa", "a021fba1ed861323b26a5ee1fff2ba1d199b6f646956b70e4c3cdf2200304e86",
+    "002ac128e1e302ed3f30eb9c0af8b78a04442e03edbf71bb7e450a24c2f9c92b", "4a9f282687211f4a3392752e159a8dd45c550afee373d39bcc507ad6c236b5c6",
+    "a392f2f825ea9e0305eec6efb1f89e00401b1ba8f46bdc12f8d4fa7aa50878c9", "49df8df0fc0d22a52e0e6e512ca78e8e4c53a0aec12122ce64064718dc9c978f",
+    "e2e96e4abc15852616373fd4ae38544509b1da0b9cf46fc5ee2c905bf875b000", "c2df9bdfe0bd7a0baa06d8f140cb585510c7bc20538fc3a01cc864224d2a379a",
+    "2203674b158f6fd8ad1f4703373bb5a55a4ad6a39edb92f3ed7b8380fb2b5734",
+]
+
+
+def test_the_label_sets_tables_are_unchanged(core):
+    assert len(LABEL_PINNED) == len(PINNED_SETS)
+    shapes, most_pairs = set(), 0
+    for (pats, flags), digest in zip(PINNED_SETS, LABEL_PINNED):
+        hs = HostLabels(core, pats, flags == NOCASE)
+        f = hs.info
+        buf = C.create_string_buffer(28 + 16 + f["table_bytes"])
+        assert core.sxs_label_table(hs.h, buf, len(buf)) == len(buf) and core.sxs_label_table(hs.h, buf, len(buf) - 1) == 0
+        assert hashlib.sha256(buf.raw).hexdigest() == digest, pats
+        words = [int.from_bytes(buf.raw[k:k + 8], "little") for k in range(28 + 16 + 256 + f["states"] * f["classes"] * 2, len(buf), 8)]
+        here, end = [0] * f["here_first"] + words[:f["here_states"]], words[f["here_states"]:]
+        most_pairs = max(most_pairs, len(set(zip(here, end))))
+        shapes.add((f["states"] == 1, f["dead"] != NONE, f["here_states"] > (f["dead"] != NONE), f["root_here"] != 0, f["all"] == 2 ** 64 - 1))
+        hs.free()
+    # every branch of the numbering is among them: `dead` as the only state, as the last one and not at all, states with here != 0, a
+    # root with a `here` of its own, 64 patterns; and more pairs of masks than a byte could number
+    assert (True, True) in {s[:2] for s in shapes} and all({True, False} <= {s[k] for s in shapes if not s[0]} for k in (1, 2, 3, 4)), shapes
+    assert most_pairs > 256, most_pairs
 
 
 # ---- 2. hand-written cases

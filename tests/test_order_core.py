@@ -22,7 +22,7 @@ from test_select_core import lay_out, records, text
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE = os.path.join(ROOT, "tests", "native")
 CSRC = os.path.join(ROOT, "stringsext_amd", "csrc")
-DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h"), os.path.join(NATIVE, "seen_set_host.hpp"), os.path.join(NATIVE, "order_core_host.cpp")] + [
+DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h"), os.path.join(NATIVE, "seen_set_host.hpp"), os.path.join(NATIVE, "guarded_host.hpp"), os.path.join(NATIVE, "order_core_host.cpp")] + [
     os.path.join(CSRC, f) for f in ("sx_order_core.hpp", "sx_label_core.hpp", "sx_seen_core.hpp", "sx_distinct_core.hpp", "sx_select_core.hpp", "sx_seltally_core.hpp")]
 STRING, FIELD, DESC, NOCASE = sx.SX_ORDER_BY_STRING, sx.SX_ORDER_BY_LABEL_FIELD, sx.SX_ORDER_DESCENDING, sx.SX_ORDER_NOCASE
 POS0 = {m: 4096 * (m + 1) for m in range(5)}        # a packed segment's position0 by mission_id (records(): mission_id = i % 5)

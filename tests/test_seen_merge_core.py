@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE = os.path.join(ROOT, "tests", "native")
 CSRC = os.path.join(ROOT, "stringsext_amd", "csrc")
 DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h")] + [os.path.join(NATIVE, f) for f in (
-    "seen_core_host.cpp", "distinct_core_host.cpp", "seen_set_host.hpp")] + [os.path.join(CSRC, f) for f in (
+    "seen_core_host.cpp", "distinct_core_host.cpp", "seen_set_host.hpp", "guarded_host.hpp")] + [os.path.join(CSRC, f) for f in (
     "sx_seen_merge_core.hpp", "sx_seen_core.hpp", "sx_distinct_core.hpp", "sx_select_core.hpp", "sx_seltally_core.hpp")]
 EMPTY = (1 << 64) - 1             # kSeenEmpty
 OFFSET_BITS = 40                  # kSeenOffsetBits

@@ -21,7 +21,7 @@ NOCASE, INVERT = sx.SX_SELECT_ASCII_NOCASE, sx.SX_SELECT_INVERT
 def build_select_core():
     """(as tests/native/build_harness.py builds the other cores: g++ on one file, rebuilt when a source is newer)"""
     so, src = os.path.join(NATIVE, "libselect_core_host.so"), os.path.join(NATIVE, "select_core_host.cpp")
-    deps = [src, os.path.join(CSRC, "sx_select_core.hpp"), os.path.join(CSRC, "sx_result_core.hpp"), os.path.join(ROOT, "include", "stringsext_amd.h")]
+    deps = [src, os.path.join(NATIVE, "guarded_host.hpp"), os.path.join(NATIVE, "select_pass2_host.hpp"), os.path.join(CSRC, "sx_select_core.hpp"), os.path.join(CSRC, "sx_result_core.hpp"), os.path.join(ROOT, "include", "stringsext_amd.h")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
         tmp = f"{so}.{os.getpid()}.tmp"
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", tmp, src])

@@ -6,6 +6,7 @@ Python's re.search over the strings — every pattern rendered for Python with `
 expected value never comes from the code under test.  The source arena ends where a page without access begins: the core may
 read nothing behind the last string, not even to decide `$`."""
 import ctypes as C
+import hashlib
 import os
 import random
 import re
@@ -20,8 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE = os.path.join(ROOT, "tests", "native")
 CSRC = os.path.join(ROOT, "stringsext_amd", "csrc")
 NOCASE = sx.SX_SELECT_ASCII_NOCASE
-DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h")] + [os.path.join(CSRC, f) for f in (
-    "sx_selre_build.cpp", "sx_selre_build.hpp", "sx_selre_core.hpp", "sx_selset_build.hpp", "sx_select_core.hpp", "sx_result_core.hpp")]
+DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h"), os.path.join(NATIVE, "guarded_host.hpp"), os.path.join(NATIVE, "select_pass2_host.hpp")] + [os.path.join(CSRC, f) for f in (
+    "sx_selre_build.cpp", "sx_selre_build.hpp", "sx_selre_front.hpp", "sx_selre_core.hpp", "sx_selset_build.hpp", "sx_select_core.hpp", "sx_result_core.hpp")]
 
 
 def built(out, src, flags):
@@ -43,6 +44,7 @@ def core():
     L.sxs_selre_free.restype, L.sxs_selre_free.argtypes = None, [C.c_void_p]
     L.sxs_selre_info.restype = None
     L.sxs_selre_info.argtypes = [C.c_void_p, C.POINTER(sx.SelectRegexInfo), C.POINTER(C.c_uint32)]
+    L.sxs_selre_table.restype, L.sxs_selre_table.argtypes = C.c_uint64, [C.POINTER(sx.Pattern), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]
     L.sxs_selre_select_host.restype = C.c_int
     L.sxs_selre_select_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.c_uint64, u64p, u64p, u64p, u64p, u64p]
@@ -580,6 +582,50 @@ def test_equivalent_patterns_give_the_same_automaton(core):
     hr = HostRegex(core, [b"^abc"])
     assert hr.info["states"] == 5 and hr.info["stop_first"] == 3          # root, a, ab, dead, matched
     hr.free()
+
+
+# sha256 of sxs_selre_table's bytes — ten words of SelreTable, the class map, the entries.  The first nine as the harness of the
+# commit before the front end moved into sx_selre_front.hpp gave them, the others as commit 046f17a gave them, the last one in
+# which each builder had a subset construction, a numbering and a row writer of its own: selre_build's output has not changed by a
+# bit.  tests/test_extract_core.py and tests/test_label_core.py pin their builders' tables of the same lists (PINNED_SETS).  Behind
+# the nine, one list per branch of a numbering that they leave out: a root that is `dead` and the only state; a root that accepts
+# at the end; two starts that differ; 64 patterns; a root with a `here` of its own; 512 pairs of masks (pattern k matches where
+# the k-th byte back is an a); a `dead` that is not the root next to states with here != 0; an anchored walk that never dies.
+SELRE_PINNED = [
+    ([b"abc"], 0, "e6b65c91f276f8dd92a28192f6bcee2737989f8e7c1784f5fc80fdd1b549d95c"),
+    ([b"^abc$"], 0, "b3833de49b6d8f4bc8dda30e36da698b346ca39b1c5c39cd9891ea0ad5474c19"),
+    ([b"a*"], 0, "e4b60262073c764435e3ca95d0b86ae886493b46949c78fa49456b821f751159"),
+    ([b"colou?r", b"gr[ae]y$"], NOCASE, "10cca68cd7cfb89b56be4d5e8b52d7a412acd023100da874d5e7e772ba40a908"),
+    ([rb"https?://[^\s/]+(/\S*)?", rb"[\w.+-]+@[\w-]+(\.[\w-]+)+", rb"(\d{1,3}\.){3}\d{1,3}"], 0, "a9ae5668225d5a13ddcbeb54f9619b5d9646b728458580c2b1290d6aa5d8925b"),
+    ([b"^[ab]*a[ab]{9}$"], 0, "9db6c4a75880c20e8beb93715326353c7277a02bb9313168f9b44b7396d05caf"),
+    ([b"(^a|b)c", b"a$|b", b"x{2,5}y?"], 0, "b9927323b63b40889c1d7fff977a37092ee93e46f8a865cc04bb8b6002211671"),
+    ([b"|".join(b"w%03d" % k for k in range(0, 300, 7)), rb"[^\x00-\x7f]{2,4}"], NOCASE, "ee8ec0484ca25f32d857e6fb948d28dd63b422054020b1ff4c869ac99e0b20fa"),
+    ([b"(?:a{2,}){2,}b|^$"], 0, "1be0b569cddd33d9c6e6fca74462441f3a0b20b14ebca7bc12c5b9e15439a6f8"),
+    ([b"a^b"], 0, "8bf16db43512c567f2ab7c6eb02b5cffb82423018a0dd21107b33ef9adae7fda"),
+    ([b"^$"], 0, "7c97c89da018550ff9cab6f036ed78f596e12d23316cdf73fba9cabf3080893a"),
+    ([b"^a|b"], 0, "22ef564b907025770706e9b8265998b89bc130688aa1744f6a3d93e86e89e84d"),
+    ([b"k%02d;" % p for p in range(63)] + [b"^z+$"], 0, "1c7eb42390e81f581ab9749a953d0dcd2aa0a9021254fcde9de9f84f2deb56f4"),
+    ([b"a*", b"b"], 0, "608e1f26fc68c92b7f4d3cfe758eb489aad28d3c9ee68b408260f25627ee6a60"),
+    ([b"a[ab]{%d}" % k for k in range(1, 10)], 0, "b8d94a8a57217c119757ec7cb537b918679c378615daf5ea85f7be4518d888d0"),
+    ([b"^abc", b"^abd$"], 0, "a0befb8e89d9ee6052911c2f0e5af156f16ccdce02113e015048e3e53203db3a"),
+    ([rb"[\x00-\xff]+"], 0, "266667dbafae5b1a1b5291a75b3a9ad5f5d3c8117b57d05d75b5604d7e8a9d85"),
+]
+PINNED_SETS = [(pats, flags) for pats, flags, _ in SELRE_PINNED]
+
+
+def test_the_regex_sets_tables_are_unchanged(core):
+    shapes = set()
+    for pats, flags, digest in SELRE_PINNED:
+        arr = (sx.Pattern * len(pats))(*[sx.Pattern(p, len(p)) for p in pats])
+        buf = C.create_string_buffer(1 << 22)
+        n = core.sxs_selre_table(arr, len(pats), flags, buf, len(buf))
+        assert n
+        assert hashlib.sha256(buf.raw[:n]).hexdigest() == digest, pats
+        states, end_first, stop_first, matched, root_end = (int.from_bytes(buf.raw[4 * k:4 * k + 4], "little") for k in (1, 5, 6, 7, 8))
+        shapes.add((states == 1, matched == 0xFFFFFFFF, stop_first + (matched != 0xFFFFFFFF) < states, bool(root_end), end_first < stop_first))
+    # every branch of the numbering is among them: the only state `matched` or `dead`, with and without `matched`, `dead`, root_end,
+    # end-accepting states
+    assert {(True, False), (True, True)} <= {s[:2] for s in shapes} and all({True, False} <= {s[k] for s in shapes if not s[0]} for k in (1, 2, 3, 4)), shapes
 
 
 # ---- 5. limits and refusals

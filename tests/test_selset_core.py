@@ -24,7 +24,7 @@ NOCASE = sx.SX_SELECT_ASCII_NOCASE
 def build_selset_core():
     """(as tests/test_select_core.py builds its harness: g++ on one file, rebuilt when a source is newer)"""
     so, src = os.path.join(NATIVE, "libselset_core_host.so"), os.path.join(NATIVE, "selset_core_host.cpp")
-    deps = [src, os.path.join(ROOT, "include", "stringsext_amd.h")] + [os.path.join(CSRC, f) for f in (
+    deps = [src, os.path.join(NATIVE, "guarded_host.hpp"), os.path.join(NATIVE, "select_pass2_host.hpp"), os.path.join(ROOT, "include", "stringsext_amd.h")] + [os.path.join(CSRC, f) for f in (
         "sx_selset_build.cpp", "sx_selset_build.hpp", "sx_keyword_front.hpp", "sx_selset_core.hpp", "sx_select_core.hpp", "sx_result_core.hpp")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
         tmp = f"{so}.{os.getpid()}.tmp"

@@ -20,7 +20,7 @@ NATIVE = os.path.join(ROOT, "tests", "native")
 CSRC = os.path.join(ROOT, "stringsext_amd", "csrc")
 NOCASE = sx.SX_SELECT_ASCII_NOCASE
 NEVER = sx.SX_TALLY_NEVER
-DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h")] + [os.path.join(CSRC, f) for f in (
+DEPS = [os.path.join(ROOT, "include", "stringsext_amd.h"), os.path.join(NATIVE, "guarded_host.hpp")] + [os.path.join(CSRC, f) for f in (
     "sx_seltally_build.cpp", "sx_seltally_build.hpp", "sx_keyword_front.hpp", "sx_seltally_core.hpp", "sx_select_core.hpp")]
 LDS_ROW_BYTES, LDS_IDS = 32 * 1024, 4096      # seltally_kernel's LDS: rows and counters (sx_seltally_build.hpp)
 

@@ -158,10 +158,10 @@ def lines():
     return list(out)
 
 
-def fitted(ls, q):
+def fitted(ls, q, at=0):
     """the reference decodes a window of 4096 bytes in slices of 2 q bytes, and a line of multi-byte characters that begins in the last three bytes of a slice
-    or at its first is cut behind its first slice: a short filler line moves such a line on"""
-    out, at = [], 0
+    or at its first is cut behind its first slice: a short filler line moves such a line on.  at: where in the buffer the lines begin"""
+    out = []
     for k, x in enumerate(ls):
         if len(x) > q and at % 4096 % (2 * q) in (2 * q - 3, 2 * q - 2, 2 * q - 1, 0):
             out.append(b"fill %d" % (k % 10))

@@ -13,7 +13,10 @@ longer one (measure_wide_kernel, from the list the narrow kernel leaves).  The e
                     lines of 254, 255, 256 and 257 bytes; 600 x `7` — a count above 255, entropy 0 —; a wide line of every printable
                     value; wide records at the first and the last place of a wavefront; more than 64 wide records in a row (the list's
                     reserve); a segment without a wide string and one of nothing else; a narrow string of `q` directly behind a wide
-                    one of nothing else (counters left behind would show); `limit` (long_plant.limit_ms()): 16 000 and 64 000 bytes
+                    one of nothing else — the two kernels count in counters of their own, so this shows no counter left behind: it
+                    pins the narrow lane's word beside a wide neighbour; a lane's own clearing is `trip`'s, and the wide wavefront's,
+                    which needs a wavefront that measures a second string, is tests/test_gpu_measure_edges.py's —; `limit`
+                    (long_plant.limit_ms()): 16 000 and 64 000 bytes
     UTF-8           fold_plant's lines in every source of the first kind; `cuts`: an extraction that cuts characters in two, as
                     tests/test_gpu_fold_edges.py makes it — chars counts the lead byte only
 

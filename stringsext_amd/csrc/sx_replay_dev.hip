@@ -276,7 +276,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SX_REPLAY_WA
     replay_region<1, EQ & 7, false, (EQ >= 8)>(P, i, o, findings + fp, arena + ap, ap + P.str_off_base);
 }
 
-// The cached outputs go into place: G lanes per region (4, 16 or 64, by the average output size), 64 / G regions of a wave
+// The cached outputs go into place: G lanes per region (4, 32 or 64, by the average output size), 64 / G regions of a wave
 // at a time — coalesced within a region (a lane of its own would copy byte by byte into 64 different lines per
 // instruction), and no decoder in the kernel, so that many waves are resident.  A finding is two uint4 (str_off at offset 8
 // of the first); the strings go as dwords aligned to the DESTINATION, each built from two source dwords, the up to three

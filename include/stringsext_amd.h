@@ -1101,6 +1101,74 @@ typedef struct sx_measure_info { uint64_t findings, bytes, chars, wide, ascii; }
 int  sx_result_measure_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_labels** out, sx_measure_info* info /* may be NULL */);
 int  sx_measure_bytes(const uint8_t* s, uint64_t len, uint32_t flags, uint64_t* word);
 
+/* The APPROXIMATE MATCHES of a result whose segments ALL lie in HBM: for every finding, WHICH keywords of a list occur in its string
+ * with at most k errors — `agrep` / `tre-agrep` behind `strings`: a flipped byte, a dropped character, `passw0rd` —, as one 64-bit
+ * word, made where the findings lie (csrc/sx_fuzzy_dev.hip) with no string byte crossing PCIe.  The word is a label: everything that
+ * takes the labels of sx_result_label_device takes these.
+ * THE RULE.  A FUZZY SET holds 1..SX_FUZZY_MAX_PATTERNS patterns.  Pattern p owns bit p, has a byte string of
+ * 1..SX_FUZZY_MAX_PATTERN_BYTES bytes, and has its own error budget k_p with 0 <= k_p <= SX_FUZZY_MAX_ERRORS and k_p < len_p.
+ * Bit p of finding i's word is set iff some substring of the finding's string has Levenshtein distance at most k_p from pattern p.
+ * The string is the UTF-8 the result holds, arena[str_off, str_off + str_len).
+ *   - A substring is any contiguous byte range, the empty one included.
+ *   - Insertion, deletion and substitution of one BYTE each cost 1.
+ *   - This is Sellers' table: row 0 all zeros, D[i][j] = min(D[i-1][j-1] + (P[i] != T[j]), D[i-1][j] + 1, D[i][j-1] + 1).  The bit is
+ *     set iff min_j D[m][j] <= k.
+ *   - k_p < len_p makes the empty substring never a match, so an empty string's word is 0.
+ *   - With SX_SELECT_ASCII_NOCASE, 'A'..'Z' and 'a'..'z' compare equal in both pattern and string.  No other byte is folded.
+ *   - Distances are in bytes, not characters.  One wrong Cyrillic letter costs up to 2.
+ *   - Bits of patterns the set lacks are 0.
+ *   - A match never spans two findings.
+ *   - k = 0 is exactly the substring selection.
+ * sx_fuzzy_set_create builds, on the host (csrc/sx_fuzzy_build.hpp), a byte-class map and one 64-bit mask per class and pattern — bit
+ * i: byte i of the pattern is of that class — and puts them into HBM on the context's device, with len_p and k_p per pattern
+ * (max_errors[p] = k_p) and two counters per pattern.  flags: 0 or SX_SELECT_ASCII_NOCASE, compiled into the set.  SX_E_INVALID, with
+ * a text in sx_last_error that names the pattern's index where one is at fault: an empty pattern, more than 64 bytes, k > 8, k >= len,
+ * n_patterns outside 1..64, unknown flags, a NULL pointer.  SX_E_STATE: a host-only context.  *out = NULL on every error.  The set
+ * owns its device memory, masks and counters, and does not depend on the context's lifetime: it may be freed before or after
+ * sx_destroy, and used with any context on the same HIP device (another device: SX_E_INVALID).
+ * sx_fuzzy_set_info_get: what was built — classes: class 0, "no pattern holds this byte", and one per distinct byte value of the
+ * patterns (after the case union), ordered by how many pattern positions hold them; the masks of the first lds_classes classes are
+ * what the kernel keeps in LDS, the rarest it reads through L2, so no set is refused for its size; table_bytes in HBM (everything
+ * but the counters); max_len and max_errors over the patterns.
+ * THE WALK is Myers' bit-vector form of Sellers' table (a column of the table as two bit vectors and the score of its last row), a
+ * lane per string, the same work per byte whatever k is; a lane takes the set's patterns in groups and walks its string once per
+ * group, and leaves a group when all its bits are set.  str_len < len_p - k_p cannot match and is not walked.
+ * THE COUNTERS, per pattern, are the label set's: findings[p] = the number of findings with bit p; first[p] = the smallest
+ * (ordinal_base + index of the finding in the result's print order) among them, or SX_LABEL_NEVER if there is none.  A new set is
+ * reset.  sx_result_fuzzy_device ADDS to them, so a stream scanned buffer by buffer gives one count of the whole stream if the caller
+ * passes the number of findings of the buffers before as ordinal_base; sums and minima: they are deterministic.
+ * sx_result_fuzzy_device makes *out, the words of r's findings (sx_labels_free), under sx_result_label_device's contract, word for
+ * word: the sources are exactly what sx_print_findings_device accepts — both record types, any layout of the strings, the result of
+ * any selection, extraction, order or fold —, and SX_E_STATE comes back wherever that function would refuse the source, decided for ALL
+ * segments before anything is launched; one array of words per source segment, bound to r, which sx_result_select_labels_device,
+ * sx_result_select_labels_range_device, sx_result_order_device and sx_labels_rebind take unchanged; the source is read, never moved;
+ * the call is no selection and ages none; it returns when the kernels are done.  SX_E_INVALID: a NULL pointer, a set on another
+ * device.  SX_E_NOMEM: the words cannot be allocated; nothing is counted then.  *out is NULL on every error.
+ * sx_fuzzy_set_reset, sx_fuzzy_set_read, sx_fuzzy_set_counters_device: as the label set's.
+ * sx_fuzzy_bytes: the word of ONE string s[0, len) for the patterns, by the same lane code on the host — no GPU, no context —;
+ * SX_E_INVALID (*word = 0) for what sx_fuzzy_set_create refuses, a NULL pointer (s may be NULL if len is 0) or len >= 2^32.
+ * Not thread-safe: one sx_result_fuzzy_device call per set at a time, and no reset or read during it.
+ * Not built: distance in characters; the best distance per pattern as a field of the word; where the match lies; transpositions as
+ * one error; patterns of more than 64 bytes; more than 64 patterns; Unicode folding inside the call (sx_result_fold_device in front
+ * of it, sx_labels_rebind behind); the sharded entry points. */
+#define SX_FUZZY_MAX_PATTERNS      64u
+#define SX_FUZZY_MAX_PATTERN_BYTES 64u
+#define SX_FUZZY_MAX_ERRORS        8u
+typedef struct sx_fuzzy_set sx_fuzzy_set;   /* compiled patterns + their counters, in HBM */
+typedef struct sx_fuzzy_set_info {
+    uint32_t n_patterns, classes, lds_classes, nocase;
+    uint64_t table_bytes;     /* everything the set holds in HBM except the counters */
+    uint32_t max_len, max_errors;
+} sx_fuzzy_set_info;
+int  sx_fuzzy_set_create(sx_ctx* ctx, const sx_pattern* patterns, const uint8_t* max_errors, uint32_t n_patterns, uint32_t flags, sx_fuzzy_set** out);
+int  sx_fuzzy_set_info_get(const sx_fuzzy_set* set, sx_fuzzy_set_info* out);
+void sx_fuzzy_set_free(sx_fuzzy_set* set);
+int  sx_fuzzy_set_reset(sx_fuzzy_set* set);
+int  sx_fuzzy_set_read(const sx_fuzzy_set* set, uint64_t* findings, uint64_t* first, uint32_t n_patterns);
+int  sx_fuzzy_set_counters_device(const sx_fuzzy_set* set, const uint64_t** d_findings, const uint64_t** d_first);
+int  sx_result_fuzzy_device(sx_ctx* ctx, const sx_result* r, sx_fuzzy_set* set, uint64_t ordinal_base, sx_labels** out);
+int  sx_fuzzy_bytes(const sx_pattern* patterns, const uint8_t* max_errors, uint32_t n_patterns, uint32_t flags, const uint8_t* s, uint64_t len, uint64_t* word);
+
 int  sx_get_stats(const sx_ctx* ctx, sx_stats* out); /* of the last scan call */
 void sx_free(void* p);
 

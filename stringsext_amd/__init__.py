@@ -37,6 +37,7 @@ SX_FOLD_SIMPLE = 0   # sx_result_fold_device (Result.fold_device), sx_fold_utf8 
 SX_MEASURE_ENTROPY_SHIFT, SX_MEASURE_DISTINCT_SHIFT, SX_MEASURE_CHARS_SHIFT = 0, 16, 32
 SX_MEASURE_LOWER, SX_MEASURE_UPPER, SX_MEASURE_DIGIT, SX_MEASURE_SPACE = 1 << 25, 1 << 26, 1 << 27, 1 << 28
 SX_MEASURE_PUNCT, SX_MEASURE_CONTROL, SX_MEASURE_HIGH = 1 << 29, 1 << 30, 1 << 31
+SX_FUZZY_MAX_PATTERNS, SX_FUZZY_MAX_PATTERN_BYTES, SX_FUZZY_MAX_ERRORS = 64, 64, 8   # sx_fuzzy_set_create (Scanner.fuzzy_set), sx_fuzzy_bytes (fuzzy)
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
        "iso-8859-2": 18, "iso-8859-5": 19, "iso-8859-15": 20, "windows-1251": 21, "windows-1252": 22,
@@ -65,6 +66,8 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_seen_set_merge", "sx_seen_set_grow", "sx_seen_set_export_size", "sx_seen_set_export", "sx_seen_blob_info_get", "sx_seen_set_import", "sx_seen_set_add_strings",
            "sx_result_seen_counts_device", "sx_result_select_labels_range_device", "sx_result_order_device",
            "sx_fold_utf8", "sx_result_fold_device", "sx_labels_rebind", "sx_result_measure_device", "sx_measure_bytes",
+           "sx_fuzzy_set_create", "sx_fuzzy_set_info_get", "sx_fuzzy_set_free", "sx_fuzzy_set_reset", "sx_fuzzy_set_read", "sx_fuzzy_set_counters_device",
+           "sx_result_fuzzy_device", "sx_fuzzy_bytes",
            "sx_get_stats", "sx_free", "sx_fill_background_device",
            "sx_device_alloc", "sx_device_free", "sx_device_upload", "sx_device_download",
            "sx_device_read_bandwidth"]
@@ -218,6 +221,11 @@ class TallySetInfo(C.Structure):   # sx_tally_set_info
 class LabelSetInfo(C.Structure):   # sx_label_set_info
     _fields_ = [("n_patterns", C.c_uint32), ("states", C.c_uint32), ("classes", C.c_uint32), ("nocase", C.c_uint32),
                 ("table_bytes", C.c_uint64), ("lds_states", C.c_uint32), ("here_states", C.c_uint32)]
+
+
+class FuzzySetInfo(C.Structure):   # sx_fuzzy_set_info
+    _fields_ = [("n_patterns", C.c_uint32), ("classes", C.c_uint32), ("lds_classes", C.c_uint32), ("nocase", C.c_uint32),
+                ("table_bytes", C.c_uint64), ("max_len", C.c_uint32), ("max_errors", C.c_uint32)]
 
 
 class OrderSpec(C.Structure):   # sx_order_spec
@@ -383,6 +391,14 @@ def lib():
     L.sx_labels_rebind.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.sx_result_measure_device.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(MeasureInfo)]
     L.sx_measure_bytes.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.sx_fuzzy_set_create.argtypes = [vp, C.POINTER(Pattern), C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.sx_fuzzy_set_info_get.argtypes = [vp, C.POINTER(FuzzySetInfo)]
+    L.sx_fuzzy_set_free.argtypes, L.sx_fuzzy_set_free.restype = [vp], None
+    L.sx_fuzzy_set_reset.argtypes = [vp]
+    L.sx_fuzzy_set_read.argtypes = [vp, pu64, pu64, C.c_uint32]
+    L.sx_fuzzy_set_counters_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.sx_result_fuzzy_device.argtypes = [vp, vp, vp, u64, C.POINTER(vp)]
+    L.sx_fuzzy_bytes.argtypes = [C.POINTER(Pattern), C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.sx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sx_free.argtypes = [vp]
     L.sx_fill_background_device.argtypes = [vp, vp, u64, u64, u64]
@@ -422,6 +438,29 @@ def measure(data):
     rc = lib().sx_measure_bytes(data, len(data), 0, C.byref(word))
     if rc != SX_OK:
         raise SxError(rc, "sx_measure_bytes")
+    return word.value
+
+
+def _error_budgets(max_errors, n):
+    """max_errors of fuzzy_set() and fuzzy() — an int for every pattern, or one per pattern — as the n bytes the library takes"""
+    ks = [max_errors] * n if isinstance(max_errors, int) else list(max_errors)
+    if len(ks) != n:
+        raise ValueError("max_errors is an int or has one entry per pattern")
+    if any(not 0 <= k <= 255 for k in ks):
+        raise ValueError("an error budget is 0..SX_FUZZY_MAX_ERRORS")
+    return bytes(ks)
+
+
+def fuzzy(patterns, max_errors, data, ignore_case=False):
+    """sx_fuzzy_bytes: the word of Result.fuzzy_device() for `data` (bytes) and a set of these patterns, by the same code and without
+    a GPU — bit p is set iff some substring of `data` is within max_errors (an int, or one per pattern) insertions, deletions and
+    substitutions of a byte of patterns[p].  SxError SX_E_INVALID for what Scanner.fuzzy_set refuses, and for 2^32 bytes or more."""
+    data = bytes(data)
+    arr, n = _pattern_array(patterns)
+    word = C.c_uint64()
+    rc = lib().sx_fuzzy_bytes(arr, _error_budgets(max_errors, n), n, SX_SELECT_ASCII_NOCASE if ignore_case else 0, data, len(data), C.byref(word))
+    if rc != SX_OK:
+        raise SxError(rc, "sx_fuzzy_bytes")
     return word.value
 
 
@@ -627,6 +666,19 @@ class Result:
             raise SxError(SX_E_INVALID, "the LabelSet has been freed" if isinstance(label_set, LabelSet) else "label_device takes a LabelSet")
         out = C.c_void_p()
         self._s._chk(lib().sx_result_label_device(self._s.h, self.h, label_set.h, ordinal_base, C.byref(out)))
+        return Labels(self._s, out)
+
+    def fuzzy_device(self, fuzzy_set, ordinal_base=0):
+        """sx_result_fuzzy_device: for every finding of this Result WHICH patterns of `fuzzy_set` (a FuzzySet: Scanner.fuzzy_set) occur
+        in its string within their error budget — Labels, one 64-bit word per finding in HBM, bit p for pattern p, fuzzy() of its
+        string —, and per pattern the number of such findings and the first of them, added to the set's counters (ordinal_base: the
+        findings of the buffers before this one).  select_device(labels, any=...), select_range_device(), order_device(labels=...)
+        and Labels.rebind() take the Labels as they take label_device()'s.  This Result is read, never moved, and the call is no
+        selection.  Raises SxError: SX_E_STATE as printed_device() does, SX_E_INVALID for a set on another device."""
+        if not isinstance(fuzzy_set, FuzzySet) or not fuzzy_set.h:
+            raise SxError(SX_E_INVALID, "the FuzzySet has been freed" if isinstance(fuzzy_set, FuzzySet) else "fuzzy_device takes a FuzzySet")
+        out = C.c_void_p()
+        self._s._chk(lib().sx_result_fuzzy_device(self._s.h, self.h, fuzzy_set.h, ordinal_base, C.byref(out)))
         return Labels(self._s, out)
 
     def distinct_device(self, ignore_case=False):
@@ -945,6 +997,44 @@ class LabelSet(_DeviceHandle):
         return f.value, m.value
 
 
+class FuzzySet(_DeviceHandle):
+    """Keywords with error budgets compiled for the approximate match on the device (sx_fuzzy_set_create; Scanner.fuzzy_set makes it),
+    with their counters: Result.fuzzy_device() says which of them every finding holds within its budget and adds to the counters, on
+    result after result.  It owns its device memory: free() it before or after the Scanner's close()."""
+
+    _free, _info_get, _info_type = "sx_fuzzy_set_free", "sx_fuzzy_set_info_get", FuzzySetInfo
+
+    def __init__(self, handle, n_patterns):
+        self.h, self.n_patterns = handle, n_patterns
+
+    @property
+    def info(self):
+        """a FuzzySetInfo (sx_fuzzy_set_info): n_patterns, classes, lds_classes, nocase, table_bytes (in HBM), max_len, max_errors"""
+        return self._info()
+
+    def read(self):
+        """(findings, first): two lists with an entry per pattern; first[p] is SX_LABEL_NEVER where findings[p] is 0"""
+        findings, first = (C.c_uint64 * self.n_patterns)(), (C.c_uint64 * self.n_patterns)()
+        rc = lib().sx_fuzzy_set_read(self._handle(), findings, first, self.n_patterns)
+        if rc != SX_OK:
+            raise SxError(rc, "sx_fuzzy_set_read")
+        return list(findings), list(first)
+
+    def reset(self):
+        """every findings = 0, every first = SX_LABEL_NEVER"""
+        rc = lib().sx_fuzzy_set_reset(self._handle())
+        if rc != SX_OK:
+            raise SxError(rc, "sx_fuzzy_set_reset")
+
+    def counters_device(self):
+        """(d_findings, d_first): device addresses of two arrays of 64 uint64, of which the first n_patterns are used"""
+        f, m = C.c_void_p(), C.c_void_p()
+        rc = lib().sx_fuzzy_set_counters_device(self._handle(), C.byref(f), C.byref(m))
+        if rc != SX_OK:
+            raise SxError(rc, "sx_fuzzy_set_counters_device")
+        return f.value, m.value
+
+
 class SeenSet(_DeviceHandle):
     """Strings remembered in HBM from one Result to the next (sx_seen_set_create; Scanner.seen_set makes it): Result.seen_device() says
     which findings' strings it held and adds the others, on result after result.  Its capacity is fixed.  It owns its device memory:
@@ -1184,6 +1274,16 @@ class Scanner:
         out = C.c_void_p()
         self._chk(lib().sx_label_set_create(self.h, arr, n, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
         return LabelSet(out, n)
+
+    def fuzzy_set(self, patterns, max_errors=1, ignore_case=False):
+        """sx_fuzzy_set_create: `patterns` (1..64 byte strings of 1..64 bytes; pattern p owns bit p of a word) with their error budgets
+        — max_errors: an int for all of them, or one per pattern; 0..8 and smaller than the pattern's length — compiled into bit masks
+        in HBM on this Scanner's device, with two counters per pattern, for Result.fuzzy_device().  ignore_case: 'A'..'Z' and 'a'..'z'
+        compare equal in pattern and string.  SxError SX_E_INVALID, with the pattern's index in the text, for what is refused."""
+        arr, n = _pattern_array(patterns)
+        out = C.c_void_p()
+        self._chk(lib().sx_fuzzy_set_create(self.h, arr, _error_budgets(max_errors, n), n, SX_SELECT_ASCII_NOCASE if ignore_case else 0, C.byref(out)))
+        return FuzzySet(out, n)
 
     def seen_set(self, capacity_strings, capacity_bytes, ignore_case=False, counted=False):
         """sx_seen_set_create: an empty SeenSet for capacity_strings strings whose entries take capacity_bytes at most — a string of

@@ -336,6 +336,10 @@ hipError_t seltally_launch(const SeltallyParams& P, hipStream_t stream);
 // labels and adds to the set's counters; nothing else is written, and both are valid once `stream` has got there
 struct LabelParams;
 hipError_t label_launch(const LabelParams& P, hipStream_t stream);
+// The approximate matches on the device (sx_fuzzy_dev.hip, FuzzyParams: sx_fuzzy_core.hpp), a segment at a time: fuzzy_match_kernel writes
+// the segment's words and adds to the set's counters; nothing else is written, and both are valid once `stream` has got there
+struct FuzzyParams;
+hipError_t fuzzy_launch(const FuzzyParams& P, hipStream_t stream);
 // The duplicate strings on the device (sx_distinct_dev.hip, DistinctParams: sx_distinct_core.hpp), one phase of one segment per launch:
 // claim and resolve of a round — every segment's claim in front of any segment's resolve —, finalize behind the last round.  Only the
 // call's own tables and, in finalize, the segment's words are written

@@ -97,7 +97,9 @@ SXD void label_count_bit(uint32_t* counts, uint64_t* mins, uint32_t p, uint64_t 
 }
 
 // When the workgroup's wavefronts are done: counter c of the workgroup's counters and minima into the set's (c < kLabelBits).
-SXD void label_flush_lane(const LabelParams& P, const uint32_t* counts, const uint64_t* mins, uint32_t c) {
+// (PP: LabelParams, or the FuzzyParams of sx_fuzzy_core.hpp)
+template <class PP>
+SXD void label_flush_lane(const PP& P, const uint32_t* counts, const uint64_t* mins, uint32_t c) {
     const uint32_t v = counts[c];
     if (!v) return;
     seltally_add64(P.set.findings + c, v);

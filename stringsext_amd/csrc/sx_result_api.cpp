@@ -1,5 +1,5 @@
 // sx_result_api.cpp — the C-ABI of include/stringsext_amd.h for a result that stays in HBM (SX_OPT_RESULT_ON_DEVICE): the print, the
-// selections, the extraction, the Unicode case fold, what the strings look like, the tally, the labels and their rebinding, the duplicate strings and the seen set — with its merge, growth, blob and string
+// selections, the extraction, the Unicode case fold, what the strings look like, the tally, the labels and their rebinding, the approximate match, the duplicate strings and the seen set — with its merge, growth, blob and string
 // lists, and its counts —, and the compiled sets they take.  What the operations share is here once — the view of a segment, a set's upload, a
 // handle's device and memory, the counters' reset, a buffer that grows, a result's labels, the two passes of whatever writes a new
 // result, the mark and add passes of whatever goes into a seen set —; what tells them apart is in their lane functions
@@ -21,6 +21,8 @@
 #include "sx_order_core.hpp"
 #include "sx_fold_core.hpp"
 #include "sx_measure_core.hpp"
+#include "sx_fuzzy_build.hpp"
+#include "sx_fuzzy_core.hpp"
 #include "sx_seen_core.hpp"
 #include "sx_seen_merge_core.hpp"
 #include "sx_seen_count_core.hpp"
@@ -65,6 +67,13 @@ struct sx_tally_set : sx_device_handle {
 struct sx_label_set : sx_device_handle {
     LabelDevice dev{};
     sx_label_set_info info{};
+};
+
+// sx_fuzzy_set_create: keywords with error budgets compiled for the approximate match; `mem` = [the class map][the masks][len and k]
+// [findings][first]
+struct sx_fuzzy_set : sx_device_handle {
+    FuzzyDevice dev{};
+    sx_fuzzy_set_info info{};
 };
 
 // sx_result_label_device: one result's labels; `mem` = an array per source segment, each 256-byte aligned.
@@ -233,6 +242,48 @@ sx_labels* labels_of(const sx_ctx* ctx, const sx_result* r, uint64_t* bytes) {
         at += up256(s.ext_nf * sizeof(uint64_t));
     }
     return lab;
+}
+
+// The words of a compiled set where the findings lie — the labels (sx_label_dev.hip), the approximate matches (sx_fuzzy_dev.hip) —: the
+// source is checked as a whole, the words' memory is had, then one kernel per segment, each with the ordinal of its first record, on
+// the selections' stream, and one wait.  Only the words and the set's counters are written.  what: the call's nouns for the messages —
+// { no device ..., ... on another device, ... on the host, device ...: , bytes of ... }; launch: P (Params) with the segment, the
+// ordinal, the words' place and the set's tables
+struct SetWordsWhat { const char *no_device, *set_lies, *host_call, *device, *words; };
+template <class Params, class Set, class Launch>
+int set_words_on_device(sx_ctx* ctx, const sx_result* r, Set* set, uint64_t ordinal_base, sx_labels** out, const SetWordsWhat& what, Launch launch) {
+    if (out) *out = nullptr;
+    if (!ctx || !r || !set || !out) return SX_E_INVALID;
+    if (host_only(ctx, what.no_device)) return SX_E_STATE;
+    if (on_another_device(ctx, *set, what.set_lies)) return SX_E_INVALID;
+    { const int rc = result_on_device(ctx, r, what.host_call); if (rc != SX_OK) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->post_stream;
+    uint64_t bytes = 0;
+    sx_labels* lab = labels_of(ctx, r, &bytes);
+    if (!lab) {
+        ctx->set_err(std::string("device ") + what.device + ": no memory for " + std::to_string(bytes) + " bytes of " + what.words);
+        return SX_E_NOMEM;
+    }
+    uint64_t walked = 0;
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; e == hipSuccess && i < lab->segs.size(); i++) {
+        Params p = params_of<Params>(seg_ref(r->r.segs[i]));
+        p.ordinal = ordinal_base + walked;
+        p.labels = (uint64_t*)lab->segs[i].d;
+        p.set = set->dev;
+        e = launch(p, st);
+        walked += lab->segs[i].n;
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) {
+        sx_labels_free(lab);
+        ctx->set_err(std::string("device ") + what.device + ": " + hipGetErrorString(e));
+        return SX_E_HIP;
+    }
+    *out = lab;
+    return SX_OK;
 }
 
 // The two passes of an operation that writes a new result, a segment at a time, as select_on_device drives them.  measure: pass 1
@@ -991,42 +1042,8 @@ int sx_label_set_counters_device(const sx_label_set* set, const uint64_t** d_fin
     return SX_OK;
 }
 
-// The labels where the findings lie (sx_label_dev.hip): the source is checked as a whole, the labels' memory is had, then one kernel per
-// segment, each with the ordinal of its first record, on the selections' stream, and one wait.  Only the labels and the set's counters
-// are written.
 int sx_result_label_device(sx_ctx* ctx, const sx_result* r, sx_label_set* set, uint64_t ordinal_base, sx_labels** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !r || !set || !out) return SX_E_INVALID;
-    if (host_only(ctx, "labels")) return SX_E_STATE;
-    if (on_another_device(ctx, *set, "the label set lies")) return SX_E_INVALID;
-    { const int rc = result_on_device(ctx, r, "label on the host"); if (rc != SX_OK) return rc; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->post_stream;
-    uint64_t bytes = 0;
-    sx_labels* lab = labels_of(ctx, r, &bytes);
-    if (!lab) {
-        ctx->set_err("device labels: no memory for " + std::to_string(bytes) + " bytes of labels");
-        return SX_E_NOMEM;
-    }
-    uint64_t walked = 0;
-    hipError_t e = hipSuccess;
-    for (size_t i = 0; e == hipSuccess && i < lab->segs.size(); i++) {
-        LabelParams p = params_of<LabelParams>(seg_ref(r->r.segs[i]));
-        p.ordinal = ordinal_base + walked;
-        p.labels = (uint64_t*)lab->segs[i].d;
-        p.set = set->dev;
-        e = label_launch(p, st);
-        walked += lab->segs[i].n;
-    }
-    const hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) {
-        sx_labels_free(lab);
-        ctx->set_err(std::string("device labels: ") + hipGetErrorString(e));
-        return SX_E_HIP;
-    }
-    *out = lab;
-    return SX_OK;
+    return set_words_on_device<LabelParams>(ctx, r, set, ordinal_base, out, { "labels", "the label set lies", "label on the host", "labels", "labels" }, label_launch);
 }
 
 uint64_t sx_labels_segments(const sx_labels* labels) { return labels ? labels->segs.size() : 0; }
@@ -1185,6 +1202,63 @@ int sx_result_measure_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx
     }
     if (info) *info = sx_measure_info{ tot[kMeasureFindings], tot[kMeasureBytes], tot[kMeasureChars], tot[kMeasureWide], tot[kMeasureAscii] };
     *out = lab;
+    return SX_OK;
+}
+
+// The approximate match (sx_fuzzy_build.hpp, sx_fuzzy_core.hpp, sx_fuzzy_dev.hip): the set, its counters, the words of a result, and
+// the same lane code for one string on the host
+int sx_fuzzy_set_reset(sx_fuzzy_set* set) {
+    if (!set) return SX_E_INVALID;
+    return reset_counters(set->device, set->dev.findings, set->dev.first, kLabelBits);
+}
+
+int sx_fuzzy_set_create(sx_ctx* ctx, const sx_pattern* patterns, const uint8_t* max_errors, uint32_t n_patterns, uint32_t flags, sx_fuzzy_set** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !patterns || !max_errors || !out) return SX_E_INVALID;
+    FuzzyTable T;
+    std::string err;
+    { const int rc = fuzzy_build(patterns, max_errors, n_patterns, flags, &T, &err); if (rc != SX_OK) { ctx->set_err("fuzzy set: " + err); return rc; } }
+    const size_t eq_bytes = T.eq.size() * sizeof(uint64_t), lenk_bytes = n_patterns * sizeof(uint32_t), counters = kLabelBits * sizeof(uint64_t);
+    uint8_t* mem = nullptr;
+    size_t at[4];
+    { const int rc = upload_set(ctx, "fuzzy set", { { T.map, sizeof T.map, 16 }, { T.eq.data(), eq_bytes, 16 }, { T.lenk, lenk_bytes, 8 } }, 2 * counters, &mem, at);
+      if (rc != SX_OK) return rc; }
+    sx_fuzzy_set* set = new_handle<sx_fuzzy_set>(ctx, mem);
+    if (!set) return SX_E_NOMEM;
+    set->dev = FuzzyDevice{ (const uint16_t*)mem, (const uint64_t*)(mem + at[1]), (const uint32_t*)(mem + at[2]), (uint64_t*)(mem + at[3]),
+                            (uint64_t*)(mem + at[3] + counters), T.n_patterns, T.classes, T.lds_classes, T.max_len };
+    set->info = sx_fuzzy_set_info{ T.n_patterns, T.classes, T.lds_classes, T.nocase, (uint64_t)(sizeof T.map + eq_bytes + lenk_bytes), T.max_len, T.max_errors };
+    if (sx_fuzzy_set_reset(set) != SX_OK) { ctx->set_err("fuzzy set: the counters could not be reset"); sx_fuzzy_set_free(set); return SX_E_HIP; }
+    *out = set;
+    return SX_OK;
+}
+int sx_fuzzy_set_info_get(const sx_fuzzy_set* set, sx_fuzzy_set_info* out) { return handle_info(set, out); }
+void sx_fuzzy_set_free(sx_fuzzy_set* set) { handle_free(set); }
+
+int sx_fuzzy_set_read(const sx_fuzzy_set* set, uint64_t* findings, uint64_t* first, uint32_t n_patterns) {
+    if (!set || n_patterns != set->info.n_patterns) return SX_E_INVALID;
+    const int rc = read_counters(set->device, set->dev.findings, findings, n_patterns);
+    return rc != SX_OK ? rc : read_counters(set->device, set->dev.first, first, n_patterns);
+}
+
+int sx_fuzzy_set_counters_device(const sx_fuzzy_set* set, const uint64_t** d_findings, const uint64_t** d_first) {
+    if (!set) return SX_E_INVALID;
+    if (d_findings) *d_findings = set->dev.findings;
+    if (d_first) *d_first = set->dev.first;
+    return SX_OK;
+}
+
+int sx_result_fuzzy_device(sx_ctx* ctx, const sx_result* r, sx_fuzzy_set* set, uint64_t ordinal_base, sx_labels** out) {
+    return set_words_on_device<FuzzyParams>(ctx, r, set, ordinal_base, out, { "approximate match", "the fuzzy set lies", "match on the host", "fuzzy", "words" }, fuzzy_launch);
+}
+
+int sx_fuzzy_bytes(const sx_pattern* patterns, const uint8_t* max_errors, uint32_t n_patterns, uint32_t flags, const uint8_t* s, uint64_t len, uint64_t* word) {
+    if (word) *word = 0;
+    if ((!s && len) || !word || len >> 32) return SX_E_INVALID;
+    FuzzyTable T;
+    { const int rc = fuzzy_build(patterns, max_errors, n_patterns, flags, &T, nullptr); if (rc != SX_OK) return rc; }
+    const FuzzyDevice dev{ T.map, T.eq.data(), T.lenk, nullptr, nullptr, T.n_patterns, T.classes, T.lds_classes, T.max_len };
+    *word = fuzzy_string_host(dev, s, (uint32_t)len);
     return SX_OK;
 }
 

@@ -1,5 +1,5 @@
 // sx_rows_dev.hpp — what the kernels that walk a table over a segment's records share (sx_selset_dev.hip, sx_selre_dev.hip,
-// sx_extract_dev.hip, sx_seltally_dev.hip, sx_label_dev.hip; sx_select_dev.hip for the epilogue; sx_seen_dev.hip, sx_seen_merge_dev.hip
+// sx_extract_dev.hip, sx_seltally_dev.hip, sx_label_dev.hip, sx_fuzzy_dev.hip; sx_select_dev.hip for the epilogue; sx_seen_dev.hip, sx_seen_merge_dev.hip
 // and sx_print_dev.hip for the wavefront's sum, prefix and reserve): the workgroup's shape, the class map and the first rows into
 // LDS, the grid that strides over the segment, the words a pass 1 of the selection leaves per wavefront, and the table checks.  Device-only: included behind <hip/hip_runtime.h> and sx_device.hpp.  The walks themselves are the kernels'.
 #pragma once

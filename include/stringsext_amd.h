@@ -1101,6 +1101,65 @@ typedef struct sx_measure_info { uint64_t findings, bytes, chars, wide, ascii; }
 int  sx_result_measure_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_labels** out, sx_measure_info* info /* may be NULL */);
 int  sx_measure_bytes(const uint8_t* s, uint64_t len, uint32_t flags, uint64_t* word);
 
+/* WHAT AN ENCODED STRING HOLDS: sx_result_decode_device.  *out (sx_result_free) is a new result in HBM with the findings of r in the
+ * same order, every string that decodes under `kind` replaced by the bytes it stands for; a string that does not decode keeps its
+ * bytes, copied.  Every operation above then works on the decoded bytes — a label set on what a base64 -EncodedCommand says —, and
+ * sx_labels_rebind carries an answer back to the encoded originals, and the call's own words forth to *out.  The output follows
+ * sx_result_fold_device's contract: output segment i corresponds to source segment i record for record — the same number of records
+ * of the same type, the same sx_segment_info, every field of a record but str_off and str_len as it was, the strings back to back in
+ * record order —, and no string is empty.
+ * THE RULE.  A string s of n bytes gives raw bytes D, or does not decode:
+ *   SX_DECODE_BASE64   pad = the number of trailing '=', two at most; body = the rest, of m bytes.  s decodes iff m >= 2, m % 4 != 1,
+ *                      pad == 0 or (m + pad) % 4 == 0, every body byte is of A-Za-z0-9 or one of + / - _, and the body does not hold
+ *                      both a byte of "+/" and a byte of "-_".  Unpadded input decodes (a JWT's segments); the bits left over behind
+ *                      the last whole byte are dropped whatever they are.  In Python: base64.b64decode(body.translate(
+ *                      bytes.maketrans(b"-_", b"+/")) + b"=" * (-m % 4), validate=True).
+ *   SX_DECODE_HEX      n is even, n >= 2, every byte is a hex digit of either case: binascii.unhexlify(s).
+ *   SX_DECODE_PERCENT  from the left, '%' with two hex digits behind it inside the string is that byte and the walk goes on three
+ *                      bytes further; any other byte is copied, '+' stays '+'.  s decodes iff at least one escape was decoded:
+ *                      urllib.parse.unquote_to_bytes(s).
+ * flags: 0, the output is D; SX_DECODE_UTF16LE, D is read as UTF-16LE and written as UTF-8 — D.decode("utf-16-le").encode("utf-8") —,
+ * and an odd length or a lone surrogate makes the whole string "does not decode"; a BOM is an ordinary U+FEFF.
+ * THE WORD of a finding, 0 where its string does not decode:
+ *   bit 0    SX_DECODE_OK       the string decodes
+ *   bit 1    SX_DECODE_TEXT     every OUTPUT byte is 0x20..0x7E, 0x09, 0x0A or 0x0D.  Most identifiers are valid base64:
+ *                               sx_result_select_labels_device with all = SX_DECODE_OK | SX_DECODE_TEXT is the filter to use
+ *   bit 2    SX_DECODE_WIDE     D, before any transcoding, has an even length >= 2, every odd-index byte 0 and every even-index byte
+ *                               of the TEXT class: a second call with SX_DECODE_UTF16LE is worth making
+ *   bit 3    SX_DECODE_PADDED   base64 only: pad > 0
+ *   bit 4    SX_DECODE_URLSAFE  base64 only: the body held '-' or '_'
+ *   bits 32..63  SX_DECODE_LEN_SHIFT, 32 bits   the output's length in bytes
+ * *words (may be NULL; sx_labels_free): one word per finding of r, laid out and bound to r exactly as sx_result_measure_device's; it
+ * is no selection and ages nothing.  The call itself counts as a selection exactly as sx_result_fold_device does; a call that returns
+ * an error takes no turn and writes no block.  r is read, never moved.
+ * *info (may be NULL): findings; decoded, text, wide = the findings whose word has SX_DECODE_OK, SX_DECODE_TEXT, SX_DECODE_WIDE;
+ * bytes_in = the source strings' bytes, bytes_out = the output strings'.
+ * SX_DECODE_UTF16LE can GROW a string: base64 to 9/8 of its source, percent towards 3/2.  Sources and SX_E_STATE exactly as
+ * sx_result_fold_device.  SX_E_INVALID (sx_last_error says which): a NULL pointer, an unknown kind or flag, a segment whose output
+ * strings have 2^32 bytes or more, a packed segment with an output string longer than 65535 bytes — decided before anything is
+ * written.  SX_E_NOMEM: a block, the words or the tables cannot be had.  *out = NULL and *words = NULL on every error.
+ *
+ * sx_decode_bytes: the same rule, the same code, for one byte string on the host; no context.  The output goes to out[0, *written);
+ * out = NULL asks for the size: *written = the output's length, nothing is written.  A string that does not decode is no error:
+ * SX_OK, *word = 0, and the output is the source, copied.  *word (may be NULL): the string's word.  SX_E_INVALID: a NULL pointer (in
+ * may be NULL where len is 0), an unknown kind or flag, len >= 2^32, or cap < the output's length — then *written says what is
+ * needed and out is untouched.
+ * Not built: base32, uuencode, quoted-printable; white space or line breaks inside base64; a 0x prefix or \x escapes; UTF-16BE; a
+ * well-formed-UTF-8 bit; nested decoding in one call; sharded entry points; a packed segment expanded where an output outgrows it. */
+enum { SX_DECODE_BASE64 = 1u, SX_DECODE_HEX = 2u, SX_DECODE_PERCENT = 3u };   /* kind */
+enum { SX_DECODE_UTF16LE = 1u };                                               /* flags */
+#define SX_DECODE_OK      ((uint64_t)1 << 0)
+#define SX_DECODE_TEXT    ((uint64_t)1 << 1)
+#define SX_DECODE_WIDE    ((uint64_t)1 << 2)
+#define SX_DECODE_PADDED  ((uint64_t)1 << 3)
+#define SX_DECODE_URLSAFE ((uint64_t)1 << 4)
+#define SX_DECODE_LEN_SHIFT 32
+typedef struct sx_decode_info { uint64_t findings, decoded, text, wide, bytes_in, bytes_out; } sx_decode_info;
+int  sx_result_decode_device(sx_ctx* ctx, const sx_result* r, uint32_t kind, uint32_t flags, sx_result** out,
+                             sx_labels** words /* may be NULL */, sx_decode_info* info /* may be NULL */);
+int  sx_decode_bytes(uint32_t kind, uint32_t flags, const uint8_t* in, uint64_t len, uint8_t* out, uint64_t cap, uint64_t* written,
+                     uint64_t* word /* may be NULL */);
+
 /* The APPROXIMATE MATCHES of a result whose segments ALL lie in HBM: for every finding, WHICH keywords of a list occur in its string
  * with at most k errors — `agrep` / `tre-agrep` behind `strings`: a flipped byte, a dropped character, `passw0rd` —, as one 64-bit
  * word, made where the findings lie (csrc/sx_fuzzy_dev.hip) with no string byte crossing PCIe.  The word is a label: everything that

@@ -37,6 +37,10 @@ SX_FOLD_SIMPLE = 0   # sx_result_fold_device (Result.fold_device), sx_fold_utf8 
 SX_MEASURE_ENTROPY_SHIFT, SX_MEASURE_DISTINCT_SHIFT, SX_MEASURE_CHARS_SHIFT = 0, 16, 32
 SX_MEASURE_LOWER, SX_MEASURE_UPPER, SX_MEASURE_DIGIT, SX_MEASURE_SPACE = 1 << 25, 1 << 26, 1 << 27, 1 << 28
 SX_MEASURE_PUNCT, SX_MEASURE_CONTROL, SX_MEASURE_HIGH = 1 << 29, 1 << 30, 1 << 31
+# sx_result_decode_device (Result.decode_device), sx_decode_bytes (decode): the kinds, the flag, a word's bits and its length field
+SX_DECODE_BASE64, SX_DECODE_HEX, SX_DECODE_PERCENT, SX_DECODE_UTF16LE = 1, 2, 3, 1
+SX_DECODE_OK, SX_DECODE_TEXT, SX_DECODE_WIDE, SX_DECODE_PADDED, SX_DECODE_URLSAFE, SX_DECODE_LEN_SHIFT = 1, 2, 4, 8, 16, 32
+DECODE_KINDS = {"base64": SX_DECODE_BASE64, "hex": SX_DECODE_HEX, "percent": SX_DECODE_PERCENT}
 SX_FUZZY_MAX_PATTERNS, SX_FUZZY_MAX_PATTERN_BYTES, SX_FUZZY_MAX_ERRORS = 64, 64, 8   # sx_fuzzy_set_create (Scanner.fuzzy_set), sx_fuzzy_bytes (fuzzy)
 SX_OPT_RESULT_ON_DEVICE = 32   # a buffer's result stays in HBM (Result.device_segments): one Mission's block, or several Missions' merged parts
 ENC = {"x-user-defined": 0, "utf-8": 1, "utf-16le": 2, "utf-16be": 3, "koi8-r": 16, "ibm866": 17,
@@ -66,6 +70,7 @@ EXPORTS = ["sx_abi_version", "sx_create", "sx_destroy", "sx_last_error", "sx_sca
            "sx_seen_set_merge", "sx_seen_set_grow", "sx_seen_set_export_size", "sx_seen_set_export", "sx_seen_blob_info_get", "sx_seen_set_import", "sx_seen_set_add_strings",
            "sx_result_seen_counts_device", "sx_result_select_labels_range_device", "sx_result_order_device",
            "sx_fold_utf8", "sx_result_fold_device", "sx_labels_rebind", "sx_result_measure_device", "sx_measure_bytes",
+           "sx_result_decode_device", "sx_decode_bytes",
            "sx_fuzzy_set_create", "sx_fuzzy_set_info_get", "sx_fuzzy_set_free", "sx_fuzzy_set_reset", "sx_fuzzy_set_read", "sx_fuzzy_set_counters_device",
            "sx_result_fuzzy_device", "sx_fuzzy_bytes",
            "sx_get_stats", "sx_free", "sx_fill_background_device",
@@ -245,6 +250,11 @@ class MeasureInfo(C.Structure):   # sx_measure_info
     _fields_ = [("findings", C.c_uint64), ("bytes", C.c_uint64), ("chars", C.c_uint64), ("wide", C.c_uint64), ("ascii", C.c_uint64)]
 
 
+class DecodeInfo(C.Structure):   # sx_decode_info
+    _fields_ = [("findings", C.c_uint64), ("decoded", C.c_uint64), ("text", C.c_uint64), ("wide", C.c_uint64), ("bytes_in", C.c_uint64),
+                ("bytes_out", C.c_uint64)]
+
+
 class DistinctInfo(C.Structure):   # sx_distinct_info
     _fields_ = [("findings", C.c_uint64), ("distinct", C.c_uint64), ("repeated", C.c_uint64), ("rounds", C.c_uint32), ("table_log2", C.c_uint32)]
 
@@ -391,6 +401,8 @@ def lib():
     L.sx_labels_rebind.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.sx_result_measure_device.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(MeasureInfo)]
     L.sx_measure_bytes.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.sx_result_decode_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.POINTER(DecodeInfo)]
+    L.sx_decode_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.sx_fuzzy_set_create.argtypes = [vp, C.POINTER(Pattern), C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(vp)]
     L.sx_fuzzy_set_info_get.argtypes = [vp, C.POINTER(FuzzySetInfo)]
     L.sx_fuzzy_set_free.argtypes, L.sx_fuzzy_set_free.restype = [vp], None
@@ -441,6 +453,30 @@ def measure(data):
     return word.value
 
 
+def _decode_kind(kind):
+    if kind not in DECODE_KINDS:
+        raise ValueError("a decoding is one of %s" % ", ".join(sorted(DECODE_KINDS)))
+    return DECODE_KINDS[kind]
+
+
+def decode(kind, data, utf16le=False):
+    """sx_decode_bytes: (the output, the word) of Result.decode_device(kind, utf16le) for `data` (bytes), by the same code and without
+    a GPU.  kind: "base64" — padded or not, either alphabet —, "hex" or "percent"; utf16le: the decoded bytes are read as UTF-16LE and
+    returned as UTF-8.  Where `data` does not decode, the output is `data` and the word 0; else the word has SX_DECODE_OK, SX_DECODE_TEXT
+    (every output byte is printable ASCII, tab, LF or CR), SX_DECODE_WIDE (the raw bytes look like UTF-16LE text: decode again with
+    utf16le=True), SX_DECODE_PADDED, SX_DECODE_URLSAFE, and word >> SX_DECODE_LEN_SHIFT is the output's length."""
+    data, k, flags = bytes(data), _decode_kind(kind), SX_DECODE_UTF16LE if utf16le else 0
+    n, word = C.c_uint64(), C.c_uint64()
+    rc = lib().sx_decode_bytes(k, flags, data, len(data), None, 0, C.byref(n), None)
+    if rc != SX_OK:
+        raise SxError(rc, "sx_decode_bytes")
+    out = C.create_string_buffer(max(1, n.value))
+    rc = lib().sx_decode_bytes(k, flags, data, len(data), out, n.value, C.byref(n), C.byref(word))
+    if rc != SX_OK:
+        raise SxError(rc, "sx_decode_bytes")
+    return out.raw[:n.value], word.value
+
+
 def _error_budgets(max_errors, n):
     """max_errors of fuzzy_set() and fuzzy() — an int for every pattern, or one per pattern — as the n bytes the library takes"""
     ks = [max_errors] * n if isinstance(max_errors, int) else list(max_errors)
@@ -469,6 +505,8 @@ class Result:
 
     order_info = None      # order_device(): sx_order_info as a dict
     fold_info = None       # fold_device(): sx_fold_info as a dict
+    decode_info = None     # decode_device(): sx_decode_info as a dict
+    decode_words = None    # decode_device(): the Labels of the call, bound to its SOURCE
 
     def __init__(self, scanner, handle):
         self._s, self.h = scanner, handle
@@ -793,6 +831,33 @@ class Result:
         self._s._chk(lib().sx_result_fold_device(self._s.h, self.h, SX_FOLD_SIMPLE, C.byref(out), C.byref(info)))
         res = Result(self._s, out)
         res.fold_info = {k: getattr(info, k) for k, _ in FoldInfo._fields_}
+        return res
+
+    def decode_device(self, kind, utf16le=False):
+        """sx_result_decode_device: WHAT AN ENCODED STRING HOLDS — a new Result on the device with this Result's findings in the same
+        order, segment for segment and record for record, every string that decodes as `kind` ("base64", "hex", "percent"; decode() is
+        the rule) replaced by the bytes it stands for, every other string copied; utf16le=True reads the decoded bytes as UTF-16LE and
+        writes UTF-8 (a PowerShell -EncodedCommand).  Every other field and the segments' SegmentInfo stay.  .decode_words is the
+        Labels of the call, one word per finding, bound to THIS Result (rebind() carries them to the new one, and any Labels of the
+        new one back); .decode_info is sx_decode_info as a dict: findings, decoded, text, wide, bytes_in, bytes_out.
+
+            runs = r.extract_device(sc.extract_set([rb"[A-Za-z0-9+/]{16,}={0,2}"]))
+            d = runs.decode_device("base64", utf16le=True)
+            hits = d.label_device(sc.label_set([rb"downloadstring", rb"invoke-"], ignore_case=True))   # on the decoded text
+            runs.select_device(hits.rebind(runs), any=3)                                                # the encoded originals
+            d.select_device(d.decode_words.rebind(d), all=SX_DECODE_OK | SX_DECODE_TEXT)               # what decodes to text
+
+        The new Result lies on the device like a selection and counts as one; the words are no selection and age nothing.  This
+        Result is not moved.  Raises SxError: SX_E_STATE wherever fold_device() would refuse this Result, SX_E_INVALID for a segment
+        whose output strings outgrow 32-bit offsets or a packed record's 16-bit length."""
+        if not self._s.h:
+            raise SxError(SX_E_STATE, "the Scanner is closed: its device memory is gone")
+        out, words, info = C.c_void_p(), C.c_void_p(), DecodeInfo()
+        self._s._chk(lib().sx_result_decode_device(self._s.h, self.h, _decode_kind(kind), SX_DECODE_UTF16LE if utf16le else 0,
+                                                   C.byref(out), C.byref(words), C.byref(info)))
+        res = Result(self._s, out)
+        res.decode_words = Labels(self._s, words)
+        res.decode_info = {k: getattr(info, k) for k, _ in DecodeInfo._fields_}
         return res
 
     def measure_device(self):

@@ -323,6 +323,16 @@ struct FoldParams;
 size_t fold_scratch_bytes(uint64_t n);
 hipError_t fold_measure(FoldParams* P, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint64_t** count, const uint64_t** bytes, const uint64_t** totals);
 hipError_t fold_place(const FoldParams& P, void* out_recs, uint8_t* out_arena, hipStream_t stream);
+// The decoding of base64, hex and percent strings on the device (sx_decode_dev.hip, DecodeParams: sx_decode_core.hpp), a segment at a
+// time, in the fold's shape.  decode_measure: pass 1 — P.words (the caller's, a word per record), kind and flags are set; fills the
+// words and P's per-wavefront tables inside `scratch` (decode_scratch_bytes(n), 256-aligned); *count, *bytes, *totals = the device
+// words with the number of records, the output strings' bytes and the segment's kDecodeTotals totals, valid once `stream` has got
+// there; decode_place: every record, with its new str_off and str_len, to out_recs, the output strings back to back to out_arena —
+// what it writes is what pass 1 measured, the caller has checked that it fits
+struct DecodeParams;
+size_t decode_scratch_bytes(uint64_t n);
+hipError_t decode_measure(DecodeParams* P, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint64_t** count, const uint64_t** bytes, const uint64_t** totals);
+hipError_t decode_place(const DecodeParams& P, void* out_recs, uint8_t* out_arena, hipStream_t stream);
 // What the strings look like, on the device (sx_measure_dev.hip, MeasureParams: sx_measure_core.hpp), a segment at a time:
 // measure_narrow_kernel writes the words of the strings a lane can measure and lists the others, measure_wide_kernel behind it writes
 // theirs; both add to the call's totals.  Nothing else is written, and all of it is valid once `stream` has got there

@@ -1,5 +1,5 @@
 // sx_result_api.cpp — the C-ABI of include/stringsext_amd.h for a result that stays in HBM (SX_OPT_RESULT_ON_DEVICE): the print, the
-// selections, the extraction, the Unicode case fold, what the strings look like, the tally, the labels and their rebinding, the approximate match, the duplicate strings and the seen set — with its merge, growth, blob and string
+// selections, the extraction, the Unicode case fold, the decoding of encoded strings, what the strings look like, the tally, the labels and their rebinding, the approximate match, the duplicate strings and the seen set — with its merge, growth, blob and string
 // lists, and its counts —, and the compiled sets they take.  What the operations share is here once — the view of a segment, a set's upload, a
 // handle's device and memory, the counters' reset, a buffer that grows, a result's labels, the two passes of whatever writes a new
 // result, the mark and add passes of whatever goes into a seen set —; what tells them apart is in their lane functions
@@ -20,6 +20,7 @@
 #include "sx_distinct_core.hpp"
 #include "sx_order_core.hpp"
 #include "sx_fold_core.hpp"
+#include "sx_decode_core.hpp"
 #include "sx_measure_core.hpp"
 #include "sx_fuzzy_build.hpp"
 #include "sx_fuzzy_core.hpp"
@@ -378,7 +379,40 @@ struct Fold final : TwoPass {
     }
 };
 
-// A new result out of one in HBM, for the six entry points, whose arguments are checked: pass 1 of every segment, one wait for the
+// decode (sx_decode_dev.hip): the fold's shape — an output record is its source record with another string —, and pass 1 leaves the
+// call's words in `lab`, which the driver has made for the source
+struct Decode final : TwoPass {
+    const uint32_t kind, flags;
+    const sx_labels* lab;
+    std::vector<DecodeParams> D;
+    std::vector<const uint64_t*> d_totals;
+    sx_decode_info info{ 0, 0, 0, 0, 0, 0 };
+    Decode(size_t ns, uint32_t k, uint32_t f, const sx_labels* l) : kind(k), flags(f), lab(l), D(ns), d_totals(ns) {}
+    size_t count_bytes() const override { return sizeof(uint64_t); }
+    size_t scratch_bytes(uint64_t n) const override { return decode_scratch_bytes(n); }
+    hipError_t measure(size_t i, const SegRef& seg, void* scratch, size_t bytes, hipStream_t st, const void** count, const uint64_t** nbytes) override {
+        D[i] = params_of<DecodeParams>(seg);
+        D[i].kind = kind; D[i].flags = flags; D[i].words = (uint64_t*)lab->segs[i].d;
+        return decode_measure(&D[i], scratch, bytes, st, (const uint64_t**)count, nbytes, &d_totals[i]);
+    }
+    size_t place_scratch_bytes(uint64_t c) const override { return 0; }
+    hipError_t place(size_t i, void* recs, uint64_t c, uint8_t* arena, void* scratch, size_t bytes, hipStream_t st) override {
+        return c == D[i].n ? decode_place(D[i], recs, arena, st) : hipErrorInvalidValue;
+    }
+    int settle(size_t i, uint64_t c, uint64_t bytes, std::string* why) override {
+        uint64_t tot[kDecodeTotals] = { 0 };
+        const hipError_t e = hipMemcpy(tot, d_totals[i], sizeof tot, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { (void)hipGetLastError(); *why = "device decode: segment " + std::to_string(i) + "'s totals: " + hipGetErrorString(e); return SX_E_HIP; }
+        const DecodeFit fit = decode_segment_fits(D[i].packed, bytes, tot[kDecodeLongest]);
+        if (fit == kDecodeTooManyBytes) { *why = "decode: segment " + std::to_string(i) + " has " + std::to_string(bytes) + " bytes of output strings: a 32-bit str_off holds less than 2^32"; return SX_E_INVALID; }
+        if (fit == kDecodePackedTooLong) { *why = "decode: a string of the packed segment " + std::to_string(i) + " has " + std::to_string(tot[kDecodeLongest]) + " bytes when it is decoded: the 16-bit str_len of sx_finding16 holds 65535"; return SX_E_INVALID; }
+        info.findings += c; info.decoded += tot[kDecodeDecoded]; info.text += tot[kDecodeText]; info.wide += tot[kDecodeWide];
+        info.bytes_in += tot[kDecodeBytesIn]; info.bytes_out += bytes;
+        return SX_OK;
+    }
+};
+
+// A new result out of one in HBM, for the eight entry points, whose arguments are checked: pass 1 of every segment, one wait for the
 // segments' totals, the selection block, pass 2 of every segment that has output records, one more wait.  The source is read, never
 // moved.  The blocks take turns: the one this call writes held the selection before the last one.
 int select_on_device(sx_ctx* ctx, const sx_result* r, TwoPass& pass, sx_result** out) {
@@ -1148,6 +1182,44 @@ int sx_result_fold_device(sx_ctx* ctx, const sx_result* r, uint32_t flags, sx_re
     Fold fold(r->r.segs.size());
     const int rc = select_on_device(ctx, r, fold, out);
     if (rc == SX_OK && info) *info = fold.info;
+    return rc;
+}
+
+static bool decode_args_ok(uint32_t kind, uint32_t flags) {
+    return kind >= SX_DECODE_BASE64 && kind <= SX_DECODE_PERCENT && !(flags & ~(uint32_t)SX_DECODE_UTF16LE);
+}
+
+int sx_decode_bytes(uint32_t kind, uint32_t flags, const uint8_t* in, uint64_t len, uint8_t* out, uint64_t cap, uint64_t* written, uint64_t* word) {
+    if (written) *written = 0;
+    if (word) *word = 0;
+    if ((!in && len) || !written || !decode_args_ok(kind, flags) || len >> 32) return SX_E_INVALID;
+    uint64_t need = 0;
+    const uint64_t w = decode_measure_string(kind, flags, in, (uint32_t)len, &need);
+    *written = need;
+    if (word) *word = w;
+    if (!out) return SX_OK;            // (the size was asked for)
+    if (need > cap) return SX_E_INVALID;
+    decode_place_string(kind, flags, w, in, (uint32_t)len, out);
+    return SX_OK;
+}
+
+// The words' memory is had as sx_result_measure_device has it, then the fold's two passes: pass 1 writes the words
+int sx_result_decode_device(sx_ctx* ctx, const sx_result* r, uint32_t kind, uint32_t flags, sx_result** out, sx_labels** words, sx_decode_info* info) {
+    if (out) *out = nullptr;
+    if (words) *words = nullptr;
+    if (!ctx || !r || !out) return SX_E_INVALID;
+    if (!decode_args_ok(kind, flags)) { ctx->set_err("decode: a kind other than SX_DECODE_BASE64, SX_DECODE_HEX, SX_DECODE_PERCENT, or a flag other than SX_DECODE_UTF16LE"); return SX_E_INVALID; }
+    if (host_only(ctx, "decode")) return SX_E_STATE;
+    { const int rc = result_on_device(ctx, r, "decode on the host, with sx_decode_bytes"); if (rc != SX_OK) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint64_t bytes = 0;
+    sx_labels* lab = labels_of(ctx, r, &bytes);
+    if (!lab) { ctx->set_err("device decode: no memory for " + std::to_string(bytes) + " bytes of words"); return SX_E_NOMEM; }
+    Decode decode(r->r.segs.size(), kind, flags, lab);
+    const int rc = select_on_device(ctx, r, decode, out);
+    if (rc != SX_OK || !words) sx_labels_free(lab);
+    else *words = lab;
+    if (rc == SX_OK && info) *info = decode.info;
     return rc;
 }
 
